@@ -8,14 +8,24 @@ resident in HBM, replayed from a hipGraph.
         bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0.  Inference shards by clip (independent units, no collective on the data path):
-every rank runs its own 64-clip batch, scaling is "weak".  `roofline` is for the dominant kernel family
-(ts::tcs_split_kernel / ts::tcs_kernel, all 78 launches of a step): algorithmic bytes (ideal fusion, SURVEY 8d) / HIP-event time of the
-encoder segment.  `cpu_baseline` times the CPU oracle (a port of the reference path, fp32 torch-CPU ops) on a bounded sample of the same
-workload on this box's host cores: P worker processes x 16 torch threads over disjoint clips, P swept IN THIS RUN (1, 4, 16 where the host has
-the cores), best aggregate reported with `processes`, `threads`, `host_cores` (started before this process touches the GPU).  The timed steps
-rotate through 5 distinct 64 x 15 s waveform batches (307 MB > the 256 MB Infinity Cache), so the front end reads its input from HBM.
-At N = 1 the same JSON object also carries `extra`: the other BASELINE.json configurations (C3, C4 phases 1 and 2, C5) measured by
-tools/bench_extra.py in the same process, each with its own roofline (and oracle check where affordable); --no-extra skips them.
+every rank runs its own 64-clip batch, scaling is "weak".  The timed steps rotate through 5 distinct 64 x 15 s waveform batches
+(307 MB > the 256 MB Infinity Cache), so the front end reads its input from HBM.  A plain run does only what the headline needs: set-up,
+warm-up, the timed steps, the outputs of the last step (--dump-outputs DIR) and the line (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step`, `config`).
+
+--dump-outputs DIR writes what the last timed step returned on rank 0 -- logits [B, V, T'] (bf16 values, stored as float32), the greedy
+decode's ids [B, T'], collapsed ids [B, T'] (zero past each row's count) and counts [B], all as float32 -- to DIR/<name>.npy; the inputs
+and weights are seeded, so two builds can be compared output for output.
+
+--full adds everything else the benchmark measures or checks, each taking runs of its own.  `roofline` is for the dominant kernel
+family (ts::tcs_split_kernel / ts::tcs_kernel, all 78 launches of a step): algorithmic bytes (ideal fusion, SURVEY 8d) / HIP-event time
+of the encoder segment.  `cpu_baseline` times the CPU oracle (a port of the reference path, fp32 torch-CPU ops) on a bounded sample of the same
+workload on the host cores: P worker processes x 16 torch threads over disjoint clips, P swept IN THIS RUN (1, 4, 16 where the host has
+the cores), best aggregate reported with `processes`, `threads`, `host_cores` (started before this process touches the GPU).  `check`
+compares the first 16 clips of the measured batch with the fp32 oracle, `check_trained` does the same on weights trained first, and
+`predict_api` times `module.predict()`.  The DDP fine-tuning step (`extra.c4_ddp`) runs on every N; at N = 1 the same JSON object also
+carries in `extra` the other BASELINE.json configurations (C3, C4 phases 1 and 2, C5) measured by tools/bench_extra.py in the same
+process, each with its own roofline (and oracle check where affordable); --no-extra skips them.
 """
 from __future__ import annotations
 
@@ -224,6 +234,22 @@ def scaling_block(result, c4_ddp):
     return blk
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, outputs):
+    """The last timed step's outputs as float32 DIR/<name>.npy (every value is exact in float32: bf16 logits, int32 ids and counts below
+    2^24).  A batch whose outputs exceed DUMP_LIMIT_BYTES is cut to its first clips, the same ones in every array."""
+    import numpy as np
+    names = ("logits", "ids", "collapsed", "counts")
+    arrays = [t.float().cpu().numpy() for t in outputs]
+    per_clip = sum(a[0].nbytes for a in arrays)
+    keep = max(1, min(arrays[0].shape[0], DUMP_LIMIT_BYTES // per_clip))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in zip(names, arrays):
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a[:keep]))
+
+
 def parity_check(gpu_logits, ref_logits, gpu_ids, labels_blank=28):
     """HIP logits [n, V, T'] (bf16 activations) vs the fp32 oracle's on the same clips: error relative to the logit scale, argmax
     agreement on the frames the oracle decides by more than 6 sigma of the measured error, and the greedy strings of those clips
@@ -262,7 +288,13 @@ def main():
     ap.add_argument("--no-trained-check", action="store_true", help="skip `check_trained` (training on the box + transcript identity vs the fp32 oracle)")
     ap.add_argument("--no-predict-api", action="store_true", help="skip `predict_api` (module.predict() wall time, graph on / off, C2 and C1 sizes)")
     ap.add_argument("--input-batches", type=int, default=5, help="distinct waveform batches the timed steps rotate through (5 x 61 MB > the 256 MB Infinity Cache)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline, cpu_baseline, check, check_trained, predict_api, extra, scaling_block")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (rank 0) to DIR/<name>.npy as float32")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -280,7 +312,7 @@ def main():
         sys.exit(2)
     # the CPU baseline runs FIRST: its worker processes are children of a process that has not touched the GPU yet
     cpu_sweep = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_sweep = cpu_baseline_sweep(seconds=args.seconds)
     if not torch.cuda.is_available():
         print("bench.py: no GPU visible (this benchmark has no CPU path)", file=sys.stderr)
@@ -326,7 +358,7 @@ def main():
 
     def step(w=None):
         logits, _ = module(wav if w is None else w, lengths)
-        return greedy_decode(logits)
+        return (logits,) + tuple(greedy_decode(logits))
 
     def encoder_only(feats, fl):
         return module.encoder(feats, fl)
@@ -335,23 +367,28 @@ def main():
         for _ in range(2):          # eager warm-up: packs weights, sizes the allocator, sets kernel attributes
             out = step()
         torch.cuda.synchronize()
-        feats, fl = module.audio_transform(wav, lengths)
+        if args.full:
+            feats, fl = module.audio_transform(wav, lengths)
         side = torch.cuda.Stream(device)
         if args.no_graph:
             run_steps = [(lambda w=w: step(w)) for w in wavs]
             run_enc = lambda: encoder_only(feats, fl)
         else:
-            g_steps, g_enc = [torch.cuda.CUDAGraph() for _ in wavs], torch.cuda.CUDAGraph()
+            g_steps, outs = [torch.cuda.CUDAGraph() for _ in wavs], []
             side.wait_stream(torch.cuda.current_stream(device))
             with torch.cuda.stream(side):
                 step()                          # the library's arena buffers are per stream: let this stream's exist (and be zeroed once)
-                encoder_only(feats, fl)         # before the capture, or their one-time zero fill would be replayed with every step
+                if args.full:
+                    encoder_only(feats, fl)     # before the capture, or their one-time zero fill would be replayed with every step
                 for gs_, w in zip(g_steps, wavs):
                     with torch.cuda.graph(gs_, stream=side):
-                        out = step(w)
-                with torch.cuda.graph(g_enc, stream=side):
-                    enc_out = encoder_only(feats, fl)
-            run_steps, run_enc = [gs_.replay for gs_ in g_steps], g_enc.replay
+                        outs.append(step(w))
+                if args.full:
+                    g_enc = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g_enc, stream=side):
+                        enc_out = encoder_only(feats, fl)
+                    run_enc = g_enc.replay
+            run_steps = [gs_.replay for gs_ in g_steps]
         n_in = len(run_steps)
 
         def barrier():
@@ -365,28 +402,26 @@ def main():
         prof_mark.mark(device)                      # profiled runs (TS_PROF_MARK=1): brackets the timed region in the kernel trace
         t0 = time.perf_counter()
         for i in range(args.steps):
-            run_steps[i % n_in]()
+            out = run_steps[i % n_in]()
         torch.cuda.synchronize(); barrier()
         dt = time.perf_counter() - t0
         prof_mark.mark(device)
         dt = max_over_ranks(dt, device, force=dist_on)
+        if args.dump_outputs and rank == 0:
+            # before anything else runs on the device: the last step's outputs may live in the library's per-stream arena
+            dump_outputs(args.dump_outputs, out if args.no_graph else outs[(args.steps - 1) % n_in])
 
-        # dominant kernel family: the fused TCS launches of the encoder, timed with HIP events on the launch stream
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        run_enc(); torch.cuda.synchronize()
-        e0.record()
-        for _ in range(args.steps):
-            run_enc()
-        e1.record(); torch.cuda.synchronize()
-        enc_ms = e0.elapsed_time(e1) / args.steps
+        if args.full:
+            # dominant kernel family: the fused TCS launches of the encoder, timed with HIP events on the launch stream
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            run_enc(); torch.cuda.synchronize()
+            e0.record()
+            for _ in range(args.steps):
+                run_enc()
+            e1.record(); torch.cuda.synchronize()
+            enc_ms = e0.elapsed_time(e1) / args.steps
 
-    layers = encoder_layers(module)
-    n_frames = 16000 * S // 160 + 1
-    alg_bytes, alg_flops, _ = tcs_algorithmic_bytes(layers, B, n_frames)
-    n_launch = len(layers)
-    achieved = alg_bytes / (enc_ms * 1e-3) / 1e9
     value = world * B * S * args.steps / dt
-    traffic, traffic_source = pmc_traffic(B, S)
     result = {
         "metric": "audio-seconds/s (16 kHz) QuartzNet15x5 inference",
         "value": value, "unit": "audio-seconds/s", "n_gpus": world, "rccl_world_size": rccl_world,
@@ -399,14 +434,27 @@ def main():
                                f"QuartzNet15x5 inference, batch {B}x{S} s per GPU (eager launches)",
                    "input_batches_rotated": len(wavs), "input_bytes_rotated": len(wavs) * B * 16000 * S * 4,
                    "batch_per_gpu": B, "clip_seconds": S, "random_init": args.weights == "random", "weights": args.weights, "trained": trained_info},
-        "roofline": {"bound": "hbm", "kernel": "ts::tcs_split_kernel / ts::tcs_kernel (all fused TCS launches of one step)",
-                     "launches_per_step": n_launch,
-                     "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                     "traffic": traffic, "traffic_source": traffic_source,
-                     "algorithmic_bytes_per_launch": alg_bytes / n_launch, "avg_launch_us": enc_ms * 1e3 / n_launch,
-                     "encoder_ms": enc_ms, "mfma_tflops": alg_flops / (enc_ms * 1e-3) / 1e12,
-                     "mfma_frac_of_dense_bf16_peak": alg_flops / (enc_ms * 1e-3) / 1e12 / MFMA_BF16_PEAK_TF},
     }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if dist_on:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    layers = encoder_layers(module)
+    n_frames = 16000 * S // 160 + 1
+    alg_bytes, alg_flops, _ = tcs_algorithmic_bytes(layers, B, n_frames)
+    n_launch = len(layers)
+    achieved = alg_bytes / (enc_ms * 1e-3) / 1e9
+    traffic, traffic_source = pmc_traffic(B, S)
+    result["roofline"] = {"bound": "hbm", "kernel": "ts::tcs_split_kernel / ts::tcs_kernel (all fused TCS launches of one step)",
+                          "launches_per_step": n_launch,
+                          "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                          "traffic": traffic, "traffic_source": traffic_source,
+                          "algorithmic_bytes_per_launch": alg_bytes / n_launch, "avg_launch_us": enc_ms * 1e3 / n_launch,
+                          "encoder_ms": enc_ms, "mfma_tflops": alg_flops / (enc_ms * 1e-3) / 1e12,
+                          "mfma_frac_of_dense_bf16_peak": alg_flops / (enc_ms * 1e-3) / 1e12 / MFMA_BF16_PEAK_TF}
     if rank == 0:
         if not args.no_cpu_baseline and world == 1:
             n_chk = min(16, B)

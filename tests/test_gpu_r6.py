@@ -1,7 +1,8 @@
 """Round-6 GPU tests: BASELINE.json configs[0] at its named size (QuartzNet5x5 predict() on 4 x 10 s) against the fixture made from the real
 reference modules; `predict()` / `forward()` replayed from the module's per-signature hipGraph (same results as eager launches, invalidated
 by weight updates, outputs never aliased); bench.py's multi-rank code path run with ONE rank under torch.distributed.run (RCCL group,
-probe all-reduce, barriers, c4_ddp's exchange, destroy); a block output with a second consumer fails loudly in the training path."""
+probe all-reduce, barriers, c4_ddp's exchange, destroy); a plain bench.py run and its --dump-outputs; a block output with a second consumer
+fails loudly in the training path."""
 import json
 import os
 import sys
@@ -129,7 +130,7 @@ def test_bench_multi_rank_path_runs_with_one_rank_under_torch_distributed_run(tm
     out_path, err_path = tmp_path / "bench.out", tmp_path / "bench.err"
     env = dict(os.environ, TS_BENCH_EXTRA_DEADLINE_S="600")
     with open(out_path, "w") as fo, open(err_path, "w") as fe:
-        rc = launch_ranks(os.path.join(ROOT, "bench.py"), 1, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+        rc = launch_ranks(os.path.join(ROOT, "bench.py"), 1, ["--gpus", "1", "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
                                                                "--no-predict-api", "--extra", "c4_ddp"], timeout_s=900, env=env, stdout=fo, stderr=fe)
     err = err_path.read_text()
     assert rc == 0, err[-3000:]
@@ -142,6 +143,39 @@ def test_bench_multi_rank_path_runs_with_one_rank_under_torch_distributed_run(tm
     assert ddp["process_group"] == "torch.distributed.run" and ddp["n_collectives_per_step"] >= 2
     assert ddp["ms_per_step"] > 0 and np.isfinite(ddp["loss_first_last"]).all()
     assert res["scaling_block"]["n_gpus"] == 1 and res["scaling_block"]["c4_ddp_step_per_s"] == ddp["value"]
+
+
+def test_bench_plain_run_prints_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` run (no --full) times --steps steps and prints the headline fields without the measurements --full adds;
+    --dump-outputs writes the outputs of the LAST timed step (rotation index (steps - 1) % input_batches) as float32, equal to an eager
+    forward of the same seeded model on that input batch."""
+    import subprocess
+    import bench
+    from thunder_speech_amd.module import greedy_decode
+    dump = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1", "--batch", "4",
+                        "--seconds", "2", "--input-batches", "3", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-3000:]
+    res = json.loads(lines[0])
+    assert res["unit"] == "audio-seconds/s" and res["higher_is_better"] is True and res["dtype"] == "bf16" and res["steps"] == 5
+    assert res["ms_per_step"] > 0 and res["value"] == pytest.approx(4 * 2 * 1e3 / res["ms_per_step"], rel=1e-6)
+    assert not {"roofline", "cpu_baseline", "check", "check_trained", "predict_api", "extra", "scaling_block"} & set(res)
+    got = {name: np.load(dump / f"{name}.npy") for name in ("logits", "ids", "collapsed", "counts")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    g = torch.Generator().manual_seed(1234)
+    wavs = [0.1 * torch.randn(4, 32000, generator=g) for _ in range(3)]
+    module = bench.build_model(torch.device("cuda", 0))
+    module.graph_inference = False
+    with torch.no_grad():
+        logits, _ = module(wavs[(5 - 1) % 3].cuda(), torch.full((4,), 32000, dtype=torch.int32, device="cuda"))
+        ids, collapsed, counts = greedy_decode(logits)
+        torch.cuda.synchronize()
+    assert got["logits"].shape == tuple(logits.shape)
+    assert np.array_equal(got["logits"], logits.float().cpu().numpy())
+    for name, t in (("ids", ids), ("collapsed", collapsed), ("counts", counts)):
+        assert np.array_equal(got[name], t.cpu().numpy().astype(np.float32)), name
 
 
 def test_block_output_with_a_second_consumer_fails_loudly_instead_of_dropping_the_residual_gradient():

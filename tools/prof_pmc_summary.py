@@ -21,7 +21,7 @@ if not vals:
 N_CU, SIMD = 256, 4
 out = [f"# Round {R} -- SQ counters of the fused TCS launches (C2 headline step, 64 x 15 s)", "",
        "`bash tools/prof_pmc_tcs.sh` on one MI355X: three `rocprofv3 --pmc` passes (no trace domain beside them) over "
-       "`python3 bench.py --steps 2 --warmup 1 --no-extra --no-cpu-baseline --no-trained-check`; every number is the mean per dispatch of one kernel "
+       "`python3 bench.py --full --steps 2 --warmup 1 --no-extra --no-cpu-baseline --no-trained-check`; every number is the mean per dispatch of one kernel "
        "instantiation (template arguments: NPASS = depthwise tap passes of 12 taps, XJ, MT, WM, DIL, NT, CHAIN, SE).", "",
        "Units (MI355X_MICROARCH.md): `SQ_WAVE_CYCLES`, `SQ_WAIT_*`, `SQ_ACTIVE_INST_*` count quad-cycles summed over waves; `SQ_VALU_MFMA_BUSY_CYCLES` counts "
        "cycles summed over SIMDs.  The kernels are persistent (every wave lives for the whole dispatch), so the dispatch lasts L = 4 x SQ_WAVE_CYCLES / SQ_WAVES "

@@ -60,7 +60,7 @@ if rows:
     bj = last_json("bench")
     if bj:
         json.dump(bj, open(os.path.join(out, f"round{R}_bench.json"), "w"), indent=1)
-        md += ["## C2 headline: `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 100 --warmup 5 --no-extra --no-cpu-baseline --no-trained-check`", "",
+        md += ["## C2 headline: `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 100 --warmup 5 --no-extra --no-cpu-baseline --no-trained-check`", "",
                f"bench line of the profiled run: value {bj['value']:.0f} {bj['unit']}, {bj['ms_per_step']:.3f} ms/step, encoder {bj['roofline']['encoder_ms']:.3f} ms, "
                f"avg_launch_us {bj['roofline']['avg_launch_us']:.1f} (HIP events), roofline.frac {bj['roofline']['frac']:.3f}", ""]
     t, tot = md_table(rows)
@@ -81,7 +81,7 @@ for name in ("fetch", "write"):
     pmc[name] = (agg, cnt)
 if pmc["fetch"][1] and pmc["write"][1]:
     fkb = pmc["fetch"][0] / pmc["fetch"][1]; wkb = pmc["write"][0] / pmc["write"][1]
-    traffic = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over `bench.py --steps 2 --warmup 1 --no-extra --no-cpu-baseline --no-trained-check`, all ts::tcs_* dispatches",
+    traffic = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over `bench.py --full --steps 2 --warmup 1 --no-extra --no-cpu-baseline --no-trained-check`, all ts::tcs_* dispatches",
                "dispatches": pmc["fetch"][1], "fetch_size_kb_per_dispatch": fkb, "write_size_kb_per_dispatch": wkb,
                "gfx950_correction": "FETCH_SIZE x2 (MI355X_MICROARCH.md, HBM section: 128-B requests tallied at 64 B); WRITE_SIZE exact",
                "traffic_bytes_per_launch": fkb * 1024 * 2 + wkb * 1024}
