@@ -4,6 +4,7 @@ surface mirrors the reference (state-dict keys, constructor errors).  No kernel 
 import ctypes
 import os
 import re
+import shutil
 import subprocess
 
 import numpy as np
@@ -44,20 +45,86 @@ def test_library_loads_and_answers_version_queries():
         assert L.ts_time_pitch(t) == _lib.time_pitch(t) and _lib.time_pitch(t) % 128 == 0 and _lib.time_pitch(t) >= t
 
 
-def test_ctypes_structs_match_header_field_order():
+_LAYOUT_PROBE = r'''
+#include <stddef.h>
+#include <stdio.h>
+#include "thunder_speech_amd.h"
+#define CLS(x) (__builtin_classify_type(x) == 5 ? "ptr" : \
+                _Generic((x), float: "f32", int32_t: "i32", int64_t: "i64", uint64_t: "u64", default: "other"))
+int main(void) {
+%s
+  return 0;
+}
+'''
+
+
+def test_ctypes_structs_match_the_c_compilers_layout(tmp_path):
+    """sizeof, offsetof and the type class of every field, as the host C compiler lays the header's structs out."""
     from thunder_speech_amd import _lib
-    src = open(HEADER).read()
-    for struct, cls in (("ts_tcs_desc", _lib.TcsDesc), ("ts_frontend_desc", _lib.FrontendDesc)):
+    from thunder_speech_amd import build as b
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    structs = (("ts_tcs_desc", _lib.TcsDesc), ("ts_frontend_desc", _lib.FrontendDesc), ("ts_wgrad_item", _lib.WgradItem))
+    lines = []
+    for struct, cls in structs:
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), src, flags=re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        names = []
-        for decl in body.split(";"):
-            decl = decl.strip()
-            if not decl:
-                continue
-            for part in decl.split(","):
-                names.append(re.findall(r"([a-z_0-9]+)\s*$", part.strip())[0])
+        names = [re.findall(r"([a-z_0-9]+)\s*$", part.strip())[0] for decl in body.split(";") if decl.strip() for part in decl.split(",")]
         assert names == [f[0] for f in cls._fields_], struct
+        lines.append(f'  {{ static {struct} s; printf("{struct} sizeof %zu\\n", sizeof s);')
+        lines += [f'    printf("{struct} {n} %zu %s\\n", offsetof({struct}, {n}), CLS(s.{n}));' for n in names]
+        lines.append("  }")
+    (tmp_path / "probe.c").write_text(_LAYOUT_PROBE % "\n".join(lines))
+    cc = shutil.which("cc") or shutil.which("gcc") or \
+        os.path.join(os.path.dirname(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")), "..", "lib", "llvm", "bin", "clang")
+    exe = str(tmp_path / "probe")
+    subprocess.run([cc, "-std=c11", "-I", os.path.join(b.ROOT, "include"), "-o", exe, str(tmp_path / "probe.c")], check=True)
+    got = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines()
+    cls_of = {ctypes.c_float: "f32", ctypes.c_int32: "i32", ctypes.c_int64: "i64", ctypes.c_uint64: "u64", ctypes.c_void_p: "ptr"}
+    want = []
+    for struct, cls in structs:
+        want.append(f"{struct} sizeof {ctypes.sizeof(cls)}")
+        want += [f"{struct} {n} {getattr(cls, n).offset} {cls_of[t]}" for n, t in cls._fields_]
+    assert got == want
+
+
+def test_derived_signatures_pin_every_type_mapping():
+    """Read from the header alone (no .so): one entry point per row of the C -> ctypes table."""
+    from thunder_speech_amd import _lib
+    S, P = _lib.SIGNATURES, ctypes.POINTER
+    i32, i64, u64, f32, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_void_p
+    assert len(S) == 119 and list(S) == _lib.EXPORTED_SYMBOLS
+    assert S["ts_abi_version"] == (ctypes.c_int, [])
+    assert S["ts_build_target"][0] is ctypes.c_char_p
+    assert S["ts_time_pitch"] == (ctypes.c_int, [i32])                                      # int
+    assert S["ts_frontend_logmel_ptr"] == (vp, [P(_lib.FrontendDesc), vp])                  # const float* return
+    assert S["ts_frontend_workspace_bytes"][0] is i64
+    assert S["ts_train_pwconv_wgrad_multi_parts"] == (ctypes.c_int, [i32, i32, i32])         # int32_t return
+    assert S["ts_tcs_subblock_fwd"] == (ctypes.c_int, [P(_lib.TcsDesc)] + [vp] * 6)
+    assert S["ts_train_pwconv_wgrad_multi"][1] == [P(_lib.WgradItem), i32, vp]
+    args = S["ts_train_dropout"][1]
+    assert args[5] is f32 and args[6] is u64 and args[2] is i64
+    assert len(S["ts_gemm_f32"][1]) == 23 and S["ts_gemm_f32"][1][:2] == [vp, i64]
+    assert S["ts_train_wgrad_reduce_multi"][1] == [vp, vp, vp, vp, i32, vp]                   # void* const*, const int64_t*
+    assert S["ts_w2v_mask_embed"][1][1] is vp                                               # const uint8_t*
+    assert (_lib.ABI_VERSION, _lib.TS_EINVAL, _lib.TS_EUNSUPPORTED, _lib.GUARD_BYTES) == (11, -1, -2, 1024)
+    assert (_lib.TCS_IN_TAILZERO, _lib.TCS_OUT_ZERO_TAIL, _lib.TCS_TAPS_PHASE) == (1, 2, 4)
+
+
+def test_header_reader_on_snippets():
+    from thunder_speech_amd._lib import read_header
+    sigs, structs, defines = read_header("""
+        #define TS_ANSWER (-42)  /* a constant */
+        typedef struct ts_pair { const void *a, *b; int32_t n, m; } ts_pair;
+        int64_t ts_split(const ts_pair* p,   /* a comment, (with parentheses) */
+                         uint64_t seed, // a line comment
+                         void* stream);
+    """)
+    assert defines == {"TS_ANSWER": -42}
+    assert [(n, t) for n, t in structs["ts_pair"]._fields_] == [("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("n", ctypes.c_int32), ("m", ctypes.c_int32)]
+    assert sigs == {"ts_split": (ctypes.c_int64, [ctypes.POINTER(structs["ts_pair"]), ctypes.c_uint64, ctypes.c_void_p])}
+    with pytest.raises(ValueError, match=r"ts_sized.*size_t"):
+        read_header("int ts_sized(const void* p, size_t n);")
+    with pytest.raises(ValueError, match=r"ts_wide.*double"):
+        read_header("double ts_wide(void);")
 
 
 def test_pack_pw_frags_layout():
