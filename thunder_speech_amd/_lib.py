@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/thunder_speech_amd.h.
+"""ctypes binding of the C ABI declared in include/thunder_speech_amd.h and its companion include/thunder_speech_amd_wavlm.h.
 
 The header is the only copy of the ABI: `read_header` derives every prototype, struct and TS_* constant from it and
 `lib()` applies the result, so a new entry point needs the header and its .hip definition and nothing here.  A C type
@@ -17,6 +17,7 @@ from typing import Optional
 from .build import ROOT, lib_path
 
 HEADER = os.path.join(ROOT, "include", "thunder_speech_amd.h")
+WAVLM_HEADER = os.path.join(ROOT, "include", "thunder_speech_amd_wavlm.h")    # companion ABI, versioned on its own
 
 # Parameters and struct fields: these scalars, `const <struct>*` as POINTER(struct), every other pointer to one of
 # _POINTEES (const or not, any depth) as c_void_p.  Return types: _RETURNS only.
@@ -67,14 +68,17 @@ def read_header(text: str):
     return signatures, structs, defines
 
 
-def _read_installed_header():
-    if not os.path.exists(HEADER):
-        raise RuntimeError(f"thunder_speech_amd: the C header {HEADER} is missing; the ctypes binding is derived from it")
-    with open(HEADER) as f:
+def _read_installed_header(path: str = HEADER):
+    if not os.path.exists(path):
+        raise RuntimeError(f"thunder_speech_amd: the C header {path} is missing; the ctypes binding is derived from it")
+    with open(path) as f:
         return read_header(f.read())
 
 
 SIGNATURES, STRUCTS, DEFINES = _read_installed_header()
+# the companion header declares no structs; its entry points are applied next to the core ones but are not part of SIGNATURES
+WAVLM_SIGNATURES, _, WAVLM_DEFINES = _read_installed_header(WAVLM_HEADER)
+WAVLM_ABI_VERSION = WAVLM_DEFINES["TS_WAVLM_ABI_VERSION"]
 TcsDesc, FrontendDesc, WgradItem = STRUCTS["ts_tcs_desc"], STRUCTS["ts_frontend_desc"], STRUCTS["ts_wgrad_item"]
 EXPORTED_SYMBOLS = list(SIGNATURES)
 ABI_VERSION = DEFINES["TS_ABI_VERSION"]
@@ -101,15 +105,18 @@ def lib() -> C.CDLL:
             "`python -m thunder_speech_amd.build` (needs hipcc / ROCm); there is no CPU fallback.")
     import torch  # noqa: F401  -- must initialise its bundled HIP runtime BEFORE our code object is loaded
     L = C.CDLL(path)
-    missing = [s for s in EXPORTED_SYMBOLS if not hasattr(L, s)]
+    missing = [s for s in EXPORTED_SYMBOLS + list(WAVLM_SIGNATURES) if not hasattr(L, s)]
     if missing:
         raise RuntimeError(f"thunder_speech_amd: {path} does not export {missing}; rebuild it")
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **WAVLM_SIGNATURES}.items():
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     if L.ts_abi_version() != ABI_VERSION:
         raise RuntimeError(f"thunder_speech_amd: {path} reports ABI {L.ts_abi_version()}, the header {HEADER} "
                            f"declares {ABI_VERSION}; rebuild it")
+    if L.ts_wavlm_abi_version() != WAVLM_ABI_VERSION:
+        raise RuntimeError(f"thunder_speech_amd: {path} reports WavLM ABI {L.ts_wavlm_abi_version()}, the header {WAVLM_HEADER} "
+                           f"declares {WAVLM_ABI_VERSION}; rebuild it")
     _lib = L
     return L
 

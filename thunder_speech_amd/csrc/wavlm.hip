@@ -1,0 +1,342 @@
+// WavLM's gated relative-position attention (transformers modeling_wavlm.py WavLMAttention.forward / compute_bias /
+// _relative_positions_bucket, reached from huggingface/compatibility.py:31-42 for a WavLM checkpoint).  Declared in
+// include/thunder_speech_amd_wavlm.h; everything around the attention core is the wav2vec2 sequence of csrc/w2v_enc.hip.
+//
+//   ts_wavlm_rel_bias        rb[h][d + t - 1] = E[bucket(d)][h] for d in [-(t - 1), t - 1]: the [H][2t - 1] diagonals of the
+//                            position bias, never the [T][T] matrix; the bucket table is built on the host (float32 log there)
+//   ts_wavlm_attention_fwd   softmax(q k^T / sqrt(hd) + gate[b][h][i] rb[h][j - i + t - 1] + key mask) v, the gate computed from
+//                            the attention's input rows: p = x_h Wg^T + bg, gate = sigmoid(p0..3) (sigmoid(p4..7) const[h] - 1) + 2
+//     precision 1, hd 64:   wavlm_flash_attn_kernel, w2v_flash_attn_kernel with the gate in the prologue and the bias window of the
+//                            tile staged in LDS next to K / V; the [T][T] scores are never stored
+//     precision 0:          scores from the f32 GEMM, one row kernel (gate, bias, mask, softmax), P V on the f32 GEMM
+#include "ts_common.hpp"
+#include "thunder_speech_amd_wavlm.h"
+
+namespace ts {
+
+int gemm_f32(hipStream_t stream, bool in_bf16, const void* a, long long a_rs, long long a_cs, long long sa, long long ska, const void* b,
+             long long b_rs, long long b_cs, long long sb, long long skb, void* c, long long ldc, long long sc, bool out_bf16, const float* bias,
+             int M, int N, int K, int nkb, int batch, bool beta);
+
+__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + __expf(-x)); }
+
+// gate = sigmoid(p0 + p1 + p2 + p3) (sigmoid(p4 + p5 + p6 + p7) const - 1) + 2 from the 8 projections p (bias included)
+__device__ __forceinline__ float wavlm_gate(const float* p, float cst) {
+  const float a = sigmoid_f(((p[0] + p[1]) + p[2]) + p[3]);
+  const float g = sigmoid_f(((p[4] + p[5]) + p[6]) + p[7]);
+  return a * (g * cst - 1.f) + 2.f;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// position bias diagonals: one thread per (head, d)
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void wavlm_rel_bias_kernel(const float* __restrict__ embed, const int* __restrict__ abs_bucket, int nb, int md,
+                                                             int heads, int t, float* __restrict__ rb) {
+  const int n = 2 * t - 1, h = blockIdx.y;
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const int d = j - (t - 1);
+  const int ad = d < 0 ? -d : d;
+  int bucket = (d > 0 ? nb / 2 : 0) + abs_bucket[ad < md ? ad : md];
+  bucket = bucket < 0 ? 0 : (bucket < nb ? bucket : nb - 1);     // a malformed table cannot read outside E
+  rb[(size_t)h * n + j] = embed[(size_t)bucket * heads + h];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// precision 0: gate + bias + key mask + softmax over one row of scores [B][H][T][T] per wavefront, in place
+// ---------------------------------------------------------------------------------------------------------------------
+struct WlRowArgs {
+  float* s;                        // [B][H][T][T] raw q . k
+  const int* key_len;
+  const float* gx;                 // gate input f32 [B][T][ld]
+  long long ld;
+  const float* wg;                 // [8][hd]
+  const float* bg;                 // [8]
+  const float* cst;                // [H]
+  const float* rb;                 // [H][2T - 1]
+  int heads, t, hd;
+  float scale;
+};
+
+__global__ __launch_bounds__(256) void wavlm_softmax_kernel(const WlRowArgs a) {
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);     // (head, query) within clip b
+  const int lane = threadIdx.x & 63, b = blockIdx.y;
+  if (row >= (long long)a.heads * a.t) return;
+  const int h = (int)(row / a.t), i = (int)(row - (long long)h * a.t);
+  const float* x = a.gx + ((size_t)b * a.t + i) * a.ld + (size_t)h * a.hd;
+  float p[8];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) p[r] = 0.f;
+  for (int d = lane; d < a.hd; d += 64) {
+    const float xv = x[d];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) p[r] = fmaf(xv, a.wg[r * a.hd + d], p[r]);
+  }
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    for (int o = 32; o > 0; o >>= 1) p[r] += __shfl_xor(p[r], o);
+    p[r] += a.bg[r];
+  }
+  const float gate = wavlm_gate(p, a.cst[h]);
+  const float* bias = a.rb + (size_t)h * (2 * a.t - 1) + (a.t - 1 - i);     // bias[j] = rb[h][j - i + t - 1]
+  float* s = a.s + ((size_t)b * a.heads * a.t + row) * a.t;
+  const int n = a.key_len ? (a.key_len[b] < a.t ? (a.key_len[b] < 0 ? 0 : a.key_len[b]) : a.t) : a.t;
+  const int lim = n > 0 ? n : a.t;                    // no valid key: the softmax runs over all keys (as ts_w2v_attention_fwd)
+  float m = -3.0e38f;
+  for (int j = lane; j < lim; j += 64) {
+    const float v = fmaf(s[j], a.scale, gate * bias[j]);
+    s[j] = v;
+    m = fmaxf(m, v);
+  }
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  float z = 0.f;
+  for (int j = lane; j < lim; j += 64) z += __expf(s[j] - m);
+  for (int o = 32; o > 0; o >>= 1) z += __shfl_xor(z, o);
+  const float rz = 1.f / z;
+  for (int j = lane; j < a.t; j += 64) s[j] = j < lim ? __expf(s[j] - m) * rz : 0.f;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Fused gated-bias attention (precision 1, head_dim 64): w2v_flash_attn_kernel (csrc/w2v_enc.hip) plus
+//   * the gate of the lane's query in the prologue: lane half h2 dots d = 32 h2 .. 32 h2 + 31 of the query's input row with the
+//     8 x 64 weights (staged in LDS once), one exchange with lane ^ 32 completes the 8 projections;
+//   * per 64-key tile the 191 diagonals rb[h][key - query + t - 1] the 128 x 64 tile touches, staged in LDS next to K and V;
+//   * the full logit s scale + gate rb (log2 units) formed BEFORE the running maximum: with a bias the maximum no longer
+//     commutes with the scale, so the scaled-max shortcut of the wav2vec2 kernel is gone.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int WA_KT = 64;          // keys per staged tile
+constexpr int WA_PITCH = 144;      // bytes per staged K / V row (64 bf16 + 16)
+constexpr int WA_QW = 128;         // queries per workgroup
+constexpr int WA_WIN = WA_QW + WA_KT;   // 191 diagonals per tile, rounded up
+
+struct WaArgs {
+  const unsigned short* qkv;       // [B][T][3C] bf16
+  unsigned short* ctx;             // [B][T][C] bf16
+  const int* key_len;
+  const unsigned short* gx;        // gate input bf16 [B][T][ld]
+  long long ld;
+  const float* wg;                 // [8][64]
+  const float* bg;                 // [8]
+  const float* cst;                // [H]
+  const float* rb;                 // [H][2T - 1]
+  int t, c;
+  float scale_log2e;
+};
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void wavlm_flash_attn_kernel(const WaArgs a) {
+  __shared__ __attribute__((aligned(16))) char ks_[WA_KT * WA_PITCH];
+  __shared__ __attribute__((aligned(16))) char vs_[WA_KT * WA_PITCH];
+  __shared__ __attribute__((aligned(16))) float rbs[WA_WIN];
+  __shared__ __attribute__((aligned(16))) float wgs[8 * 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.z, head = blockIdx.y;
+  const int qw0 = blockIdx.x * WA_QW, q0 = qw0 + wave * 32;
+  const size_t rowp = (size_t)3 * a.c;
+  const unsigned short* base = a.qkv + (size_t)b * a.t * rowp + (size_t)head * 64;
+  int lim = a.t;
+  if (a.key_len) {
+    const int n = a.key_len[b] < a.t ? a.key_len[b] : a.t;
+    lim = n > 0 ? n : a.t;                       // no valid key: the reference's softmax degenerates to all keys
+  }
+  const int half = lane >> 5, n32 = lane & 31;
+  const int qrow = q0 + n32 < a.t ? q0 + n32 : a.t - 1;
+  s16x8 qf[4];
+  {
+    const uint4* qp = reinterpret_cast<const uint4*>(base + (size_t)qrow * rowp + 8 * half);
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = __builtin_bit_cast(s16x8, qp[2 * ks]);
+  }
+  // ---- gate of this lane's query, in log2 units ----
+  *reinterpret_cast<f32x2*>(wgs + 2 * tid) = *reinterpret_cast<const f32x2*>(a.wg + 2 * tid);
+  __syncthreads();
+  float gl;
+  {
+    const uint4* xp = reinterpret_cast<const uint4*>(a.gx + ((size_t)b * a.t + qrow) * a.ld + (size_t)head * 64 + 32 * half);
+    float p[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) p[r] = 0.f;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const uint4 u = xp[v];
+      const unsigned w4[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float x0 = bf16_lo(w4[e]), x1 = bf16_hi(w4[e]);
+        const int d = 32 * half + 8 * v + 2 * e;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+          const f32x2 w = *reinterpret_cast<const f32x2*>(wgs + r * 64 + d);
+          p[r] = fmaf(x1, w[1], fmaf(x0, w[0], p[r]));
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 8; ++r) p[r] += __shfl_xor(p[r], 32) + a.bg[r];
+    gl = wavlm_gate(p, a.cst[head]) * 1.4426950408889634f;
+  }
+  const float* rbh = a.rb + (size_t)head * (2 * a.t - 1);
+  f32x16 o[2];
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) o[mt][i] = 0.f;
+  float m_run = -INFINITY, l_run = 0.f;
+  const int pm = (n32 & ~12) | ((n32 & 4) << 1) | ((n32 & 8) >> 1);          // K row order: bits 2 and 3 swapped
+  const int q4 = (lane >> 2) & 3, gq = (lane >> 4) & 1, p4 = lane & 3;
+  const int v_off = (8 * half + q4) * WA_PITCH + (16 * gq + 4 * p4) * 2;     // transposing read of the V tile
+  // window slot of (key k0 + kk, query qw0 + qq) is kk - qq + WA_QW - 1; this lane's query is qq = 32 wave + n32
+  const int wbase = WA_QW - 1 - (wave * 32 + n32) + 8 * half;
+
+  for (int k0 = 0; k0 < lim; k0 += WA_KT) {
+    __syncthreads();                                                          // the previous tile has been consumed
+#pragma unroll
+    for (int rep = 0; rep < 2; ++rep) {
+      const int chunk = tid + 256 * rep, r = chunk >> 3, cc = chunk & 7;
+      const int key = k0 + r < a.t ? k0 + r : a.t - 1;
+      const unsigned short* src = base + (size_t)key * rowp + cc * 8;
+      *reinterpret_cast<uint4*>(ks_ + r * WA_PITCH + cc * 16) = *reinterpret_cast<const uint4*>(src + a.c);
+      *reinterpret_cast<uint4*>(vs_ + r * WA_PITCH + cc * 16) = *reinterpret_cast<const uint4*>(src + 2 * a.c);
+    }
+    if (tid < WA_WIN) {
+      // diagonal d = k0 - qw0 - (WA_QW - 1) + tid; slots outside [-(t - 1), t - 1] belong to clamped keys / queries (never stored)
+      int j = k0 - qw0 - (WA_QW - 1) + tid + a.t - 1;
+      j = j < 0 ? 0 : (j > 2 * a.t - 2 ? 2 * a.t - 2 : j);
+      rbs[tid] = rbh[j];
+    }
+    __syncthreads();
+    const bool full = k0 + WA_KT <= lim;                                      // no masked key in this tile (uniform)
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub) {
+      if (k0 + sub * 32 >= lim) break;                                        // uniform: nothing but masked keys
+      f32x16 s;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) s[i] = 0.f;
+      const char* kr = ks_ + (sub * 32 + pm) * WA_PITCH + half * 16;
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks)
+        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const s16x8*>(kr + ks * 32), qf[ks], s, 0, 0, 0);
+      // accumulator register i <-> key k0 + 32 sub + 16 (i / 8) + 8 half + i % 8
+      const float* wr = rbs + wbase + 32 * sub;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) s[i] = fmaf(s[i], a.scale_log2e, gl * wr[16 * (i >> 3) + (i & 7)]);
+      if (!full) {
+        const int kbase = k0 + sub * 32 + 8 * half;
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+          if (kbase + 16 * (i >> 3) + (i & 7) >= lim) s[i] = -INFINITY;
+      }
+      float mx = s[0];
+#pragma unroll
+      for (int i = 1; i < 16; ++i) mx = fmaxf(mx, s[i]);
+      mx = fmaxf(mx, __shfl_xor(mx, 32));
+      const float m_new = fmaxf(m_run, mx);                                   // finite: the first sub-tile holds key 0
+      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+      float rs = 0.f;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) { s[i] = __builtin_amdgcn_exp2f(s[i] - m_new); rs += s[i]; }
+      l_run = l_run * alpha + rs;
+      m_run = m_new;
+      if (__any(alpha != 1.f)) {
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) o[mt][i] *= alpha;
+      }
+#pragma unroll
+      for (int ks2 = 0; ks2 < 2; ++ks2) {
+        const unsigned p01 = pack_bf16(s[8 * ks2 + 0], s[8 * ks2 + 1]), p23 = pack_bf16(s[8 * ks2 + 2], s[8 * ks2 + 3]);
+        const unsigned p45 = pack_bf16(s[8 * ks2 + 4], s[8 * ks2 + 5]), p67 = pack_bf16(s[8 * ks2 + 6], s[8 * ks2 + 7]);
+        const s16x8 pb = __builtin_bit_cast(s16x8, uint4{p01, p23, p45, p67});
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+          const char* va = vs_ + (sub * 32 + 16 * ks2) * WA_PITCH + v_off + 64 * mt;
+          const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((TS_LDS s16x4*)((TS_LDS char*)va));
+          const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((TS_LDS s16x4*)((TS_LDS char*)va + 4 * WA_PITCH));
+          const s16x8 vf = s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+          o[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pb, o[mt], 0, 0, 0);
+        }
+      }
+    }
+  }
+  const float l = l_run + __shfl_xor(l_run, 32);
+  const float inv = 1.f / l;
+  const int query = q0 + n32;
+  if (query < a.t) {
+    unsigned short* dst = a.ctx + ((size_t)b * a.t + query) * a.c + (size_t)head * 64 + 4 * half;
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g)       // accumulator registers 4g .. 4g+3 <-> d = 32 mt + 8 g + 4 half + 0..3
+        *reinterpret_cast<uint2*>(dst + 32 * mt + 8 * g) =
+            uint2{pack_bf16(o[mt][4 * g] * inv, o[mt][4 * g + 1] * inv), pack_bf16(o[mt][4 * g + 2] * inv, o[mt][4 * g + 3] * inv)};
+  }
+}
+
+}  // namespace ts
+
+using namespace ts;
+
+extern "C" int ts_wavlm_abi_version(void) { return TS_WAVLM_ABI_VERSION; }
+
+extern "C" int ts_wavlm_rel_bias(const float* embed, const int32_t* abs_bucket, int32_t num_buckets, int32_t max_distance, int32_t heads,
+                                 int32_t t, float* rel_bias, void* stream_) {
+  if (!embed || !abs_bucket || !rel_bias || num_buckets < 2 || max_distance < 0 || heads <= 0 || t <= 0) return TS_EINVAL;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(wavlm_rel_bias_kernel, dim3((unsigned)((2LL * t - 1 + 255) / 256), heads), dim3(256), 0, stream, embed, abs_bucket,
+                     num_buckets, max_distance, heads, t, rel_bias);
+  return hip_status(hipGetLastError());
+}
+
+extern "C" int64_t ts_wavlm_attention_workspace_bytes(int32_t batch, int32_t t, int32_t heads, int32_t precision) {
+  if (batch <= 0 || t <= 0 || heads <= 0) return TS_EINVAL;
+  if (precision < 0 || precision > 1) return TS_EUNSUPPORTED;
+  return precision ? 0 : (int64_t)batch * heads * t * t * (int64_t)sizeof(float);
+}
+
+extern "C" int ts_wavlm_attention_fwd(const void* qkv, int32_t batch, int32_t t, int32_t c, int32_t heads, const int32_t* key_len,
+                                      int32_t precision, const void* gate_x, int64_t ld_gate_x, const float* gate_w, const float* gate_b,
+                                      const float* gate_const, const float* rel_bias, void* ctx, void* workspace, void* stream_) {
+  if (!qkv || !ctx || !gate_x || !gate_w || !gate_b || !gate_const || !rel_bias || batch <= 0 || t <= 0 || c <= 0 || heads <= 0 || c % heads ||
+      ld_gate_x < c)
+    return TS_EINVAL;
+  if (precision < 0 || precision > 1) return TS_EUNSUPPORTED;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  (void)hipGetLastError();
+  const int hd = c / heads;
+  if (precision) {
+    if (hd != 64 || ld_gate_x % 8 || (reinterpret_cast<uintptr_t>(gate_x) & 15) || (reinterpret_cast<uintptr_t>(qkv) & 15) ||
+        (reinterpret_cast<uintptr_t>(gate_w) & 7))
+      return TS_EUNSUPPORTED;
+    WaArgs w{};
+    w.qkv = static_cast<const unsigned short*>(qkv); w.ctx = static_cast<unsigned short*>(ctx); w.key_len = key_len;
+    w.gx = static_cast<const unsigned short*>(gate_x); w.ld = ld_gate_x;
+    w.wg = gate_w; w.bg = gate_b; w.cst = gate_const; w.rb = rel_bias;
+    w.t = t; w.c = c; w.scale_log2e = 1.4426950408889634f / sqrtf((float)hd);
+    hipLaunchKernelGGL(wavlm_flash_attn_kernel, dim3((t + WA_QW - 1) / WA_QW, heads, batch), dim3(256), 0, stream, w);
+    return hip_status(hipGetLastError());
+  }
+  if (!workspace) return TS_EINVAL;
+  float* s = static_cast<float*>(workspace);
+  const float* q = static_cast<const float*>(qkv);
+  for (int b = 0; b < batch; ++b) {
+    const float* qb = q + (size_t)b * t * 3 * c;
+    // scores[query][key] = q . k, batched over the heads (head h = columns [h hd, (h+1) hd) of each third of a qkv row)
+    if (int st = gemm_f32(stream, false, qb, 3LL * c, 1, hd, 0, qb + c, 1, 3LL * c, hd, 0, s + (size_t)b * heads * t * t, t, (long long)t * t,
+                          false, nullptr, t, t, hd, 1, heads, false))
+      return st;
+  }
+  WlRowArgs r{};
+  r.s = s; r.key_len = key_len; r.gx = static_cast<const float*>(gate_x); r.ld = ld_gate_x; r.wg = gate_w; r.bg = gate_b; r.cst = gate_const;
+  r.rb = rel_bias; r.heads = heads; r.t = t; r.hd = hd; r.scale = 1.f / sqrtf((float)hd);
+  hipLaunchKernelGGL(wavlm_softmax_kernel, dim3((unsigned)(((long long)heads * t + 3) / 4), batch), dim3(256), 0, stream, r);
+  for (int b = 0; b < batch; ++b) {
+    const float* v = q + (size_t)b * t * 3 * c + 2 * c;
+    float* out = static_cast<float*>(ctx) + (size_t)b * t * c;
+    // ctx[query][d] = sum_key p[query][key] v[key][d], batched over the heads
+    if (int st = gemm_f32(stream, false, s + (size_t)b * heads * t * t, t, 1, (long long)t * t, 0, v, 3LL * c, 1, hd, 0, out, c, hd, false, nullptr,
+                          t, hd, t, 1, heads, false))
+      return st;
+  }
+  return hip_status(hipGetLastError());
+}

@@ -6,9 +6,11 @@ src/thunder/huggingface/compatibility.py:31-42: `self.original_encoder(audio, at
 weights (same attribute name `original_encoder`, same state-dict keys, so checkpoints and fine-tuning code see no
 difference); the arithmetic runs in `Wav2Vec2Plan`, which keeps packed fp32 device copies of the weights and issues one C-ABI
 call per stage.  Both published families (group-norm / post-LN: wav2vec2-base-960h, -large-960h; layer-norm / pre-LN: -large-lv60, xlsr);
-training mode (fine-tuning with the conv feature extractor frozen) runs through huggingface/train.py; no CPU fallback."""
+WavLM runs the same sequence with its gated relative-position attention (csrc/wavlm.hip, include/thunder_speech_amd_wavlm.h) in place of
+the wav2vec2 one (inference only); training mode (fine-tuning with the conv feature extractor frozen) runs through huggingface/train.py; no CPU fallback."""
 from __future__ import annotations
 
+import math
 import os
 
 import ctypes as C
@@ -20,7 +22,7 @@ from torch import nn
 from .. import _lib, tensors as _t
 from ..blocks import _PackedCache
 
-__all__ = ["Wav2Vec2Plan", "HuggingFaceEncoderAdapt", "feat_extract_output_lengths"]
+__all__ = ["Wav2Vec2Plan", "HuggingFaceEncoderAdapt", "feat_extract_output_lengths", "relative_position_bucket", "wavlm_bucket_table"]
 
 
 def feat_extract_output_lengths(conv_kernel, conv_stride, lengths: torch.Tensor, adapter_layers: int = 0, adapter_stride: int = 2) -> torch.Tensor:
@@ -38,9 +40,33 @@ def feat_extract_output_lengths(conv_kernel, conv_stride, lengths: torch.Tensor,
 # families), hubert (the same layers; the feature projection's LayerNorm is optional) and data2vec-audio (the reference's own test,
 # tests/huggingface/test_module_huggingface.py:107-110: layer-norm conv feature extractor, post-LN encoder, the positional embedding as a
 # stack of grouped convs each followed by an affine-free LayerNorm and GELU); unispeech / unispeech-sat (UniSpeechModel / UniSpeechSatModel run the wav2vec2
-# encoder arithmetic unchanged: tests/test_oracle_w2v.py checks the oracle against both).  Others (wavlm's gated relative-position attention, sew's
-# squeezed encoder, wav2vec2-conformer ...) have layers this library holds no kernels for and raise.
-SUPPORTED_MODEL_TYPES = ("wav2vec2", "hubert", "data2vec-audio", "unispeech", "unispeech-sat")
+# encoder arithmetic unchanged: tests/test_oracle_w2v.py checks the oracle against both); wavlm (base / base-plus: group norm, post-LN; large: layer
+# norm, pre-LN): the wav2vec2 layers with WavLMAttention's gated relative-position bias in the attention core (csrc/wavlm.hip, head_dim 64 -- every
+# published WavLM -- inference only).  Others (sew's squeezed encoder, wav2vec2-conformer ...) have layers this library holds no kernels for and raise.
+SUPPORTED_MODEL_TYPES = ("wav2vec2", "hubert", "data2vec-audio", "unispeech", "unispeech-sat", "wavlm")
+
+
+def relative_position_bucket(relative_positions: torch.Tensor, num_buckets: int, max_distance: int) -> torch.Tensor:
+    """WavLMAttention._relative_positions_bucket (transformers modeling_wavlm.py) restated op for op: the same float32 torch operations in the
+    same order, so the bucket boundaries of the log branch fall where transformers puts them (a device logf one ulp away would move some)."""
+    num_buckets = num_buckets // 2
+    relative_buckets = (relative_positions > 0).to(torch.long) * num_buckets
+    relative_positions = torch.abs(relative_positions)
+    max_exact = num_buckets // 2
+    is_small = relative_positions < max_exact
+    if_large = torch.log(relative_positions.float() / max_exact)
+    if_large = if_large / math.log(max_distance / max_exact)
+    if_large = if_large * (num_buckets - max_exact)
+    if_large = (max_exact + if_large).to(torch.long)
+    if_large = torch.min(if_large, torch.full_like(if_large, num_buckets - 1))
+    relative_buckets += torch.where(is_small, relative_positions, if_large)
+    return relative_buckets
+
+
+def wavlm_bucket_table(num_buckets: int, max_distance: int) -> torch.Tensor:
+    """int32 [max_distance + 1]: the bucket of d = -|d| (no sign offset) for 0 <= |d| <= max_distance -- the `abs_bucket` table of ts_wavlm_rel_bias,
+    which adds the offset of d > 0 and clamps |d| to max_distance on the device (every |d| >= max_distance lands in bucket num_buckets / 2 - 1)."""
+    return relative_position_bucket(-torch.arange(max_distance + 1, dtype=torch.long), num_buckets, max_distance).to(torch.int32)
 
 
 def _check_config(cfg) -> None:
@@ -55,6 +81,9 @@ def _check_config(cfg) -> None:
         bad.append("activation != gelu")
     if getattr(cfg, "position_embeddings_type", None) not in (None, "absolute") and hasattr(cfg, "position_embeddings_type"):
         bad.append(f"position_embeddings_type={cfg.position_embeddings_type!r}")
+    if getattr(cfg, "model_type", "wav2vec2") == "wavlm" and int(cfg.hidden_size) != 64 * int(cfg.num_attention_heads):
+        bad.append(f"model_type='wavlm' with head_dim={int(cfg.hidden_size) // int(cfg.num_attention_heads)} (the gated relative-position attention "
+                   "kernels take head_dim 64, as every published WavLM)")
     if bad:
         raise NotImplementedError("wav2vec2 HIP path: unsupported configuration: " + ", ".join(bad))
 
@@ -85,6 +114,7 @@ class Wav2Vec2Plan:
         self.eps = float(cfg.layer_norm_eps)
         self.model_type = getattr(cfg, "model_type", "wav2vec2")
         self.d2v = self.model_type == "data2vec-audio"
+        self.wavlm = self.model_type == "wavlm"
         # lv60 / xlsr family; Data2VecAudioConvLayer is always conv -> LayerNorm -> GELU and its config carries no feat_extract_norm
         self.layer_norm_convs = self.d2v or getattr(cfg, "feat_extract_norm", "group") == "layer"
         self.stable_ln = bool(getattr(cfg, "do_stable_layer_norm", False))
@@ -147,6 +177,15 @@ class Wav2Vec2Plan:
                 w1=gw(f(q + "feed_forward.intermediate_dense.weight")), b1=f(q + "feed_forward.intermediate_dense.bias"),
                 w2=gw(f(q + "feed_forward.output_dense.weight")), b2=f(q + "feed_forward.output_dense.bias"),
                 ln2=(f(q + "final_layer_norm.weight"), f(q + "final_layer_norm.bias"))))
+            if self.wavlm:
+                # WavLMAttention's gate: gru_rel_pos_linear [8][64] + bias, gru_rel_pos_const [1][H][1][1] -> [H]
+                self.layers[-1].update(gate_w=f(q + "attention.gru_rel_pos_linear.weight"), gate_b=f(q + "attention.gru_rel_pos_linear.bias"),
+                                       gate_const=f(q + "attention.gru_rel_pos_const").reshape(-1).contiguous())
+        if self.wavlm:
+            # the position bias is layer 0's (compute_bias once per forward, reused by every layer): its embedding and the t-independent bucket table
+            self.nb, self.md = int(cfg.num_buckets), int(cfg.max_bucket_distance)
+            self.rel_embed = f("encoder.layers.0.attention.rel_attn_embed.weight")                      # [num_buckets][H]
+            self.abs_bucket = wavlm_bucket_table(self.nb, self.md).to(self.device).contiguous()
 
     def _frag(self, w: torch.Tensor):
         """The bf16 GEMM weight `w` [n][k] in MFMA B-fragment order (ts_gemm_nt_pack_w), packed once per weight: the GEMM kernel then
@@ -288,11 +327,24 @@ class Wav2Vec2Plan:
             _lib.check(L.ts_w2v_posconv_fwd(h.data_ptr(), b, t, c, self.pos_w.data_ptr(), self.pos_b.data_ptr(), self.kpos, self.groups,
                                             self.prec, hp.data_ptr(), None, ws.data_ptr(), stream), "ts_w2v_posconv_fwd")
         del ws
-        att_ws = self._buf(L.ts_w2v_attention_workspace_bytes(b, t, self.heads, self.prec), dtype=torch.uint8)
+        if self.wavlm:
+            att_ws = self._buf(L.ts_wavlm_attention_workspace_bytes(b, t, self.heads, self.prec), dtype=torch.uint8)
+            rel_bias = self._buf(self.heads, 2 * t - 1)
+            _lib.check(L.ts_wavlm_rel_bias(self.rel_embed.data_ptr(), self.abs_bucket.data_ptr(), self.nb, self.md, self.heads, t,
+                                           rel_bias.data_ptr(), stream), "ts_wavlm_rel_bias")
+        else:
+            att_ws = self._buf(L.ts_w2v_attention_workspace_bytes(b, t, self.heads, self.prec), dtype=torch.uint8)
 
         def attention(x_op):
+            # x_op: the attention's input as the QKV GEMM reads it -- WavLM's gate is computed from the same rows
             _, qkv_op = self._linear(L, stream, x_op, lw["wqkv"], lw["bqkv"], want_op=True)
             ctx_op = self._buf(b, t, c, dtype=torch.bfloat16 if self.prec else torch.float32)
+            if self.wavlm:
+                _lib.check(L.ts_wavlm_attention_fwd(qkv_op.data_ptr(), b, t, c, self.heads, self._ptr(key_len), self.prec, x_op.data_ptr(), c,
+                                                    lw["gate_w"].data_ptr(), lw["gate_b"].data_ptr(), lw["gate_const"].data_ptr(),
+                                                    rel_bias.data_ptr(), ctx_op.data_ptr(), att_ws.data_ptr() if att_ws.numel() else None,
+                                                    stream), "ts_wavlm_attention_fwd")
+                return ctx_op
             _lib.check(L.ts_w2v_attention_fwd(qkv_op.data_ptr(), b, t, c, self.heads, self._ptr(key_len), self.prec, ctx_op.data_ptr(),
                                               att_ws.data_ptr(), stream), "ts_w2v_attention_fwd")
             return ctx_op
@@ -382,6 +434,10 @@ class HuggingFaceEncoderAdapt(nn.Module):
         return self._fe_cache.get(params, lambda: Wav2Vec2Plan(self.original_encoder.config, sd, device, self.precision, feature_extractor_only=True))
 
     def forward(self, audio: torch.Tensor, audio_lengths: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        if self.training and getattr(self.original_encoder.config, "model_type", "wav2vec2") == "wavlm":
+            # the training path (huggingface/train.py) has no backward for the gated relative-position bias: it would silently run wav2vec2 attention
+            raise NotImplementedError("wavlm: fine-tuning is not implemented (the gated relative-position attention has no backward on the HIP path); "
+                                      "use the module in eval mode")
         _t.require_gpu(audio, "wav2vec2 encoder")
         x = audio.to(torch.float32).contiguous()
         if self.training:
