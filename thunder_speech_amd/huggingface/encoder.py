@@ -7,7 +7,8 @@ weights (same attribute name `original_encoder`, same state-dict keys, so checkp
 difference); the arithmetic runs in `Wav2Vec2Plan`, which keeps packed fp32 device copies of the weights and issues one C-ABI
 call per stage.  Both published families (group-norm / post-LN: wav2vec2-base-960h, -large-960h; layer-norm / pre-LN: -large-lv60, xlsr);
 WavLM runs the same sequence with its gated relative-position attention (csrc/wavlm.hip, include/thunder_speech_amd_wavlm.h) in place of
-the wav2vec2 one (inference only); training mode (fine-tuning with the conv feature extractor frozen) runs through huggingface/train.py; no CPU fallback."""
+the wav2vec2 one (fine-tuning in mixed precision only: csrc/wavlm_train.hip); training mode (fine-tuning with the conv feature extractor frozen) runs
+through huggingface/train.py; no CPU fallback."""
 from __future__ import annotations
 
 import math
@@ -42,7 +43,8 @@ def feat_extract_output_lengths(conv_kernel, conv_stride, lengths: torch.Tensor,
 # stack of grouped convs each followed by an affine-free LayerNorm and GELU); unispeech / unispeech-sat (UniSpeechModel / UniSpeechSatModel run the wav2vec2
 # encoder arithmetic unchanged: tests/test_oracle_w2v.py checks the oracle against both); wavlm (base / base-plus: group norm, post-LN; large: layer
 # norm, pre-LN): the wav2vec2 layers with WavLMAttention's gated relative-position bias in the attention core (csrc/wavlm.hip, head_dim 64 -- every
-# published WavLM -- inference only).  Others (sew's squeezed encoder, wav2vec2-conformer ...) have layers this library holds no kernels for and raise.
+# published WavLM -- fine-tuned with train_precision="bf16" only, csrc/wavlm_train.hip).  Others (sew's squeezed encoder, wav2vec2-conformer ...) have
+# layers this library holds no kernels for and raise.
 SUPPORTED_MODEL_TYPES = ("wav2vec2", "hubert", "data2vec-audio", "unispeech", "unispeech-sat", "wavlm")
 
 
@@ -434,10 +436,14 @@ class HuggingFaceEncoderAdapt(nn.Module):
         return self._fe_cache.get(params, lambda: Wav2Vec2Plan(self.original_encoder.config, sd, device, self.precision, feature_extractor_only=True))
 
     def forward(self, audio: torch.Tensor, audio_lengths: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        if self.training and getattr(self.original_encoder.config, "model_type", "wav2vec2") == "wavlm" and self.train_precision != "bf16":
+            # the gated relative-position attention trains on the fused mixed-precision kernels only (csrc/wavlm_train.hip); f32 fine-tuning would
+            # need a materialised-probability path of its own
+            raise NotImplementedError(f"wavlm: fine-tuning with train_precision={self.train_precision!r} is not implemented (the gated relative-position "
+                                      'attention trains in mixed precision only); use train_precision="bf16", or the module in eval mode')
         if self.training and getattr(self.original_encoder.config, "model_type", "wav2vec2") == "wavlm":
-            # the training path (huggingface/train.py) has no backward for the gated relative-position bias: it would silently run wav2vec2 attention
-            raise NotImplementedError("wavlm: fine-tuning is not implemented (the gated relative-position attention has no backward on the HIP path); "
-                                      "use the module in eval mode")
+            from .train import refuse_untrainable
+            refuse_untrainable(self, True)              # adapter, mask_feature_prob, unfrozen feature extractor: by name, before any device work
         _t.require_gpu(audio, "wav2vec2 encoder")
         x = audio.to(torch.float32).contiguous()
         if self.training:

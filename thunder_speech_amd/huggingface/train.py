@@ -1,5 +1,7 @@
 """wav2vec2 fine-tuning on the HIP kernels: the training-mode forward of `transformers.Wav2Vec2Model` as a chain of autograd nodes whose
-forward and backward are C-ABI launches (csrc/gemm_f32.hip for every product, csrc/w2v_train.hip for the rest).
+forward and backward are C-ABI launches (csrc/gemm_f32.hip for every product, csrc/w2v_train.hip for the rest).  `transformers.WavLMModel`
+trains on the same chain in mixed precision, with its gated relative-position attention on csrc/wavlm_train.hip (WavLMGate, WavLMRelBias,
+WavLMAttentionFused).
 
 The reference fine-tunes HuggingFace CTC checkpoints through `BaseCTCModule.training_step` (src/thunder/module.py:102-127) with the conv feature
 extractor frozen (`_HuggingFaceEncoderAdapt.__init__`, src/thunder/huggingface/compatibility.py:27-28 -> `freeze_feature_encoder()`); autograd
@@ -473,6 +475,100 @@ class AttentionFused(torch.autograd.Function):
         return dqkv, None, None, None, None
 
 
+class WavLMGate(torch.autograd.Function):
+    """WavLMAttention's gate from the attention's input rows x [B, T, C] (f32; ts_wavlm_gate_fwd / _bwd, csrc/wavlm_train.hip):
+    g[b][h][i] = ga (gb c_h - 1) + 2 with ga, gb the sigmoids of the two 4-sums of x_h W^T + beta.  c: gru_rel_pos_const as [H].
+    The backward writes dx (autograd adds it to the QKV projection's dx) and dW, dbeta, dc in a fixed summation order."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, cst):
+        x, w, bias, cst = _f32c(x), _f32c(w), _f32c(bias), _f32c(cst)
+        b, t, c = x.shape
+        heads = cst.numel()
+        g = torch.empty(b, heads, t, dtype=torch.float32, device=x.device)
+        gab = torch.empty(2, b, heads, t, dtype=torch.float32, device=x.device)
+        _lib.check(_lib.lib().ts_wavlm_gate_fwd(x.data_ptr(), b, t, heads, c, w.data_ptr(), bias.data_ptr(), cst.data_ptr(), g.data_ptr(), gab.data_ptr(),
+                                                _s(x)), "ts_wavlm_gate_fwd")
+        ctx.save_for_backward(x, w, cst, gab)
+        return g
+
+    @staticmethod
+    def backward(ctx, dg):
+        x, w, cst, gab = ctx.saved_tensors
+        dg = _f32c(dg)
+        b, t, c = x.shape
+        heads = cst.numel()
+        L = _lib.lib()
+        dx, dw = torch.empty_like(x), torch.empty_like(w)
+        db, dc = torch.empty(8, dtype=torch.float32, device=x.device), torch.empty_like(cst)
+        ws = torch.empty(L.ts_wavlm_gate_bwd_workspace(b, t, heads), dtype=torch.uint8, device=x.device)
+        _lib.check(L.ts_wavlm_gate_bwd(x.data_ptr(), b, t, heads, c, w.data_ptr(), cst.data_ptr(), gab.data_ptr(), dg.data_ptr(), dx.data_ptr(),
+                                       dw.data_ptr(), db.data_ptr(), dc.data_ptr(), ws.data_ptr(), _s(x)), "ts_wavlm_gate_bwd")
+        return dx, dw, db, dc
+
+
+class WavLMRelBias(torch.autograd.Function):
+    """compute_bias as the [H][2t - 1] diagonals (ts_wavlm_rel_bias) from layer 0's rel_attn_embed [num_buckets][H]; built once per forward and
+    passed to every layer, so autograd sums the layers' diagonal gradients before the backward (ts_wavlm_rel_bias_bwd) gathers them per bucket."""
+
+    @staticmethod
+    def forward(ctx, embed, abs_bucket, nb, md, t):
+        embed = _f32c(embed)
+        heads = embed.shape[1]
+        rb = torch.empty(heads, 2 * t - 1, dtype=torch.float32, device=embed.device)
+        _lib.check(_lib.lib().ts_wavlm_rel_bias(embed.data_ptr(), abs_bucket.data_ptr(), nb, md, heads, t, rb.data_ptr(), _s(embed)), "ts_wavlm_rel_bias")
+        ctx.save_for_backward(abs_bucket)
+        ctx.geom = (nb, md, heads, t)
+        return rb
+
+    @staticmethod
+    def backward(ctx, drb):
+        (abs_bucket,) = ctx.saved_tensors
+        nb, md, heads, t = ctx.geom
+        drb = _f32c(drb)
+        de = torch.empty(nb, heads, dtype=torch.float32, device=drb.device)
+        _lib.check(_lib.lib().ts_wavlm_rel_bias_bwd(drb.data_ptr(), abs_bucket.data_ptr(), nb, md, heads, t, de.data_ptr(), _s(drb)), "ts_wavlm_rel_bias_bwd")
+        return de, None, None, None, None
+
+
+class WavLMAttentionFused(torch.autograd.Function):
+    """AttentionFused with WavLM's gated relative-position bias in the logits (csrc/wavlm_train.hip; head_dim 64):
+    ctx = dropout(softmax(q k^T / 8 + g[b][h][i] rb[h][j - i + t - 1], keys >= key_len masked)) v.  The backward also returns the gradients of the
+    gate g [B][H][T] and of this layer's use of the diagonals rb [H][2T - 1]."""
+
+    @staticmethod
+    def forward(ctx, qkv, key_len, g, rb, heads, p_drop, seed):
+        qkv, g, rb = _f32c(qkv), _f32c(g), _f32c(rb)
+        b, t, c3 = qkv.shape
+        c = c3 // 3
+        q16, _ = _cast(qkv.view(b * t, c3), b * t, c3, True, False)
+        out = torch.empty(b, t, c, dtype=torch.float32, device=qkv.device)
+        lse2 = torch.empty(b, heads, t, dtype=torch.float32, device=qkv.device)
+        L = _lib.lib()
+        ws = torch.empty(L.ts_wavlm_attention_train_fwd_workspace(b, t, c, heads), dtype=torch.uint8, device=qkv.device) if p_drop > 0 else None
+        st = L.ts_wavlm_attention_train_fwd(q16.data_ptr(), b, t, c, heads, key_len.data_ptr() if key_len is not None else None, float(p_drop), int(seed),
+                                            g.data_ptr(), rb.data_ptr(), out.data_ptr(), lse2.data_ptr(), ws.data_ptr() if ws is not None else None, _s(qkv))
+        _lib.check(st, "ts_wavlm_attention_train_fwd")
+        ctx.save_for_backward(q16, out, lse2, key_len, ws, g, rb)
+        ctx.geom = (b, t, c, heads, float(p_drop), int(seed))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q16, out, lse2, key_len, mask, g, rb = ctx.saved_tensors
+        b, t, c, heads, p_drop, seed = ctx.geom
+        dout = _f32c(dout)
+        L = _lib.lib()
+        ws = torch.empty(L.ts_wavlm_attention_train_bwd_workspace(b, t, c, heads), dtype=torch.uint8, device=dout.device)
+        dqkv = torch.empty(b, t, 3 * c, dtype=torch.float32, device=dout.device)
+        dg, drb = torch.empty_like(g), torch.empty_like(rb)
+        st = L.ts_wavlm_attention_train_bwd(q16.data_ptr(), b, t, c, heads, key_len.data_ptr() if key_len is not None else None, p_drop, seed, g.data_ptr(),
+                                            rb.data_ptr(), dout.data_ptr(), out.data_ptr(), lse2.data_ptr(), mask.data_ptr() if mask is not None else None,
+                                            dqkv.data_ptr(), dg.data_ptr(), drb.data_ptr(), ws.data_ptr(), _s(dout))
+        _lib.check(st, "ts_wavlm_attention_train_bwd")
+        return dqkv, None, dg, drb, None, None, None
+
+
 MIXED_POSCONV = True        # mixed mode: the positional conv's forward and data gradient on the bf16 matrix-core kernel (False: f32 products, for A/B)
 FUSED_ATTENTION = True      # mixed mode: AttentionFused where it applies (False: the materialised-probabilities path, for A/B)
 
@@ -624,15 +720,21 @@ def train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
         _MIXED = False
 
 
-def _train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
-    from .encoder import feat_extract_output_lengths
+def refuse_untrainable(adapt, mixed: bool) -> None:
+    """Raise NotImplementedError, by name, for a configuration this training path has no backward for (no device work: the WavLM adapter calls it
+    before its GPU check).  `mixed`: train_precision == "bf16"."""
     enc = adapt.original_encoder
     cfg = enc.config
-    dev = audio.device
-    if getattr(cfg, "model_type", "wav2vec2") != "wav2vec2":
+    model_type = getattr(cfg, "model_type", "wav2vec2")
+    wavlm = model_type == "wavlm"
+    if wavlm and not (mixed and FUSED_ATTENTION):
+        # the gated relative-position attention trains on the fused mixed-precision kernels only (csrc/wavlm_train.hip): there is no
+        # materialised-probability WavLM path to fall back to
+        raise NotImplementedError('HIP fine-tuning path: model_type=\'wavlm\' trains with train_precision="bf16" and the fused attention only')
+    if model_type not in ("wav2vec2", "wavlm"):
         # hubert / data2vec-audio run the inference path (huggingface/encoder.py); their training-mode forward (no feature-projection LayerNorm,
         # stacked positional convs) has no autograd nodes here
-        raise NotImplementedError(f"HIP fine-tuning path: model_type={cfg.model_type!r} is inference-only (wav2vec2 checkpoints fine-tune)")
+        raise NotImplementedError(f"HIP fine-tuning path: model_type={cfg.model_type!r} is inference-only (wav2vec2 and wavlm checkpoints fine-tune)")
     if getattr(cfg, "add_adapter", False):
         raise NotImplementedError("HIP fine-tuning path: add_adapter=True is inference-only (the adapter layers have no backward here)")
     if float(getattr(cfg, "mask_feature_prob", 0.0)) > 0.0 and getattr(cfg, "apply_spec_augment", True):
@@ -644,6 +746,15 @@ def _train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
         # returning no gradient
         raise NotImplementedError("wav2vec2 HIP training path: the conv feature extractor is frozen (freeze_feature_encoder); "
                                   f"{len(unfrozen)} of its parameters have requires_grad=True (first: feature_extractor.{unfrozen[0]})")
+
+
+def _train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
+    from .encoder import feat_extract_output_lengths
+    refuse_untrainable(adapt, _MIXED)
+    enc = adapt.original_encoder
+    cfg = enc.config
+    dev = audio.device
+    wavlm = getattr(cfg, "model_type", "wav2vec2") == "wavlm"
     plan = adapt._plan_frozen(dev)
     with torch.no_grad():                                   # frozen conv feature extractor (compatibility.py:27-28): the inference kernels
         feats = plan.feature_extractor(audio)
@@ -680,15 +791,28 @@ def _train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
     if not stable:
         h = LayerNorm.apply(h, None, en.layer_norm.weight, en.layer_norm.bias, eps)
     h = dropout(h, p_hid)
-    for layer in en.layers:
-        if torch.rand([]).item() < float(cfg.layerdrop):            # LayerDrop: transformers draws torch.rand([]) per layer in training
+    rb = None
+    if wavlm:
+        # WavLMEncoder: layer 0 computes the position bias (compute_bias) and every layer reuses it -- here as [H][2t - 1] diagonals
+        from .encoder import wavlm_bucket_table
+        nb, md = int(cfg.num_buckets), int(cfg.max_bucket_distance)
+        abs_bucket = wavlm_bucket_table(nb, md).to(dev).contiguous()
+        rb = WavLMRelBias.apply(en.layers[0].attention.rel_attn_embed.weight, abs_bucket, nb, md, t)
+    for i, layer in enumerate(en.layers):
+        # LayerDrop: transformers draws torch.rand([]) per layer in training; WavLMEncoder never skips layer 0 (it owns the position bias)
+        if torch.rand([]).item() < float(cfg.layerdrop) and not (wavlm and i == 0):
             continue
         att, ff = layer.attention, layer.feed_forward
         wqkv = torch.cat([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight], 0)
         bqkv = torch.cat([att.q_proj.bias, att.k_proj.bias, att.v_proj.bias], 0)
 
         def attend(x):
-            ctxt = attention(linear(x, wqkv, bqkv), key_len, heads, p_att, next_seed() if p_att > 0 else 0)
+            seed = next_seed() if p_att > 0 else 0
+            if wavlm:                                               # the gate reads the same rows the QKV projection multiplies
+                g = WavLMGate.apply(x, att.gru_rel_pos_linear.weight, att.gru_rel_pos_linear.bias, att.gru_rel_pos_const.view(-1))
+                ctxt = WavLMAttentionFused.apply(linear(x, wqkv, bqkv), key_len, g, rb, heads, p_att, seed)
+            else:
+                ctxt = attention(linear(x, wqkv, bqkv), key_len, heads, p_att, seed)
             return dropout(linear(ctxt, att.out_proj.weight, att.out_proj.bias), p_hid)
 
         def ffn(x):
