@@ -1,5 +1,5 @@
-"""ctypes binding of the C ABI declared in include/thunder_speech_amd.h and its companions include/thunder_speech_amd_wavlm.h and
-include/thunder_speech_amd_wavlm_train.h.
+"""ctypes binding of the C ABI declared in include/thunder_speech_amd.h and its companions include/thunder_speech_amd_wavlm.h,
+include/thunder_speech_amd_wavlm_train.h and include/thunder_speech_amd_conformer.h.
 
 The header is the only copy of the ABI: `read_header` derives every prototype, struct and TS_* constant from it and
 `lib()` applies the result, so a new entry point needs the header and its .hip definition and nothing here.  A C type
@@ -20,6 +20,7 @@ from .build import ROOT, lib_path
 HEADER = os.path.join(ROOT, "include", "thunder_speech_amd.h")
 WAVLM_HEADER = os.path.join(ROOT, "include", "thunder_speech_amd_wavlm.h")    # companion ABI, versioned on its own
 WAVLM_TRAIN_HEADER = os.path.join(ROOT, "include", "thunder_speech_amd_wavlm_train.h")    # second companion (WavLM fine-tuning), versioned on its own
+CONFORMER_HEADER = os.path.join(ROOT, "include", "thunder_speech_amd_conformer.h")        # third companion (wav2vec2-conformer), versioned on its own
 
 # Parameters and struct fields: these scalars, `const <struct>*` as POINTER(struct), every other pointer to one of
 # _POINTEES (const or not, any depth) as c_void_p.  Return types: _RETURNS only.
@@ -83,6 +84,8 @@ WAVLM_SIGNATURES, _, WAVLM_DEFINES = _read_installed_header(WAVLM_HEADER)
 WAVLM_ABI_VERSION = WAVLM_DEFINES["TS_WAVLM_ABI_VERSION"]
 WAVLM_TRAIN_SIGNATURES, _, WAVLM_TRAIN_DEFINES = _read_installed_header(WAVLM_TRAIN_HEADER)
 WAVLM_TRAIN_ABI_VERSION = WAVLM_TRAIN_DEFINES["TS_WAVLM_TRAIN_ABI_VERSION"]
+CONFORMER_SIGNATURES, _, CONFORMER_DEFINES = _read_installed_header(CONFORMER_HEADER)
+CONFORMER_ABI_VERSION = CONFORMER_DEFINES["TS_CONFORMER_ABI_VERSION"]
 TcsDesc, FrontendDesc, WgradItem = STRUCTS["ts_tcs_desc"], STRUCTS["ts_frontend_desc"], STRUCTS["ts_wgrad_item"]
 EXPORTED_SYMBOLS = list(SIGNATURES)
 ABI_VERSION = DEFINES["TS_ABI_VERSION"]
@@ -109,10 +112,10 @@ def lib() -> C.CDLL:
             "`python -m thunder_speech_amd.build` (needs hipcc / ROCm); there is no CPU fallback.")
     import torch  # noqa: F401  -- must initialise its bundled HIP runtime BEFORE our code object is loaded
     L = C.CDLL(path)
-    missing = [s for s in EXPORTED_SYMBOLS + list(WAVLM_SIGNATURES) + list(WAVLM_TRAIN_SIGNATURES) if not hasattr(L, s)]
+    missing = [s for s in EXPORTED_SYMBOLS + list(WAVLM_SIGNATURES) + list(WAVLM_TRAIN_SIGNATURES) + list(CONFORMER_SIGNATURES) if not hasattr(L, s)]
     if missing:
         raise RuntimeError(f"thunder_speech_amd: {path} does not export {missing}; rebuild it")
-    for name, (restype, argtypes) in {**SIGNATURES, **WAVLM_SIGNATURES, **WAVLM_TRAIN_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **WAVLM_SIGNATURES, **WAVLM_TRAIN_SIGNATURES, **CONFORMER_SIGNATURES}.items():
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     if L.ts_abi_version() != ABI_VERSION:
@@ -124,6 +127,9 @@ def lib() -> C.CDLL:
     if L.ts_wavlm_train_abi_version() != WAVLM_TRAIN_ABI_VERSION:
         raise RuntimeError(f"thunder_speech_amd: {path} reports WavLM training ABI {L.ts_wavlm_train_abi_version()}, the header "
                            f"{WAVLM_TRAIN_HEADER} declares {WAVLM_TRAIN_ABI_VERSION}; rebuild it")
+    if L.ts_conformer_abi_version() != CONFORMER_ABI_VERSION:
+        raise RuntimeError(f"thunder_speech_amd: {path} reports conformer ABI {L.ts_conformer_abi_version()}, the header {CONFORMER_HEADER} "
+                           f"declares {CONFORMER_ABI_VERSION}; rebuild it")
     _lib = L
     return L
 

@@ -16,7 +16,7 @@
 //    half-stages ahead + ds_write_b128 -- was built as well and measured 15-25 % slower on every shape.)
 //  * ping-pong: a wave alternates a LOAD phase (fragment reads, DMA issue) with an MFMA phase of 16 back-to-back MFMAs, one barrier
 //    per phase, and the second wave row runs one phase behind the first: on every SIMD one wave multiplies while the other loads.
-//  * epilogue: bias and erf-GELU in registers, then staged through the idle ring for 16-byte row stores: residual add (f32), f32 and /
+//  * epilogue: bias and erf-GELU or SiLU in registers, then staged through the idle ring for 16-byte row stores: residual add (f32), f32 and /
 //    or bf16 result; rows beyond M are clamped on the way in and
 //    masked on the way out; N % 32 == 0 and K % 32 == 0 (every linear of the supported checkpoints).
 //  * workgroup -> tile map keeps the column tiles of one row panel on one XCD (they share the A rows in that XCD's L2).
@@ -67,6 +67,7 @@ __device__ __forceinline__ float erf_as_g(float x) {
   return copysignf(r, x);
 }
 __device__ __forceinline__ float gelu_g(float x) { return 0.5f * x * (1.f + erf_as_g(x * 0.70710678118654752f)); }
+__device__ __forceinline__ float silu_g(float x) { return x / (1.f + __expf(-x)); }
 
 }  // namespace
 
@@ -79,7 +80,9 @@ __device__ __forceinline__ float gelu_g(float x) { return 0.5f * x * (1.f + erf_
 // WMR: wave rows.  2: the 256 x 256 tile above, 8 waves.  1 (packed weights only): a 128 x 256 tile on 4 waves and 72 KiB of LDS, so that TWO
 // workgroups share a CU: they fall out of step by themselves, one's epilogue and cold prologue run under the other's k-loop, and the matrix
 // core is handed back and forth between the two waves of a SIMD without the stagger barriers.
-template <bool PB, int WMR = 2>
+// SILU: the epilogue applies SiLU (wav2vec2-conformer's swish, csrc/conformer.hip) -- an instantiation of its own, so that the GELU / plain
+// instantiations keep their code exactly
+template <bool PB, int WMR = 2, bool SILU = false>
 __global__ __launch_bounds__(256 * WMR) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_nt_kernel(const GemmArgs a) {
   static_assert(WMR == 2 || PB, "the half tile exists for packed weights only");
   constexpr int GMT = 128 * WMR;                                             // rows of this instantiation's tile
@@ -300,6 +303,7 @@ __global__ __launch_bounds__(256 * WMR) __attribute__((amdgpu_waves_per_eu(2, 2)
         for (int r = 0; r < 4; ++r) {
           float v = acc[i][j][r] + bv;
           if (a.act & 1) v = gelu_g(v);
+          if constexpr (SILU) v = silu_g(v);
           *reinterpret_cast<unsigned short*>(ep16 + (16 * i + 4 * fc + r) * EP16 + (16 * j + fr) * 2) = (unsigned short)pack_bf16(v, 0.f);
         }
     }
@@ -332,6 +336,7 @@ __global__ __launch_bounds__(256 * WMR) __attribute__((amdgpu_waves_per_eu(2, 2)
         for (int r = 0; r < 4; ++r) {
           float v = acc[i][2 * j + jj][r] + bv[jj];
           if (a.act & 1) v = gelu_g(v);
+          if constexpr (SILU) v = silu_g(v);
           ep[(16 * i + 4 * fc + r) * 32 + 16 * jj + fr] = v;
         }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                    // wave-private tile: LDS operations of one wave are in order
@@ -379,8 +384,8 @@ int gemm_nt_pack_w(hipStream_t stream, const void* w, long long ldw, int N, int 
 // wf: w in fragment order (gemm_nt_pack_w) or null
 static int gemm_nt_bf16_sw(hipStream_t stream, const void* x, long long lda, long long sx, const void* w, long long ldw, const float* bias,
                            const float* res, long long ld_res, float* y, long long ldc, void* y16, long long ld16, long long sy, long long M, int N, int K,
-                           int gelu, int batch, const void* wf, long long sw) {
-  if (!x || !w || (!y && !y16) || M <= 0 || N <= 0 || K <= 0 || batch <= 0) return TS_EINVAL;
+                           int act, int batch, const void* wf, long long sw) {
+  if (!x || !w || (!y && !y16) || M <= 0 || N <= 0 || K <= 0 || batch <= 0 || act < 0 || act > 2) return TS_EINVAL;
   if (N % 32 || K % GKH || lda % 8 || ldw % 8 || ldw < K) return TS_EUNSUPPORTED;
   if ((y && (ldc % 4 || (reinterpret_cast<uintptr_t>(y) & 15))) || (y16 && (ld16 % 8 || (reinterpret_cast<uintptr_t>(y16) & 15))) ||
       (res && (ld_res % 4 || (reinterpret_cast<uintptr_t>(res) & 15))) || sy % (y16 ? 8 : 4))
@@ -390,40 +395,53 @@ static int gemm_nt_bf16_sw(hipStream_t stream, const void* x, long long lda, lon
   if (((M - 1) * lda + K) * 2 >= (1ll << 31) - 1 || ((long long)(N - 1) * ldw + K) * 2 >= (1ll << 31) - 1) return TS_EUNSUPPORTED;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return TS_EINVAL;
-  static bool attr[64] = {};        // the attribute belongs to the (function, device) pair
-  if (!attr[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS) != hipSuccess)
+  static bool attr[2][64] = {};     // the attribute belongs to the (function, device) pair
+  const int silu = act == 2 ? 1 : 0;
+  if (!attr[silu][dev]) {
+    if (hipFuncSetAttribute(silu ? reinterpret_cast<const void*>(gemm_nt_kernel<false, 2, true>) : reinterpret_cast<const void*>(gemm_nt_kernel<false>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS) != hipSuccess)
       return TS_EUNSUPPORTED;
-    attr[dev] = true;
+    attr[silu][dev] = true;
   }
   if (wf && (reinterpret_cast<uintptr_t>(wf) & 15)) return TS_EUNSUPPORTED;
   GemmArgs a;
   a.x = static_cast<const unsigned short*>(x); a.w = static_cast<const unsigned short*>(w); a.wf = static_cast<const unsigned short*>(wf); a.bias = bias; a.res = res; a.y = y;
   a.y16 = static_cast<unsigned short*>(y16);
   a.lda = lda; a.ldw = ldw; a.ld_res = ld_res; a.ldc = ldc; a.ld16 = ld16; a.sx = sx; a.sy = sy; a.sw = sw;
-  a.M = (int)M; a.N = N; a.K = K; a.act = gelu ? 1 : 0;
+  a.M = (int)M; a.N = N; a.K = K; a.act = act == 1 ? 1 : 0;
   a.n_mt = (int)((M + GM - 1) / GM); a.n_nt = (N + GN - 1) / GN;
   a.blk_c = a.n_nt % 4 == 0 ? 4 : (a.n_nt % 3 == 0 ? 3 : (a.n_nt % 2 == 0 ? 2 : 1));
   (void)hipGetLastError();
   const dim3 grid((unsigned)(a.n_mt * a.n_nt), (unsigned)batch);
   if (wf) {                                        // packed weights: 128-row tiles, two workgroups per CU
     constexpr int LDS_H = 4 * 128 * 144;
-    static bool attr_h[64] = {};
-    if (!attr_h[dev]) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_H) != hipSuccess)
+    static bool attr_h[2][64] = {};
+    if (!attr_h[silu][dev]) {
+      if (hipFuncSetAttribute(silu ? reinterpret_cast<const void*>(gemm_nt_kernel<true, 1, true>) : reinterpret_cast<const void*>(gemm_nt_kernel<true, 1>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_H) != hipSuccess)
         return TS_EUNSUPPORTED;
-      attr_h[dev] = true;
+      attr_h[silu][dev] = true;
     }
     a.n_mt = (int)((M + 127) / 128);
-    hipLaunchKernelGGL((gemm_nt_kernel<true, 1>), dim3((unsigned)(a.n_mt * a.n_nt), (unsigned)batch), dim3(256), LDS_H, stream, a);
-  } else hipLaunchKernelGGL(gemm_nt_kernel<false>, grid, dim3(512), GEMM_LDS, stream, a);
+    const dim3 grid_h((unsigned)(a.n_mt * a.n_nt), (unsigned)batch);
+    if (silu) hipLaunchKernelGGL((gemm_nt_kernel<true, 1, true>), grid_h, dim3(256), LDS_H, stream, a);
+    else hipLaunchKernelGGL((gemm_nt_kernel<true, 1>), grid_h, dim3(256), LDS_H, stream, a);
+  } else if (silu) hipLaunchKernelGGL((gemm_nt_kernel<false, 2, true>), grid, dim3(512), GEMM_LDS, stream, a);
+  else hipLaunchKernelGGL(gemm_nt_kernel<false>, grid, dim3(512), GEMM_LDS, stream, a);
   return hip_status(hipGetLastError());
 }
 
 int gemm_nt_bf16(hipStream_t stream, const void* x, long long lda, long long sx, const void* w, long long ldw, const float* bias,
                  const float* res, long long ld_res, float* y, long long ldc, void* y16, long long ld16, long long sy, long long M, int N, int K,
                  int gelu, int batch, const void* wf) {
-  return gemm_nt_bf16_sw(stream, x, lda, sx, w, ldw, bias, res, ld_res, y, ldc, y16, ld16, sy, M, N, K, gelu, batch, wf, 0);
+  return gemm_nt_bf16_sw(stream, x, lda, sx, w, ldw, bias, res, ld_res, y, ldc, y16, ld16, sy, M, N, K, gelu ? 1 : 0, batch, wf, 0);
+}
+
+// the same with the epilogue's activation by code: 0 none, 1 GELU, 2 SiLU (ts_conformer_linear_fwd)
+int gemm_nt_bf16_act(hipStream_t stream, const void* x, long long lda, long long sx, const void* w, long long ldw, const float* bias,
+                     const float* res, long long ld_res, float* y, long long ldc, void* y16, long long ld16, long long sy, long long M, int N, int K,
+                     int act, int batch, const void* wf) {
+  return gemm_nt_bf16_sw(stream, x, lda, sx, w, ldw, bias, res, ld_res, y, ldc, y16, ld16, sy, M, N, K, act, batch, wf, 0);
 }
 
 }  // namespace ts

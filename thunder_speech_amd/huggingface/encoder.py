@@ -7,7 +7,8 @@ weights (same attribute name `original_encoder`, same state-dict keys, so checkp
 difference); the arithmetic runs in `Wav2Vec2Plan`, which keeps packed fp32 device copies of the weights and issues one C-ABI
 call per stage.  Both published families (group-norm / post-LN: wav2vec2-base-960h, -large-960h; layer-norm / pre-LN: -large-lv60, xlsr);
 WavLM runs the same sequence with its gated relative-position attention (csrc/wavlm.hip, include/thunder_speech_amd_wavlm.h) in place of
-the wav2vec2 one (fine-tuning in mixed precision only: csrc/wavlm_train.hip); training mode (fine-tuning with the conv feature extractor frozen) runs
+the wav2vec2 one (fine-tuning in mixed precision only: csrc/wavlm_train.hip); wav2vec2-conformer (rotary) runs conformer blocks behind the same
+front end (huggingface/conformer.py, inference only); training mode (fine-tuning with the conv feature extractor frozen) runs
 through huggingface/train.py; no CPU fallback."""
 from __future__ import annotations
 
@@ -43,9 +44,12 @@ def feat_extract_output_lengths(conv_kernel, conv_stride, lengths: torch.Tensor,
 # stack of grouped convs each followed by an affine-free LayerNorm and GELU); unispeech / unispeech-sat (UniSpeechModel / UniSpeechSatModel run the wav2vec2
 # encoder arithmetic unchanged: tests/test_oracle_w2v.py checks the oracle against both); wavlm (base / base-plus: group norm, post-LN; large: layer
 # norm, pre-LN): the wav2vec2 layers with WavLMAttention's gated relative-position bias in the attention core (csrc/wavlm.hip, head_dim 64 -- every
-# published WavLM -- fine-tuned with train_precision="bf16" only, csrc/wavlm_train.hip).  Others (sew's squeezed encoder, wav2vec2-conformer ...) have
-# layers this library holds no kernels for and raise.
-SUPPORTED_MODEL_TYPES = ("wav2vec2", "hubert", "data2vec-audio", "unispeech", "unispeech-sat", "wavlm")
+# published WavLM -- fine-tuned with train_precision="bf16" only, csrc/wavlm_train.hip); wav2vec2-conformer with rotary position embeddings
+# (inference only): the wav2vec2 front end and adapter around conformer blocks (huggingface/conformer.py, csrc/conformer.hip,
+# include/thunder_speech_amd_conformer.h).  Others (sew's squeezed encoder, sew-d, the conformer's relative-position variant ...) have layers this
+# library holds no kernels for and raise.
+SUPPORTED_MODEL_TYPES = ("wav2vec2", "hubert", "data2vec-audio", "unispeech", "unispeech-sat", "wavlm", "wav2vec2-conformer")
+CONFORMER_ACTIVATIONS = ("swish", "silu", "gelu")
 
 
 def relative_position_bucket(relative_positions: torch.Tensor, num_buckets: int, max_distance: int) -> torch.Tensor:
@@ -71,6 +75,29 @@ def wavlm_bucket_table(num_buckets: int, max_distance: int) -> torch.Tensor:
     return relative_position_bucket(-torch.arange(max_distance + 1, dtype=torch.long), num_buckets, max_distance).to(torch.int32)
 
 
+def _check_conformer_config(cfg, bad: list) -> None:
+    """wav2vec2-conformer: the rotary variant at head_dim 64, swish / gelu, odd depthwise kernels up to 63 (csrc/conformer.hip)."""
+    pet = getattr(cfg, "position_embeddings_type", None)
+    if pet == "relative":
+        bad.append("model_type='wav2vec2-conformer' with position_embeddings_type='relative' (the Transformer-XL relative-position attention "
+                   "has no HIP kernel; the rotary variant runs)")
+    elif pet is None:
+        bad.append("model_type='wav2vec2-conformer' with position_embeddings_type=None (a conformer without position embeddings is not a "
+                   "published checkpoint; the rotary variant runs)")
+    elif pet != "rotary":
+        bad.append(f"model_type='wav2vec2-conformer' with position_embeddings_type={pet!r}")
+    if int(cfg.hidden_size) != 64 * int(cfg.num_attention_heads):
+        bad.append(f"model_type='wav2vec2-conformer' with head_dim={int(cfg.hidden_size) // int(cfg.num_attention_heads)} (the rotary LayerNorm "
+                   "kernel takes head_dim 64, as every published conformer)")
+    if getattr(cfg, "hidden_act", None) not in CONFORMER_ACTIVATIONS:
+        bad.append(f"model_type='wav2vec2-conformer' with hidden_act={getattr(cfg, 'hidden_act', None)!r} (supported: {', '.join(CONFORMER_ACTIVATIONS)})")
+    k = int(cfg.conv_depthwise_kernel_size)
+    if k < 1 or k > 63 or k % 2 == 0:
+        bad.append(f"model_type='wav2vec2-conformer' with conv_depthwise_kernel_size={k} (odd kernels up to 63 run)")
+    if getattr(cfg, "feat_extract_activation", "gelu") != "gelu":
+        bad.append("feat_extract_activation != gelu")
+
+
 def _check_config(cfg) -> None:
     bad = []
     if getattr(cfg, "model_type", "wav2vec2") not in SUPPORTED_MODEL_TYPES:
@@ -79,6 +106,11 @@ def _check_config(cfg) -> None:
         bad.append("conv_pos_batch_norm=True")
     if getattr(cfg, "feat_extract_norm", "group") not in ("group", "layer"):
         bad.append(f"feat_extract_norm={cfg.feat_extract_norm!r}")
+    if getattr(cfg, "model_type", "wav2vec2") == "wav2vec2-conformer":
+        _check_conformer_config(cfg, bad)
+        if bad:
+            raise NotImplementedError("wav2vec2-conformer HIP path: unsupported configuration: " + ", ".join(bad))
+        return
     if getattr(cfg, "hidden_act", "gelu") != "gelu" or getattr(cfg, "feat_extract_activation", "gelu") != "gelu":
         bad.append("activation != gelu")
     if getattr(cfg, "position_embeddings_type", None) not in (None, "absolute") and hasattr(cfg, "position_embeddings_type"):
@@ -136,8 +168,7 @@ class Wav2Vec2Plan:
         self.layers = []
         if self.feature_extractor_only:
             return
-        self.fp_ln = (f("feature_projection.layer_norm.weight"), f("feature_projection.layer_norm.bias")) if self.fp_has_ln else None
-        self.fp_w, self.fp_b = gw(f("feature_projection.projection.weight")), f("feature_projection.projection.bias")
+        self._pack_projection(f, gw)
         cg = self.hidden // self.groups
         if self.d2v:
             # Data2VecAudioPositionalConvEmbedding: num_conv_pos_embeddings LAYERS of conv_pos_kernel_size taps, plain weights
@@ -159,16 +190,7 @@ class Wav2Vec2Plan:
             self.pos_w = gw(w_eff.view(self.groups, cg, cg, self.kpos).permute(3, 0, 1, 2))   # [k][g][out][in]
             self.pos_b = f(p + "bias")
         self.enc_ln = (f("encoder.layer_norm.weight"), f("encoder.layer_norm.bias"))
-        # Wav2Vec2Adapter behind the encoder (config.add_adapter): optional projection + LayerNorm, then strided conv (padding 1, 2x channels) + GLU layers.
-        # Its projection and convolutions run on the f32 GEMM in both precision modes (three short layers at an eighth of the frame rate and below).
-        self.adapter = bool(getattr(cfg, "add_adapter", False))
-        if self.adapter:
-            self.ad_k, self.ad_s = int(cfg.adapter_kernel_size), int(cfg.adapter_stride)
-            self.ad_proj = None
-            if "adapter.proj.weight" in sd:
-                self.ad_proj = (f("adapter.proj.weight"), f("adapter.proj.bias"), (f("adapter.proj_layer_norm.weight"), f("adapter.proj_layer_norm.bias")))
-            self.ad_layers = [(f(f"adapter.layers.{i}.conv.weight").permute(0, 2, 1).contiguous(), f(f"adapter.layers.{i}.conv.bias"))
-                              for i in range(int(cfg.num_adapter_layers))]
+        self._pack_adapter(cfg, sd, f)
         for i in range(self.n_layers):
             q = f"encoder.layers.{i}."
             self.layers.append(dict(
@@ -188,6 +210,24 @@ class Wav2Vec2Plan:
             self.nb, self.md = int(cfg.num_buckets), int(cfg.max_bucket_distance)
             self.rel_embed = f("encoder.layers.0.attention.rel_attn_embed.weight")                      # [num_buckets][H]
             self.abs_bucket = wavlm_bucket_table(self.nb, self.md).to(self.device).contiguous()
+
+    def _pack_projection(self, f, gw) -> None:
+        """The feature projection: optional LayerNorm (config.layer_norm_eps), then the linear layer -- GEMM operand `gw`."""
+        self.fp_ln = (f("feature_projection.layer_norm.weight"), f("feature_projection.layer_norm.bias")) if self.fp_has_ln else None
+        self.fp_w, self.fp_b = gw(f("feature_projection.projection.weight")), f("feature_projection.projection.bias")
+
+    def _pack_adapter(self, cfg, sd, f) -> None:
+        """Wav2Vec2Adapter behind the encoder (config.add_adapter; Wav2Vec2ConformerAdapter is the same module): optional projection + LayerNorm,
+        then strided conv (padding 1, 2x channels) + GLU layers.  Its projection and convolutions run on the f32 GEMM in both precision modes
+        (three short layers at an eighth of the frame rate and below)."""
+        self.adapter = bool(getattr(cfg, "add_adapter", False))
+        if self.adapter:
+            self.ad_k, self.ad_s = int(cfg.adapter_kernel_size), int(cfg.adapter_stride)
+            self.ad_proj = None
+            if "adapter.proj.weight" in sd:
+                self.ad_proj = (f("adapter.proj.weight"), f("adapter.proj.bias"), (f("adapter.proj_layer_norm.weight"), f("adapter.proj_layer_norm.bias")))
+            self.ad_layers = [(f(f"adapter.layers.{i}.conv.weight").permute(0, 2, 1).contiguous(), f(f"adapter.layers.{i}.conv.bias"))
+                              for i in range(int(cfg.num_adapter_layers))]
 
     def _frag(self, w: torch.Tensor):
         """The bf16 GEMM weight `w` [n][k] in MFMA B-fragment order (ts_gemm_nt_pack_w), packed once per weight: the GEMM kernel then
@@ -421,7 +461,11 @@ class HuggingFaceEncoderAdapt(nn.Module):
 
     def _plan(self, device) -> Wav2Vec2Plan:
         params = list(self.original_encoder.parameters())
-        return self._cache.get(params, lambda: Wav2Vec2Plan(self.original_encoder.config, self.original_encoder.state_dict(), device, self.precision))
+        cfg = self.original_encoder.config
+        if getattr(cfg, "model_type", "wav2vec2") == "wav2vec2-conformer":
+            from .conformer import ConformerPlan
+            return self._cache.get(params, lambda: ConformerPlan(cfg, self.original_encoder.state_dict(), device, self.precision))
+        return self._cache.get(params, lambda: Wav2Vec2Plan(cfg, self.original_encoder.state_dict(), device, self.precision))
 
     def _plan_frozen(self, device) -> Wav2Vec2Plan:
         """The plan the training path runs the frozen conv feature extractor on: built from and keyed on the feature extractor's parameters
@@ -436,6 +480,9 @@ class HuggingFaceEncoderAdapt(nn.Module):
         return self._fe_cache.get(params, lambda: Wav2Vec2Plan(self.original_encoder.config, sd, device, self.precision, feature_extractor_only=True))
 
     def forward(self, audio: torch.Tensor, audio_lengths: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        if self.training and getattr(self.original_encoder.config, "model_type", "wav2vec2") == "wav2vec2-conformer":
+            # no conformer backward exists (BatchNorm in train mode, the depthwise conv, the rotary products): refused before any device work
+            raise NotImplementedError("wav2vec2-conformer: fine-tuning is not implemented (inference only); use the module in eval mode")
         if self.training and getattr(self.original_encoder.config, "model_type", "wav2vec2") == "wavlm" and self.train_precision != "bf16":
             # the gated relative-position attention trains on the fused mixed-precision kernels only (csrc/wavlm_train.hip); f32 fine-tuning would
             # need a materialised-probability path of its own
