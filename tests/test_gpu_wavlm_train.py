@@ -65,6 +65,17 @@ def _reference(q16, g, rb, key_len, heads, p, keep, dout):
     return ctx.detach(), qkv.grad, g.grad, rb.grad
 
 
+def _lse2(q16, g, rb, key_len, heads, dtype):
+    """log2(sum over the valid keys of exp(q k / 8 + gate rel_bias)) in `dtype` on the CPU, [B][H][t]; -inf for a clip without a valid key."""
+    b, t, c3 = q16.shape
+    c = c3 // 3
+    q, k = [z.reshape(b, t, heads, 64).transpose(1, 2) for z in q16.cpu().to(dtype).split(c, dim=-1)[:2]]
+    s = (q @ k.transpose(-1, -2)) / 8.0 + g.cpu().to(dtype)[..., None] * rb.cpu().to(dtype)[:, _diag_index(t)][None]
+    n = torch.full((b,), t) if key_len is None else key_len.cpu().long().clamp(max=t)
+    s = s.masked_fill((torch.arange(t)[None, :] >= n[:, None])[:, None, None, :], float("-inf"))
+    return torch.logsumexp(s, -1) / float(np.log(2.0)), n
+
+
 def _run(q16, g, rb, key_len, heads, p, seed, dout):
     """ts_wavlm_attention_train_fwd / _bwd with every output filled with NaN first."""
     from thunder_speech_amd import _lib
@@ -111,6 +122,15 @@ def test_fused_attention_kernels_match_a_float64_restatement(b, t, heads, p, rag
     for x in (ctx, dqkv, dg, drb):
         assert bool(torch.isfinite(x).all())
     assert not bool(torch.isnan(lse2).any())
+    # the row statistic the backward rebuilds every probability from: f32 arithmetic on bf16 operands, so within 4 x the error of the same expression in
+    # float32 on the CPU (floor 1e-5 x max |lse2|); a clip without a valid key holds +inf (every rebuilt probability exp2(s - inf) is 0)
+    want, n = _lse2(q16, g, rb, key_len, heads, torch.float64)
+    some = n > 0
+    own = float((_lse2(q16, g, rb, key_len, heads, torch.float32)[0].double() - want)[some].abs().max())
+    err = float((lse2.double().cpu() - want)[some].abs().max())
+    print(f"lse2 b={b} t={t}: error {err:.3e}, float32 on the CPU {own:.3e}")
+    assert err <= max(4.0 * own, 1e-5 * float(want[some].abs().max())), (err, own)
+    assert bool((lse2.cpu()[~some] == float("inf")).all())
     rctx, rdqkv, rdg, rdrb = _reference(q16, g, rb, key_len, heads, p, keep, dout)
     c = 64 * heads
 

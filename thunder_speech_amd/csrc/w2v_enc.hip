@@ -168,6 +168,13 @@ __global__ __launch_bounds__(256) void w2v_conv0_finalize_kernel(const Conv0Args
   var = var < 0.0 ? 0.0 : var;
   const double rs = 1.0 / sqrt(var + (double)a.eps);
   const double g = a.gamma[c];
+  if (a.t0 == 1) {
+    // one frame: the channel's only value IS its mean, so the normalised value is exactly 0 and the result beta whatever the signal.  The affine form
+    // v * scale + shift would instead return the f32 roundings of two terms of size |v| g / sqrt(eps) = 316 |v| g that cancel (1e-4 off at |v| = 3)
+    a.stats[((size_t)b * a.c + c) * 2] = 0.f;
+    a.stats[((size_t)b * a.c + c) * 2 + 1] = a.beta[c];
+    return;
+  }
   a.stats[((size_t)b * a.c + c) * 2] = (float)(rs * g);
   a.stats[((size_t)b * a.c + c) * 2 + 1] = (float)((double)a.beta[c] - mu * rs * g);
 }
@@ -663,6 +670,9 @@ extern "C" int ts_w2v_layernorm_fwd(const float* x, const float* res, const floa
                                     int64_t rows, int32_t c, int32_t act, float* y, void* y_bf16, void* stream_) {
   if (!x || !w || !b || (!y && !y_bf16) || rows <= 0 || c <= 0) return TS_EINVAL;
   if (c % 4 || c > 4096) return TS_EUNSUPPORTED;
+  // the kernel moves float4s (8-byte pairs for the bf16 copy): as in ts_w2v_layernorm_bwd, a misaligned pointer is refused before any launch
+  const auto mis = [](const void* p, uintptr_t m) { return p && (reinterpret_cast<uintptr_t>(p) & m) != 0; };
+  if (mis(x, 15) || mis(res, 15) || mis(xbias, 15) || mis(w, 15) || mis(b, 15) || mis(y, 15) || mis(y_bf16, 7)) return TS_EUNSUPPORTED;
   TS_STREAM;
   const dim3 grid((unsigned)((rows + 3) / 4));
   unsigned short* y16 = static_cast<unsigned short*>(y_bf16);
