@@ -45,6 +45,35 @@ def test_library_loads_and_answers_version_queries():
         assert L.ts_time_pitch(t) == _lib.time_pitch(t) and _lib.time_pitch(t) % 128 == 0 and _lib.time_pitch(t) >= t
 
 
+def test_training_attention_mask_workspace_covers_the_dkv_kernels_reach():
+    """The dropout mask is a bitstring of n = batch * heads * t * t bits in the forward's workspace, which the caller may hand to the backward as
+    fwd_mask.  The dKV kernels rebuild whole 64-key tiles, keys past t included: the furthest keep8() call belongs to the last row (first bit
+    n - t) in the last key tile (k0 = 64 * ((t - 1) // 64)) at sub = 1, half = 1, second run of 8 -- bit e0 = n - t + k0 + 32 + 8 + 16 -- and
+    keep8 reads the 32-bit words e0 // 32 and e0 // 32 + 1.  Both paths must size the workspace to hold that word, and so must the part of the
+    backward's workspace that holds a re-drawn mask."""
+    from thunder_speech_amd import _lib
+    L = _lib.lib()
+    short = []
+    for bh in range(1, 34):
+        for t in range(1, 201):
+            n = bh * t * t
+            e0 = n - t + 64 * ((t - 1) // 64) + 32 + 8 + 16
+            need = 4 * (e0 // 32 + 2)                                   # bytes up to and including word e0 // 32 + 1
+            for batch, heads in ((bh, 1), (1, bh)):
+                c = 64 * heads
+                al16 = lambda n: (n + 15) // 16 * 16
+                # what precedes the re-drawn mask in the backward's workspace: dO bf16 | D f32 (| the WavLM path's drb records, 95 f32 each)
+                front = al16(batch * t * c * 2) + al16(batch * heads * t * 4)
+                records = al16(batch * heads * ((t + 63) // 64) * ((t + 31) // 32) * 95 * 4)
+                got = (L.ts_w2v_attention_train_fwd_workspace(batch, t, c, heads),
+                       L.ts_wavlm_attention_train_fwd_workspace(batch, t, c, heads),
+                       L.ts_w2v_attention_train_bwd_workspace(batch, t, c, heads) - front,
+                       L.ts_wavlm_attention_train_bwd_workspace(batch, t, c, heads) - front - records)
+                if min(got) < need:
+                    short.append((batch, heads, t, need, got))
+    assert not short, short[:5]
+
+
 _LAYOUT_PROBE = r'''
 #include <stddef.h>
 #include <stdio.h>

@@ -9,7 +9,7 @@
 //     precision 1, hd 64:   wavlm_flash_attn_kernel, w2v_flash_attn_kernel with the gate in the prologue and the bias window of the
 //                            tile staged in LDS next to K / V; the [T][T] scores are never stored
 //     precision 0:          scores from the f32 GEMM, one row kernel (gate, bias, mask, softmax), P V on the f32 GEMM
-#include "ts_common.hpp"
+#include "attn_tile.hpp"
 #include "thunder_speech_amd_wavlm.h"
 
 namespace ts {
@@ -17,15 +17,6 @@ namespace ts {
 int gemm_f32(hipStream_t stream, bool in_bf16, const void* a, long long a_rs, long long a_cs, long long sa, long long ska, const void* b,
              long long b_rs, long long b_cs, long long sb, long long skb, void* c, long long ldc, long long sc, bool out_bf16, const float* bias,
              int M, int N, int K, int nkb, int batch, bool beta);
-
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + __expf(-x)); }
-
-// gate = sigmoid(p0 + p1 + p2 + p3) (sigmoid(p4 + p5 + p6 + p7) const - 1) + 2 from the 8 projections p (bias included)
-__device__ __forceinline__ float wavlm_gate(const float* p, float cst) {
-  const float a = sigmoid_f(((p[0] + p[1]) + p[2]) + p[3]);
-  const float g = sigmoid_f(((p[4] + p[5]) + p[6]) + p[7]);
-  return a * (g * cst - 1.f) + 2.f;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // position bias diagonals: one thread per (head, d)
@@ -35,11 +26,7 @@ __global__ __launch_bounds__(256) void wavlm_rel_bias_kernel(const float* __rest
   const int n = 2 * t - 1, h = blockIdx.y;
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= n) return;
-  const int d = j - (t - 1);
-  const int ad = d < 0 ? -d : d;
-  int bucket = (d > 0 ? nb / 2 : 0) + abs_bucket[ad < md ? ad : md];
-  bucket = bucket < 0 ? 0 : (bucket < nb ? bucket : nb - 1);     // a malformed table cannot read outside E
-  rb[(size_t)h * n + j] = embed[(size_t)bucket * heads + h];
+  rb[(size_t)h * n + j] = embed[(size_t)wavlm_bucket(j - (t - 1), nb, md, abs_bucket) * heads + h];
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -97,18 +84,11 @@ __global__ __launch_bounds__(256) void wavlm_softmax_kernel(const WlRowArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Fused gated-bias attention (precision 1, head_dim 64): w2v_flash_attn_kernel (csrc/w2v_enc.hip) plus
+// Fused gated-bias attention (precision 1, head_dim 64).  To the base sequence of csrc/attn_tile.hpp (w2v_flash_attn_kernel) it adds
 //   * the gate of the lane's query in the prologue: lane half h2 dots d = 32 h2 .. 32 h2 + 31 of the query's input row with the
 //     8 x 64 weights (staged in LDS once), one exchange with lane ^ 32 completes the 8 projections;
-//   * per 64-key tile the 191 diagonals rb[h][key - query + t - 1] the 128 x 64 tile touches, staged in LDS next to K and V;
-//   * the full logit s scale + gate rb (log2 units) formed BEFORE the running maximum: with a bias the maximum no longer
-//     commutes with the scale, so the scaled-max shortcut of the wav2vec2 kernel is gone.
+//   * per 64-key tile the window of bias diagonals (stage_window) and the logit formed from it before the maximum (wavlm_logits).
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int WA_KT = 64;          // keys per staged tile
-constexpr int WA_PITCH = 144;      // bytes per staged K / V row (64 bf16 + 16)
-constexpr int WA_QW = 128;         // queries per workgroup
-constexpr int WA_WIN = WA_QW + WA_KT;   // 191 diagonals per tile, rounded up
-
 struct WaArgs {
   const unsigned short* qkv;       // [B][T][3C] bf16
   unsigned short* ctx;             // [B][T][C] bf16
@@ -124,28 +104,22 @@ struct WaArgs {
 };
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void wavlm_flash_attn_kernel(const WaArgs a) {
-  __shared__ __attribute__((aligned(16))) char ks_[WA_KT * WA_PITCH];
-  __shared__ __attribute__((aligned(16))) char vs_[WA_KT * WA_PITCH];
-  __shared__ __attribute__((aligned(16))) float rbs[WA_WIN];
+  __shared__ __attribute__((aligned(16))) char ks_[AT_KV];
+  __shared__ __attribute__((aligned(16))) char vs_[AT_KV];
+  __shared__ __attribute__((aligned(16))) float rbs[AT_WIN];
   __shared__ __attribute__((aligned(16))) float wgs[8 * 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.z, head = blockIdx.y;
-  const int qw0 = blockIdx.x * WA_QW, q0 = qw0 + wave * 32;
+  const int qw0 = blockIdx.x * AT_QW, q0 = qw0 + wave * 32;
   const size_t rowp = (size_t)3 * a.c;
   const unsigned short* base = a.qkv + (size_t)b * a.t * rowp + (size_t)head * 64;
-  int lim = a.t;
-  if (a.key_len) {
-    const int n = a.key_len[b] < a.t ? a.key_len[b] : a.t;
-    lim = n > 0 ? n : a.t;                       // no valid key: the reference's softmax degenerates to all keys
-  }
-  const int half = lane >> 5, n32 = lane & 31;
-  const int qrow = q0 + n32 < a.t ? q0 + n32 : a.t - 1;
+  const int lim = key_limit<true>(a.key_len, b, a.t);
+  const TileLane g = tile_lane(lane);
+  const int half = g.half;
+  const int query = q0 + g.n32;
+  const int qrow = query < a.t ? query : a.t - 1;
   s16x8 qf[4];
-  {
-    const uint4* qp = reinterpret_cast<const uint4*>(base + (size_t)qrow * rowp + 8 * half);
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[ks] = __builtin_bit_cast(s16x8, qp[2 * ks]);
-  }
+  load_row_frags(qf, base + (size_t)qrow * rowp + 8 * half);
   // ---- gate of this lane's query, in log2 units ----
   *reinterpret_cast<f32x2*>(wgs + 2 * tid) = *reinterpret_cast<const f32x2*>(a.wg + 2 * tid);
   __syncthreads();
@@ -172,104 +146,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     }
 #pragma unroll
     for (int r = 0; r < 8; ++r) p[r] += __shfl_xor(p[r], 32) + a.bg[r];
-    gl = wavlm_gate(p, a.cst[head]) * 1.4426950408889634f;
+    gl = wavlm_gate(p, a.cst[head]) * LOG2E;
   }
   const float* rbh = a.rb + (size_t)head * (2 * a.t - 1);
   f32x16 o[2];
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) o[mt][i] = 0.f;
+  zero(o[0]); zero(o[1]);
   float m_run = -INFINITY, l_run = 0.f;
-  const int pm = (n32 & ~12) | ((n32 & 4) << 1) | ((n32 & 8) >> 1);          // K row order: bits 2 and 3 swapped
-  const int q4 = (lane >> 2) & 3, gq = (lane >> 4) & 1, p4 = lane & 3;
-  const int v_off = (8 * half + q4) * WA_PITCH + (16 * gq + 4 * p4) * 2;     // transposing read of the V tile
-  // window slot of (key k0 + kk, query qw0 + qq) is kk - qq + WA_QW - 1; this lane's query is qq = 32 wave + n32
-  const int wbase = WA_QW - 1 - (wave * 32 + n32) + 8 * half;
+  const int wbase = window_base(wave, g);
 
-  for (int k0 = 0; k0 < lim; k0 += WA_KT) {
+  for (int k0 = 0; k0 < lim; k0 += AT_KT) {
     __syncthreads();                                                          // the previous tile has been consumed
-#pragma unroll
-    for (int rep = 0; rep < 2; ++rep) {
-      const int chunk = tid + 256 * rep, r = chunk >> 3, cc = chunk & 7;
-      const int key = k0 + r < a.t ? k0 + r : a.t - 1;
-      const unsigned short* src = base + (size_t)key * rowp + cc * 8;
-      *reinterpret_cast<uint4*>(ks_ + r * WA_PITCH + cc * 16) = *reinterpret_cast<const uint4*>(src + a.c);
-      *reinterpret_cast<uint4*>(vs_ + r * WA_PITCH + cc * 16) = *reinterpret_cast<const uint4*>(src + 2 * a.c);
-    }
-    if (tid < WA_WIN) {
-      // diagonal d = k0 - qw0 - (WA_QW - 1) + tid; slots outside [-(t - 1), t - 1] belong to clamped keys / queries (never stored)
-      int j = k0 - qw0 - (WA_QW - 1) + tid + a.t - 1;
-      j = j < 0 ? 0 : (j > 2 * a.t - 2 ? 2 * a.t - 2 : j);
-      rbs[tid] = rbh[j];
-    }
+    stage_kv(ks_, vs_, base, rowp, a.c, a.t, k0, tid);
+    stage_window(rbs, rbh, a.t, k0, qw0, tid);
     __syncthreads();
-    const bool full = k0 + WA_KT <= lim;                                      // no masked key in this tile (uniform)
+    const bool full = k0 + AT_KT <= lim;                                      // no masked key in this tile (uniform)
 #pragma unroll
     for (int sub = 0; sub < 2; ++sub) {
       if (k0 + sub * 32 >= lim) break;                                        // uniform: nothing but masked keys
-      f32x16 s;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) s[i] = 0.f;
-      const char* kr = ks_ + (sub * 32 + pm) * WA_PITCH + half * 16;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks)
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const s16x8*>(kr + ks * 32), qf[ks], s, 0, 0, 0);
-      // accumulator register i <-> key k0 + 32 sub + 16 (i / 8) + 8 half + i % 8
-      const float* wr = rbs + wbase + 32 * sub;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) s[i] = fmaf(s[i], a.scale_log2e, gl * wr[16 * (i >> 3) + (i & 7)]);
-      if (!full) {
-        const int kbase = k0 + sub * 32 + 8 * half;
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-          if (kbase + 16 * (i >> 3) + (i & 7) >= lim) s[i] = -INFINITY;
-      }
-      float mx = s[0];
-#pragma unroll
-      for (int i = 1; i < 16; ++i) mx = fmaxf(mx, s[i]);
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      const float m_new = fmaxf(m_run, mx);                                   // finite: the first sub-tile holds key 0
-      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-      float rs = 0.f;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) { s[i] = __builtin_amdgcn_exp2f(s[i] - m_new); rs += s[i]; }
-      l_run = l_run * alpha + rs;
-      m_run = m_new;
-      if (__any(alpha != 1.f)) {
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) o[mt][i] *= alpha;
-      }
-#pragma unroll
-      for (int ks2 = 0; ks2 < 2; ++ks2) {
-        const unsigned p01 = pack_bf16(s[8 * ks2 + 0], s[8 * ks2 + 1]), p23 = pack_bf16(s[8 * ks2 + 2], s[8 * ks2 + 3]);
-        const unsigned p45 = pack_bf16(s[8 * ks2 + 4], s[8 * ks2 + 5]), p67 = pack_bf16(s[8 * ks2 + 6], s[8 * ks2 + 7]);
-        const s16x8 pb = __builtin_bit_cast(s16x8, uint4{p01, p23, p45, p67});
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-          const char* va = vs_ + (sub * 32 + 16 * ks2) * WA_PITCH + v_off + 64 * mt;
-          const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((TS_LDS s16x4*)((TS_LDS char*)va));
-          const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((TS_LDS s16x4*)((TS_LDS char*)va + 4 * WA_PITCH));
-          const s16x8 vf = s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-          o[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pb, o[mt], 0, 0, 0);
-        }
-      }
+      f32x16 s = wavlm_logits(qk_subtile(ks_, sub, g, qf), a.scale_log2e, gl, rbs + wbase + 32 * sub);
+      if (!full) s = mask_tail(s, k0 + sub * 32 + 8 * half, lim);
+      const SoftmaxStep sm = softmax_step<false>(s, m_run, l_run);
+      m_run = sm.m; l_run = sm.l;
+      rescale(o, sm.alpha);
+      acc_tile_t(o, sm.p, vs_, sub, g);
     }
   }
   const float l = l_run + __shfl_xor(l_run, 32);
   const float inv = 1.f / l;
-  const int query = q0 + n32;
-  if (query < a.t) {
-    unsigned short* dst = a.ctx + ((size_t)b * a.t + query) * a.c + (size_t)head * 64 + 4 * half;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g)       // accumulator registers 4g .. 4g+3 <-> d = 32 mt + 8 g + 4 half + 0..3
-        *reinterpret_cast<uint2*>(dst + 32 * mt + 8 * g) =
-            uint2{pack_bf16(o[mt][4 * g] * inv, o[mt][4 * g + 1] * inv), pack_bf16(o[mt][4 * g + 2] * inv, o[mt][4 * g + 3] * inv)};
-  }
+  if (query < a.t) store_bf16(a.ctx + ((size_t)b * a.t + query) * a.c + (size_t)head * 64 + 4 * half, o, inv);
 }
 
 }  // namespace ts
@@ -312,8 +216,8 @@ extern "C" int ts_wavlm_attention_fwd(const void* qkv, int32_t batch, int32_t t,
     w.qkv = static_cast<const unsigned short*>(qkv); w.ctx = static_cast<unsigned short*>(ctx); w.key_len = key_len;
     w.gx = static_cast<const unsigned short*>(gate_x); w.ld = ld_gate_x;
     w.wg = gate_w; w.bg = gate_b; w.cst = gate_const; w.rb = rel_bias;
-    w.t = t; w.c = c; w.scale_log2e = 1.4426950408889634f / sqrtf((float)hd);
-    hipLaunchKernelGGL(wavlm_flash_attn_kernel, dim3((t + WA_QW - 1) / WA_QW, heads, batch), dim3(256), 0, stream, w);
+    w.t = t; w.c = c; w.scale_log2e = LOG2E / sqrtf((float)hd);
+    hipLaunchKernelGGL(wavlm_flash_attn_kernel, dim3((t + AT_QW - 1) / AT_QW, heads, batch), dim3(256), 0, stream, w);
     return hip_status(hipGetLastError());
   }
   if (!workspace) return TS_EINVAL;
