@@ -333,7 +333,8 @@ int ts_grad_wire_unpack(const void* wire_bf16, float* grad, int64_t n, void* str
  * 0 = f32 (the reference's arithmetic), 1 = bf16 storage with f32 arithmetic inside the kernels (mixed precision).
  * Parameters, their gradients, statistics and lengths (int32 [B]) are f32 / int32 in both modes.
  *   depthwise MaskedConv1d (quartznet/blocks.py:169-182, groups = C): x masked by len_in; y masked by len_out when given
- *   1x1 MaskedConv1d: plain GEMMs (rocBLAS) on inputs the caller has masked with ts_train_mask_time
+ *   1x1 MaskedConv1d: plain GEMMs on inputs the caller has masked with ts_train_mask_time -- this library's own (csrc/gemm_f32.hip; in bf16
+ *     the training step uses the pointwise-only mode of ts_tcs_subblock_fwd and csrc/train_gemm.hip instead); no vendor library is linked
  *   BatchNorm1d in train mode (quartznet/blocks.py:222, statistics over all B*T frames incl. padding -- quirk A4 --,
  *     biased variance, eps) with optional fused ReLU; mean_rstd f32 [C][2] is saved for the backward
  *   residual add + ReLU (quartznet/blocks.py:332-337)
@@ -527,7 +528,8 @@ int ts_w2v_preprocess(const float* wave, const int32_t* wave_len, int32_t batch,
  * wav2vec2 encoder (config C5), replaces the `self.original_encoder(audio, attention_mask=...)` call of
  * _HuggingFaceEncoderAdapt.forward (huggingface/compatibility.py:31-42), i.e. transformers' Wav2Vec2Model for the
  * group-norm / post-LN checkpoints (wav2vec2-base-960h, -large-960h).  One entry point per stage of that forward pass;
- * all activations f32, TIME-MAJOR [B][T][C] (the reference's final transpose(-1, -2) is a view).  GEMMs are rocBLAS calls.
+ * all activations f32, TIME-MAJOR [B][T][C] (the reference's final transpose(-1, -2) is a view).  GEMMs are this
+ * library's own: csrc/gemm_f32.hip for f32 operands, csrc/gemm_nt.hip for bf16 ones.
  * ---------------------------------------------------------------------------------------------- */
 /* `precision` (all GEMM-carrying entry points): 0 = f32 operands; 1 = bf16 operands (x / w / qkv pointers are bf16), f32
  * accumulation and f32 results.  `y_bf16` (may be NULL): a dense bf16 copy of the result for the next GEMM, written by the

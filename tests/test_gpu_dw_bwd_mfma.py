@@ -1,4 +1,4 @@
-"""GPU parity of the matrix-core depthwise backward (csrc/train_enc.hip dw_bwd_mfma_kernel, selected by ts_train_dwconv_bwd_select) -- the backward
+"""GPU parity of the matrix-core depthwise backward (csrc/train_dw.hip dw_bwd_mfma_kernel, selected by ts_train_dwconv_bwd_select) -- the backward
 of the depthwise MaskedConv1d of a training-mode QuartznetBlock (/root/reference/src/thunder/quartznet/blocks.py:95-164, 317-338) on bf16 rows --
 against float64 autograd through F.conv1d on the same bf16 inputs, and against the packed-f32 FIR kernel it replaces.  Tolerances: dx is stored in
 bf16 (half an ulp = 0.4 % of a value; 6e-3 of the tensor's scale covers it), dw is an f32 sum of exact bf16 products (1e-5), the folded BatchNorm's

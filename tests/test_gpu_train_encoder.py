@@ -216,7 +216,7 @@ def test_bf16_activation_mode_stays_within_bf16_tolerance(golden, name):
                                                (2, 2, 2050, 127, 2), (32, 4, 501, 63, 1), (20, 2, 1100, 127, 1), (17, 6, 90, 5, 1), (32, 2, 501, 75, 1),
                                                (40, 2, 333, 39, 1)])
 def test_same_depthwise_pair_kernels_match_conv1d_autograd(act, batch, ch, t, k, dil):
-    """The packed-FMA "same" depthwise kernels (one wavefront = two channel rows, csrc/train_enc.hip dw_fwd_pair / dw_bwd_pair)
+    """The packed-FMA "same" depthwise kernels (one wavefront = two channel rows, csrc/train_dw.hip dw_fwd_pair / dw_bwd_pair)
     against F.conv1d(groups = C) + autograd on the masked input (quartznet/blocks.py:169-182): ragged lengths, several 512-frame
     wave tiles, clip counts that leave waves idle; dilation 2 (the K87 block of QuartzNet) runs the same kernels in phase-split form
     (a row = (even, odd) frame pairs; odd channel counts allowed); with bf16 rows and >= 17 clips the forward runs on the matrix cores

@@ -1,70 +1,13 @@
-// Training-mode encoder kernels (fine-tuning phase 2: encoder unfrozen): one launch per reference op and
-// direction, so that every op's forward AND backward can be checked against the oracle's autograd.  Activations are [B][C][pitch]
-// rows (time contiguous, pitch a multiple of 8 elements, 16-byte aligned rows; columns >= T are scratch) in one of two element
-// types, selected per call by `act`: 0 = f32 (the reference's arithmetic), 1 = bf16 storage with f32 arithmetic inside every
-// kernel (mixed precision: half the activation traffic, bf16 MFMA GEMMs; parameters, gradients of parameters, statistics stay
-// f32).  The pointwise convolutions and their two backward products are plain GEMMs and go to rocBLAS; everything else is
-// hand-written.
-//   masked depthwise conv fwd / bwd-data / bwd-weight   quartznet/blocks.py:169-182 (MaskedConv1d, groups = C)
-//   masked 1x1 conv fwd / bwd-data / bwd-weight          same class, kernel_size = 1            (rocBLAS sgemm)
-//   BatchNorm1d(train) [+ ReLU] fwd / bwd                quartznet/blocks.py:222 (eps 1e-3), statistics over ALL B*T frames (A4)
-//   residual add + ReLU fwd / bwd                        quartznet/blocks.py:332-337
+// Training-mode encoder kernels (fine-tuning phase 2: encoder unfrozen), part 1 of 3: the masked depthwise convolution,
+//   fwd / bwd-data / bwd-weight   quartznet/blocks.py:169-182 (MaskedConv1d, groups = C)
+// one launch per reference op and direction, so that every op's forward AND backward can be checked against the oracle's autograd.  The row
+// conventions and the two element types (`act`) are csrc/train_act.hpp's; BatchNorm and the block tail are csrc/train_bn.hip, the row-wise
+// element kernels and the pointwise products csrc/train_rows.hip.  In order: the general-geometry kernels, the packed-f32 pair / phase kernels of
+// the "same" layers, the matrix-core forward and backward for bf16 rows, then the dispatch with the deterministic-mode workspace.
 #include "ts_common.hpp"
-
-#include <cstdlib>
-
+#include "train_act.hpp"
 
 namespace ts {
-
-__device__ __forceinline__ int clamp_len(const int* len, int b, int t) {
-  if (!len) return t;
-  const int l = len[b];
-  return l < 0 ? 0 : (l > t ? t : l);
-}
-
-// element access of the two activation types (f32 / bf16 bits)
-typedef unsigned short bf16_t;
-__device__ __forceinline__ float ldf(const float* p, size_t i) { return p[i]; }
-__device__ __forceinline__ float ldf(const bf16_t* p, size_t i) { return bf16_to_f32(p[i]); }
-__device__ __forceinline__ void stf(float* p, size_t i, float v) { p[i] = v; }
-__device__ __forceinline__ void stf(bf16_t* p, size_t i, float v) { p[i] = (bf16_t)(pack_bf16(v, 0.f) & 0xffffu); }
-// 8 consecutive elements of a 16-byte aligned row position
-__device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
-  const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-  v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
-}
-__device__ __forceinline__ void load8(const bf16_t* p, float (&v)[8]) {
-  const u32x4 a = *reinterpret_cast<const u32x4*>(p);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { v[2 * j] = bf16_lo(a[j]); v[2 * j + 1] = bf16_hi(a[j]); }
-}
-// Activation rows leave with streaming (nontemporal) stores: a training launch writes 8-16 MB that the NEXT launch reads, possibly on another
-// XCD, so the lines have to reach memory anyway -- streaming them out while the kernel runs beats leaving them dirty in the XCD's L2 for the
-// end-of-kernel write-back the next launch waits for (measured on the 1x1 products: -10 % per launch, profiles/round6_pw_tile.txt).
-#ifndef TS_TRAIN_NT
-#define TS_TRAIN_NT 0
-#endif
-__device__ __forceinline__ void st16(u32x4* p, u32x4 v) {
-#if TS_TRAIN_NT
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
-__device__ __forceinline__ void st16(f32x4* p, f32x4 v) {
-#if TS_TRAIN_NT
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
-__device__ __forceinline__ void store8(float* p, const float (&v)[8]) {
-  st16(reinterpret_cast<f32x4*>(p), f32x4{v[0], v[1], v[2], v[3]});
-  st16(reinterpret_cast<f32x4*>(p + 4), f32x4{v[4], v[5], v[6], v[7]});
-}
-__device__ __forceinline__ void store8(bf16_t* p, const float (&v)[8]) {
-  st16(reinterpret_cast<u32x4*>(p), u32x4{pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]), pack_bf16(v[6], v[7])});
-}
 
 constexpr int DW_TILE = 1024;      // output frames per workgroup (forward) / input frames per workgroup (backward-data)
 constexpr int DW_KMAX = 128;       // taps cached in LDS
@@ -352,11 +295,6 @@ __device__ __forceinline__ void stage_fetch(Staged<T>& st, const T* ra, const T*
 // Input transform of the rows being staged: the BatchNorm(train) [+ ReLU] of the PREVIOUS repeat, y = relu?(v * scale + shift), applied on
 // the fly so that y is never stored (train_ops.SubBlock hands the un-normalised v of a repeat to the next one).  on == false: identity.
 struct RowAffine { float sa, ha, sb, hb; bool relu, on; };
-constexpr int BN_G = 8;                                   // clip groups of the BatchNorm partial sums
-__device__ __forceinline__ void bn_total(const double* __restrict__ part, int ch, int c, double& s1, double& s2, int ng = BN_G) {
-  s1 = 0.0; s2 = 0.0;
-  for (int g = 0; g < ng; ++g) { s1 += part[((size_t)g * ch + c) * 2]; s2 += part[((size_t)g * ch + c) * 2 + 1]; }
-}
 struct PairAffine { const float* mean_rstd; const float* gamma; const float* beta; int relu; };   // per channel; mean_rstd == nullptr: none
 // forward side: the previous repeat only left the clip-group sums of its 1x1 output (chan_sums_kernel<0>); the depthwise kernel turns
 // them into mean / rstd itself (a few double operations per wave), and the wave that owns clip 0 of a channel pair publishes mean_rstd
@@ -367,15 +305,6 @@ struct PairBnIn {
   float* mean_rstd; float* running_mean; float* running_var; float momentum; long long* nbt;
   const float* tiles = nullptr; int n_tiles = 0;          // instead of `part`: per-tile (sum, sum of squares) pairs, f32 [ch][n_tiles][2] (ts_tcs_desc.stats)
 };
-// the channel's totals out of the per-tile pairs: the 64 lanes of a wave share the tiles, then combine (every lane of the wave must call this)
-__device__ __forceinline__ void bn_total_tiles(const float* __restrict__ tiles, int n_tiles, int ch, int c, int lane, double& s1, double& s2) {
-  double a1 = 0.0, a2 = 0.0;
-  const float* const row = tiles + (size_t)c * n_tiles * 2;
-  for (int p = lane; p < n_tiles; p += 64) { a1 += (double)row[2 * p]; a2 += (double)row[2 * p + 1]; }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { a1 += __shfl_xor(a1, o); a2 += __shfl_xor(a2, o); }
-  s1 = a1; s2 = a2;
-}
 
 __device__ __forceinline__ RowAffine row_affine(const PairAffine& p, int c) {
   RowAffine r{1.f, 0.f, 1.f, 0.f, false, false};
@@ -394,7 +323,7 @@ __device__ __forceinline__ RowAffine row_affine(const PairBnIn& p, int c, int ch
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       double s1, s2;
-      bn_total(p.part, ch, c + e, s1, s2);
+      bn_total(p.part, ch, c + e, s1, s2, late_const(BN_G));
       const double mu = s1 / p.n;
       double var = s2 / p.n - mu * mu;
       var = var < 0.0 ? 0.0 : var;
@@ -500,13 +429,8 @@ __device__ __forceinline__ void fir_pair(const v2f* src, int q, int e0, int k8, 
   }
 }
 
-__device__ __forceinline__ void store_pair(float* ra, float* rb, const v2f (&acc)[8], int t, int lim) {
-  float a[8], b[8];
-#pragma unroll
-  for (int m = 0; m < 8; ++m) { const bool on = t + m < lim; a[m] = on ? acc[m][0] : 0.f; b[m] = on ? acc[m][1] : 0.f; }
-  store8(ra + t, a); store8(rb + t, b);
-}
-__device__ __forceinline__ void store_pair(bf16_t* ra, bf16_t* rb, const v2f (&acc)[8], int t, int lim) {
+template <class T>
+__device__ __forceinline__ void store_pair(T* ra, T* rb, const v2f (&acc)[8], int t, int lim) {
   float a[8], b[8];
 #pragma unroll
   for (int m = 0; m < 8; ++m) { const bool on = t + m < lim; a[m] = on ? acc[m][0] : 0.f; b[m] = on ? acc[m][1] : 0.f; }
@@ -650,7 +574,7 @@ __global__ __launch_bounds__(256) void dw_fwd_mfma_kernel(const bf16_t* __restri
   bool aff_on = false, aff_relu = false;
   if (aff.part || aff.tiles) {
     double s1, s2;
-    if (aff.tiles) bn_total_tiles(aff.tiles, aff.n_tiles, ch, c, lane, s1, s2); else bn_total(aff.part, ch, c, s1, s2);
+    if (aff.tiles) bn_total_tiles(aff.tiles, aff.n_tiles, ch, c, lane, s1, s2); else bn_total(aff.part, ch, c, s1, s2, late_const(BN_G));
     const double mu = s1 / aff.n;
     double var = s2 / aff.n - mu * mu;
     var = var < 0.0 ? 0.0 : var;
@@ -1151,521 +1075,9 @@ __global__ __launch_bounds__(256, TT <= 128 ? 2 : 1) void dw_bwd_mfma_kernel(con
   }
 }
 
-// ----------------------------------------------------------------------------------------------------------------------
-// Row-wise streaming kernels: one WAVE = one (row, 512-frame chunk) unit, 64 lanes x 8 elements (16 / 32 bytes per lane), four
-// units per 256-thread workgroup (a 10 s clip is 501 frames: with one workgroup per row three of its four waves had nothing to do).
-// Rows are pitched and 16-byte aligned, so every access is a whole vector; columns >= t are scratch and may be overwritten.
-// ----------------------------------------------------------------------------------------------------------------------
-constexpr int ROW_CHUNK = 512;
-// defines `row`, `chunk`, `i` (first frame of this lane) and returns from the kernel when the unit lies outside the tensor
-#define TS_ROW_UNIT(n_rows)                                                                   \
-  const int _cpr = (t + ROW_CHUNK - 1) / ROW_CHUNK;                                           \
-  const long long _u = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);                        \
-  const long long _r = _u / _cpr;                                                             \
-  const int row = (int)_r, chunk = (int)(_u % _cpr), i = chunk * ROW_CHUNK + (threadIdx.x & 63) * 8; \
-  if (_r >= (long long)(n_rows) || i >= t) return
-
-// y = x with frames >= len[b] zeroed (the re-masking in front of every MaskedConv1d, and of gradients on the way back)
-template <class T>
-__global__ __launch_bounds__(256) void mask_time_kernel(const T* __restrict__ x, const int* __restrict__ len, T* __restrict__ y,
-                                                        int batch, int ch, int t, int pitch_x, int pitch_y) {
-  TS_ROW_UNIT((long long)batch * ch);
-  const int b = row / ch;
-  const int l = clamp_len(len, b, t);
-  float v[8];
-  load8(x + (size_t)row * pitch_x + i, v);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) v[j] = i + j < l ? v[j] : 0.f;
-  store8(y + (size_t)row * pitch_y + i, v);
-}
-
-// Per-channel sums over all B*T frames in BN_G clip groups (grid ch x BN_G): part[g][c] = (s1, s2), fp64 accumulation; the
-// consumers add the BN_G partials in a fixed order (deterministic, no atomics).
-//   MODE 0 (forward statistics):  s1 = sum v,  s2 = sum v^2
-//   MODE 1 (backward statistics): g = dy * (y > 0 if relu), xhat = (v - mean) * rstd:  s1 = sum g,  s2 = sum g * xhat
-//          -- g and xhat are recomputed here and in the apply kernel instead of being written out and read back twice
-template <int MODE, class T>
-__global__ __launch_bounds__(256) void chan_sums_kernel(const T* __restrict__ a, const T* __restrict__ y, const T* __restrict__ v,
-                                                        const float* __restrict__ mean_rstd, double* __restrict__ part, int batch,
-                                                        int ch, int t, int pitch, int relu) {
-  __shared__ double r1[256], r2[256];
-  const int c = blockIdx.x, grp = blockIdx.y;
-  const int per = (batch + BN_G - 1) / BN_G;
-  const int b_lo = grp * per, b_hi = b_lo + per < batch ? b_lo + per : batch;
-  float mu = 0.f, rs = 0.f;
-  if (MODE == 1) { mu = mean_rstd[2 * c]; rs = mean_rstd[2 * c + 1]; }
-  double s1 = 0.0, s2 = 0.0;
-  for (int b = b_lo + (threadIdx.x >> 6); b < b_hi; b += 4) {          // one wave per clip row (a 10 s clip = 501 frames = 63 lanes x 8)
-    const size_t row = ((size_t)b * ch + c) * pitch;
-    for (int i = (threadIdx.x & 63) * 8; i < t; i += 512) {
-      float va[8], vy[8], vv[8];
-      load8(a + row + i, va);
-      if (MODE == 1) { load8(v + row + i, vv); if (relu) load8(y + row + i, vy); }
-      float p1 = 0.f, p2 = 0.f;                 // 8 terms in f32, then f64 across the row
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        if (i + j < t) {
-          if (MODE == 0) { p1 += va[j]; p2 = fmaf(va[j], va[j], p2); }
-          else {
-            const float gv = (relu && !(vy[j] > 0.f)) ? 0.f : va[j];
-            p1 += gv;
-            p2 = fmaf(gv, (vv[j] - mu) * rs, p2);
-          }
-        }
-      }
-      s1 += (double)p1; s2 += (double)p2;
-    }
-  }
-  r1[threadIdx.x] = s1; r2[threadIdx.x] = s2;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) { r1[threadIdx.x] += r1[threadIdx.x + o]; r2[threadIdx.x] += r2[threadIdx.x + o]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { part[((size_t)grp * ch + c) * 2] = r1[0]; part[((size_t)grp * ch + c) * 2 + 1] = r2[0]; }
-}
-
-// BatchNorm(train) forward: stats[c] = (sum v, sum v^2) -> mean, rstd (biased variance, eps), y = gamma*(v-mean)*rstd + beta [ReLU].
-template <class T>
-__global__ __launch_bounds__(256) void bn_fwd_kernel(const T* __restrict__ v, const double* __restrict__ part,
-                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                     T* __restrict__ y, float* __restrict__ mean_rstd, int batch, int ch, int t, int pitch,
-                                                     float eps, int relu, float* __restrict__ running_mean,
-                                                     float* __restrict__ running_var, float momentum,
-                                                     long long* __restrict__ num_batches_tracked, int ng) {
-  TS_ROW_UNIT((long long)batch * ch);
-  const int c = row % ch;
-  float mu, sc;
-  {                                                        // every lane forms the channel's statistics (a few double operations)
-    const double n = (double)batch * t;
-    double s1, s2;
-    bn_total(part, ch, c, s1, s2, ng);
-    const double m = s1 / n;
-    double var = s2 / n - m * m;
-    var = var < 0.0 ? 0.0 : var;
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-    mu = (float)m; sc = gamma[c] * rstd;
-    if (row < ch && chunk == 0 && (threadIdx.x & 63) == 0) {     // clip 0's wave of this channel publishes the statistics
-      mean_rstd[2 * c] = mu; mean_rstd[2 * c + 1] = rstd;
-      if (running_mean) {    // nn.BatchNorm1d's update: momentum blend of the batch mean and the UNBIASED batch variance
-        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mu;
-        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)(var * (n / (n > 1.0 ? n - 1.0 : 1.0)));
-        if (c == 0 && num_batches_tracked) *num_batches_tracked += 1;
-      }
-    }
-  }
-  const float be = beta[c];
-  float x[8];
-  load8(v + (size_t)row * pitch + i, x);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    float o = sc * (x[j] - mu) + be;
-    x[j] = (relu && !(o > 0.f)) ? 0.f : o;
-  }
-  store8(y + (size_t)row * pitch + i, x);
-}
-
-// Block tail (quartznet/blocks.py:332-337): out = relu(BatchNorm(v_a) + BatchNorm(v_b)) -- main branch and residual branch -- from the
-// clip-group sums of both in ONE pass (instead of two BatchNorm apply passes and an add + ReLU pass); publishes both mean_rstd and
-// applies both running-statistics updates.
-struct BnSide {
-  const void* v; const double* part; const float* gamma; const float* beta; float eps;
-  float* mean_rstd; float* running_mean; float* running_var; float momentum; long long* nbt;
-};
-template <class T>
-__global__ __launch_bounds__(256) void bn2_add_relu_kernel(BnSide a, BnSide b, T* __restrict__ out, int batch, int ch, int t, int pitch) {
-  TS_ROW_UNIT((long long)batch * ch);
-  const int c = row % ch;
-  float scs[2], hs[2];
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const BnSide& s = e == 0 ? a : b;
-    const double n = (double)batch * t;
-    double s1, s2;
-    bn_total(s.part, ch, c, s1, s2);
-    const double mu = s1 / n;
-    double var = s2 / n - mu * mu;
-    var = var < 0.0 ? 0.0 : var;
-    const float rstd = (float)(1.0 / sqrt(var + (double)s.eps));
-    scs[e] = s.gamma[c] * rstd; hs[e] = s.beta[c] - (float)mu * scs[e];
-    if (row < ch && chunk == 0 && (threadIdx.x & 63) == 0) {
-      s.mean_rstd[2 * c] = (float)mu; s.mean_rstd[2 * c + 1] = rstd;
-      if (s.running_mean) {
-        s.running_mean[c] = (1.f - s.momentum) * s.running_mean[c] + s.momentum * (float)mu;
-        s.running_var[c] = (1.f - s.momentum) * s.running_var[c] + s.momentum * (float)(var * (n / (n > 1.0 ? n - 1.0 : 1.0)));
-        if (c == 0 && s.nbt) *s.nbt += 1;
-      }
-    }
-  }
-  const float sa = scs[0], ha = hs[0] + hs[1], sb = scs[1];
-  float x[8], z[8];
-  load8(static_cast<const T*>(a.v) + (size_t)row * pitch + i, x);
-  load8(static_cast<const T*>(b.v) + (size_t)row * pitch + i, z);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float o = fmaf(x[j], sa, fmaf(z[j], sb, ha));
-    x[j] = o > 0.f ? o : 0.f;
-  }
-  store8(out + (size_t)row * pitch + i, x);
-}
-
-// ----------------------------------------------------------------------------------------------------------------------
-// Block tail in ONE launch each way (round 5): a workgroup owns a CHANNEL -- its batch x ceil(t / 512) row units of both branches live in
-// registers between the statistics and the apply step, so every tensor is read once and written once and no second launch has to wait for the
-// channel sums.  Replaces, per block, chan_sums<0> x 2 + bn2_add_relu (forward: 23 us -> one launch) and (chan_sums<1> + bn_bwd_apply) x 2
-// (backward: 38 us -> one launch) at 32 x 501 frames.  A wave holds up to CU_MAX units; larger batches keep the two-step kernels.
-// The variance is formed around the mean (two passes over the registers), not as E[x^2] - mean^2: f32 is then enough per lane, the sums across
-// lanes and waves run in f64 like the clip-group partials they replace.
-// ----------------------------------------------------------------------------------------------------------------------
-// rows stay in registers in their STORAGE form (bf16 rows: 4 VGPRs per 8 frames) and are widened where they are used
-template <class T> struct ChanRegs;
-template <> struct ChanRegs<bf16_t> {
-  static constexpr int UMAX = 8;
-  typedef u32x4 raw;
-  static __device__ __forceinline__ raw load(const bf16_t* p) { return *reinterpret_cast<const u32x4*>(p); }
-  static __device__ __forceinline__ void widen(const raw& r, float (&v)[8]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { v[2 * j] = bf16_lo(r[j]); v[2 * j + 1] = bf16_hi(r[j]); }
-  }
-  static __device__ __forceinline__ raw narrow(const float (&v)[8]) {        // exact for values that are bf16 already
-    return u32x4{pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]), pack_bf16(v[6], v[7])};
-  }
-  // the compiler would rather keep the widened floats alive across the reduction than convert twice (256 VGPRs, one wave per SIMD): an opaque
-  // touch of the storage registers makes the second widening a new computation
-  static __device__ __forceinline__ void pin(raw& r) { asm volatile("" : "+v"(r)); }
-};
-template <> struct ChanRegs<float> {
-  static constexpr int UMAX = 4;
-  struct raw { f32x4 lo, hi; };
-  static __device__ __forceinline__ raw load(const float* p) { return raw{*reinterpret_cast<const f32x4*>(p), *reinterpret_cast<const f32x4*>(p + 4)}; }
-  static __device__ __forceinline__ void widen(const raw& r, float (&v)[8]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { v[j] = r.lo[j]; v[4 + j] = r.hi[j]; }
-  }
-  static __device__ __forceinline__ raw narrow(const float (&v)[8]) { return raw{f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}}; }
-  static __device__ __forceinline__ void pin(raw&) {}
-};
-
-__device__ __forceinline__ double chan_reduce(double v, double* red) {      // all 256 threads -> the sum, in every thread
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();                                                          // `red` may still be read from the previous call
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
-struct Bn2FwdArgs {
-  BnSide a, b;
-  void* out;
-  int batch, ch, t, pitch;
-};
-
-template <class T>
-__global__ __launch_bounds__(256) void bn2_fwd_chan_kernel(const Bn2FwdArgs g) {
-  typedef ChanRegs<T> R;
-  constexpr int UMAX = R::UMAX;
-  __shared__ double red[4];
-  const int c = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int cpr = (g.t + ROW_CHUNK - 1) / ROW_CHUNK, units = g.batch * cpr;
-  const T* const va = static_cast<const T*>(g.a.v);
-  const T* const vb = static_cast<const T*>(g.b.v);
-  typename R::raw xa[UMAX], xb[UMAX];
-  int off[UMAX], nval[UMAX];                       // element offsets fit 31 bits (checked by the launcher)
-#pragma unroll
-  for (int u = 0; u < UMAX; ++u) {
-    const int unit = wave + 4 * u;
-    const int b = unit / cpr, i = (unit % cpr) * ROW_CHUNK + lane * 8;
-    nval[u] = unit < units ? (g.t - i < 0 ? 0 : (g.t - i > 8 ? 8 : g.t - i)) : 0;
-    off[u] = nval[u] > 0 ? (b * g.ch + c) * g.pitch + i : 0;
-    xa[u] = R::load(va + off[u]);                  // idle lanes re-read element 0: in bounds, never used
-    xb[u] = R::load(vb + off[u]);
-  }
-  const double n = (double)g.batch * g.t;
-  float scs[2], hs[2];
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const BnSide& sd = e == 0 ? g.a : g.b;
-    float p = 0.f;
-#pragma unroll
-    for (int u = 0; u < UMAX; ++u) {
-      float x[8];
-      R::widen(e == 0 ? xa[u] : xb[u], x);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) p += j < nval[u] ? x[j] : 0.f;
-    }
-    const double mu = chan_reduce((double)p, red) / n;
-    const float mf = (float)mu;
-    float q = 0.f;
-#pragma unroll
-    for (int u = 0; u < UMAX; ++u) {
-      float x[8];
-      R::pin(e == 0 ? xa[u] : xb[u]);
-      R::widen(e == 0 ? xa[u] : xb[u], x);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float d = x[j] - mf;
-        q = j < nval[u] ? fmaf(d, d, q) : q;
-      }
-    }
-    double var = chan_reduce((double)q, red) / n;
-    var -= (mu - (double)mf) * (mu - (double)mf);              // the deviations were taken from the f32-rounded mean
-    var = var < 0.0 ? 0.0 : var;
-    const float rstd = (float)(1.0 / sqrt(var + (double)sd.eps));
-    scs[e] = sd.gamma[c] * rstd; hs[e] = sd.beta[c] - mf * scs[e];
-    if (threadIdx.x == 0) {
-      sd.mean_rstd[2 * c] = mf; sd.mean_rstd[2 * c + 1] = rstd;
-      if (sd.running_mean) {
-        sd.running_mean[c] = (1.f - sd.momentum) * sd.running_mean[c] + sd.momentum * mf;
-        sd.running_var[c] = (1.f - sd.momentum) * sd.running_var[c] + sd.momentum * (float)(var * (n / (n > 1.0 ? n - 1.0 : 1.0)));
-        if (c == 0 && sd.nbt) *sd.nbt += 1;
-      }
-    }
-  }
-  const float sa = scs[0], sb = scs[1], ha = hs[0] + hs[1];
-  T* const out = static_cast<T*>(g.out);
-#pragma unroll
-  for (int u = 0; u < UMAX; ++u) {
-    if (nval[u] > 0) {
-      float x[8], z[8], o[8];
-      R::pin(xa[u]);
-      R::pin(xb[u]);
-      R::widen(xa[u], x);
-      R::widen(xb[u], z);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float r = fmaf(x[j], sa, fmaf(z[j], sb, ha));
-        o[j] = r > 0.f ? r : 0.f;
-      }
-      store8(out + off[u], o);
-    }
-  }
-}
-
-struct Bn2BwdArgs {
-  const void* dout; const void* dout2; const int* len2;     // dout2 (may be NULL): a second gradient of `out`, counted for frames < len2[clip] only
-  const void* out; const void* va; const void* vb;
-  const float* gamma_a; const float* mr_a; const float* gamma_b; const float* mr_b;
-  void* dva; void* dvb;
-  float* dgamma_a; float* dbeta_a; float* dgamma_b; float* dbeta_b;
-  int batch, ch, t, pitch;
-};
-
-// out = relu(BN_a(va) + BN_b(vb)):  g = dout * (out > 0);  dv_e = gamma_e rstd_e (g - mean(g) - xhat_e mean(g xhat_e)),  dbeta_e = sum g, dgamma_e = sum g xhat_e
-template <class T>
-__global__ __launch_bounds__(256) void bn2_bwd_chan_kernel(const Bn2BwdArgs g) {
-  typedef ChanRegs<T> R;
-  constexpr int UMAX = R::UMAX;
-  __shared__ double red[4];
-  const int c = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int cpr = (g.t + ROW_CHUNK - 1) / ROW_CHUNK, units = g.batch * cpr;
-  const float mua = g.mr_a[2 * c], rsa = g.mr_a[2 * c + 1], mub = g.mr_b[2 * c], rsb = g.mr_b[2 * c + 1];
-  typename R::raw gg[UMAX], xa[UMAX], xb[UMAX];    // the gated gradient and both un-normalised inputs, in storage form
-  int off[UMAX], nval[UMAX];
-  float p0 = 0.f, pa = 0.f, pb = 0.f;
-  // loads in batches of UB units (left alone the scheduler hoists all 4 UMAX row loads to the top: 256 VGPRs, one wave per SIMD)
-  constexpr int UB = UMAX < 4 ? UMAX : 4;
-#pragma unroll
-  for (int u0 = 0; u0 < UMAX; u0 += UB) {
-    typename R::raw dr[UB], orr[UB];
-#pragma unroll
-    for (int k = 0; k < UB; ++k) {
-      const int u = u0 + k, unit = wave + 4 * u;
-      const int b = unit / cpr, i = (unit % cpr) * ROW_CHUNK + lane * 8;
-      nval[u] = unit < units ? (g.t - i < 0 ? 0 : (g.t - i > 8 ? 8 : g.t - i)) : 0;
-      off[u] = nval[u] > 0 ? (b * g.ch + c) * g.pitch + i : 0;
-      xa[u] = R::load(static_cast<const T*>(g.va) + off[u]);
-      xb[u] = R::load(static_cast<const T*>(g.vb) + off[u]);
-      dr[k] = R::load(static_cast<const T*>(g.dout) + off[u]);
-      orr[k] = R::load(static_cast<const T*>(g.out) + off[u]);
-      if (g.dout2) {
-        // the block's output fed two consumers (the next block's main and residual branch): their gradients are added HERE instead of in a pass
-        // of their own (Fork.backward's ts_train_add); the residual branch's input mask zeroes its share from the clip's length on
-        float d1[8], d2[8];
-        R::widen(dr[k], d1);
-        R::widen(R::load(static_cast<const T*>(g.dout2) + off[u]), d2);
-        const int l2 = g.len2 ? g.len2[b] : 0x7fffffff;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) d1[j] += i + j < l2 ? d2[j] : 0.f;
-        dr[k] = R::narrow(d1);                     // bf16 rows: rounded like the stored sum of the separate pass
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < UB; ++k) {
-      const int u = u0 + k;
-      float d[8], o[8], x[8], z[8];
-      R::widen(dr[k], d);
-      R::widen(orr[k], o);
-      R::widen(xa[u], x);
-      R::widen(xb[u], z);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const bool in = j < nval[u];                       // columns >= t are scratch: they may hold anything, NaN included
-        d[j] = (in && o[j] > 0.f) ? d[j] : 0.f;
-        p0 += d[j];
-        pa = fmaf(d[j], in ? (x[j] - mua) * rsa : 0.f, pa);
-        pb = fmaf(d[j], in ? (z[j] - mub) * rsb : 0.f, pb);
-      }
-      gg[u] = R::narrow(d);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  const double n = (double)g.batch * g.t;
-  const double s0 = chan_reduce((double)p0, red), sa = chan_reduce((double)pa, red), sb = chan_reduce((double)pb, red);
-  if (threadIdx.x == 0) {
-    g.dbeta_a[c] = (float)s0; g.dgamma_a[c] = (float)sa;
-    g.dbeta_b[c] = (float)s0; g.dgamma_b[c] = (float)sb;
-  }
-  const float mg = (float)(s0 / n), mga = (float)(sa / n), mgb = (float)(sb / n);
-  const float ka = g.gamma_a[c] * rsa, kb = g.gamma_b[c] * rsb;
-#pragma unroll
-  for (int u = 0; u < UMAX; ++u) {
-    if (nval[u] > 0) {
-      float d[8], x[8], z[8], da[8], db[8];
-      R::pin(gg[u]);
-      R::pin(xa[u]);
-      R::pin(xb[u]);
-      R::widen(gg[u], d);
-      R::widen(xa[u], x);
-      R::widen(xb[u], z);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        da[j] = ka * (d[j] - mg - (x[j] - mua) * rsa * mga);
-        db[j] = kb * (d[j] - mg - (z[j] - mub) * rsb * mgb);
-      }
-      store8(static_cast<T*>(g.dva) + off[u], da);
-      store8(static_cast<T*>(g.dvb) + off[u], db);
-    }
-  }
-}
-
-// dv = gamma*rstd * (g - mean(g) - xhat * mean(g*xhat)),  g = dy * (y > 0) when relu,  xhat = (v - mean) * rstd
-template <class T>
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__ dy, const T* __restrict__ y, const T* __restrict__ v,
-                                                           const double* __restrict__ part, const float* __restrict__ gamma,
-                                                           const float* __restrict__ mean_rstd, T* __restrict__ dv,
-                                                           float* __restrict__ dgamma, float* __restrict__ dbeta, int batch, int ch, int t,
-                                                           int pitch, int relu) {
-  TS_ROW_UNIT((long long)batch * ch);
-  const int c = row % ch;
-  float mg, mgx;
-  {
-    const double n = (double)batch * t;
-    double s1, s2;
-    bn_total(part, ch, c, s1, s2);
-    mg = (float)(s1 / n); mgx = (float)(s2 / n);
-    if (row < ch && chunk == 0 && (threadIdx.x & 63) == 0) { dbeta[c] = (float)s1; dgamma[c] = (float)s2; }
-  }
-  const float mu = mean_rstd[2 * c], rs = mean_rstd[2 * c + 1], k = gamma[c] * rs;
-  const size_t base = (size_t)row * pitch + i;
-  float g[8], vy[8], vv[8];
-  load8(dy + base, g);
-  load8(v + base, vv);
-  if (relu) load8(y + base, vy);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float gj = (relu && !(vy[j] > 0.f)) ? 0.f : g[j];
-    g[j] = k * (gj - mg - (vv[j] - mu) * rs * mgx);
-  }
-  store8(dv + base, g);
-}
-
-// second half of a BatchNorm(train) backward whose first half ran in dw_bwd_pair_kernel's epilogue: g = dL/dy * (y > 0) is stored,
-// S1 = sum g (= dbeta) and S2 = sum g * xhat (= dgamma) are complete:  dv = gamma * rstd * (g - S1 / n - xhat * S2 / n)
-template <class T>
-__global__ __launch_bounds__(256) void bn_bwd_sums_kernel(const T* __restrict__ g, const T* __restrict__ v, const float* __restrict__ gamma,
-                                                          const float* __restrict__ mean_rstd, const float* __restrict__ dgamma,
-                                                          const float* __restrict__ dbeta, T* __restrict__ dv, int batch, int ch, int t, int pitch) {
-  TS_ROW_UNIT((long long)batch * ch);
-  const int c = row % ch;
-  const float inv_n = 1.f / ((float)batch * (float)t);
-  const float mg = dbeta[c] * inv_n, mgx = dgamma[c] * inv_n, mu = mean_rstd[2 * c], rs = mean_rstd[2 * c + 1], k = gamma[c] * rs;
-  const size_t base = (size_t)row * pitch + i;
-  float gg[8], vv[8];
-  load8(g + base, gg);
-  load8(v + base, vv);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) gg[j] = k * (gg[j] - mg - (vv[j] - mu) * rs * mgx);
-  store8(dv + base, gg);
-}
-
-// out = relu(a + b) (RELU) or a + b; backward of the first: da = db = dout * (out > 0)
-template <class T, bool RELU>
-__device__ __forceinline__ void add_rows(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ o, long long rows, int t, int pitch,
-                                         const int* __restrict__ len_b = nullptr, int ch = 1) {
-  TS_ROW_UNIT(rows);
-  const size_t base = (size_t)row * pitch + i;
-  float x[8], z[8];
-  load8(a + base, x);
-  if (b) load8(b + base, z);
-  if (len_b) {                                             // b counts only up to its clip's length (the mask of a MaskedConv1d input, backward)
-    const int l = clamp_len(len_b, row / ch, t);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) z[j] = i + j < l ? z[j] : 0.f;
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { const float s = x[j] + (b ? z[j] : 0.f); x[j] = (!RELU || s > 0.f) ? s : 0.f; }
-  store8(o + base, x);
-}
-template <class T>
-__global__ __launch_bounds__(256) void add_relu_fwd_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ o, long long rows, int t, int pitch) {
-  add_rows<T, true>(a, b, o, rows, t, pitch);
-}
-template <class T>
-__global__ __launch_bounds__(256) void add_fwd_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ o, long long rows, int t, int pitch,
-                                                      const int* __restrict__ len_b, int ch) {
-  add_rows<T, false>(a, b, o, rows, t, pitch, len_b, ch);
-}
-template <class T>
-__global__ __launch_bounds__(256) void relu_bwd_kernel(const T* __restrict__ dout, const T* __restrict__ out, T* __restrict__ din, long long rows, int t, int pitch) {
-  TS_ROW_UNIT(rows);
-  const size_t base = (size_t)row * pitch + i;
-  float g[8], o[8];
-  load8(dout + base, g);
-  load8(out + base, o);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) g[j] = o[j] > 0.f ? g[j] : 0.f;
-  store8(din + base, g);
-}
-
-// sum of `parts` partial [rows] vectors (the per-clip dW of the pointwise backward)
-__global__ __launch_bounds__(256) void sum_parts_kernel(const float* __restrict__ parts, float* __restrict__ out, long long rows, int n_parts) {
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= rows) return;
-  float s = 0.f;
-  for (int i = 0; i < n_parts; ++i) s += parts[(size_t)i * rows + idx];
-  out[idx] = s;
-}
-
-// reference-layout f32 [rows][t] (contiguous) <-> pitched activation rows of either type: the boundary of the training path
-template <class T>
-__global__ __launch_bounds__(256) void act_import_kernel(const float* __restrict__ src, T* __restrict__ dst, long long rows, int t, int pitch) {
-  TS_ROW_UNIT(rows);
-  float v[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) v[j] = i + j < t ? src[(size_t)row * t + i + j] : 0.f;
-  store8(dst + (size_t)row * pitch + i, v);
-}
-template <class T>
-__global__ __launch_bounds__(256) void act_export_kernel(const T* __restrict__ src, float* __restrict__ dst, long long rows, int t, int pitch) {
-  TS_ROW_UNIT(rows);
-  float v[8];
-  load8(src + (size_t)row * pitch + i, v);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) if (i + j < t) dst[(size_t)row * t + i + j] = v[j];
-}
-
-static inline unsigned blocks(long long n) { return (unsigned)((n + 255) / 256); }
-static inline dim3 row_grid(long long rows, int t) { return dim3((unsigned)((rows * ((t + ROW_CHUNK - 1) / ROW_CHUNK) + 3) / 4)); }
-static inline bool rows_ok(const void* p, int pitch, int act) {
-  return pitch % 8 == 0 && reinterpret_cast<uintptr_t>(p) % (act ? 16 : 32) == 0;
-}
-
 }  // namespace ts
 
 using namespace ts;
-#define TS_STREAM hipStream_t stream = reinterpret_cast<hipStream_t>(stream_); (void)hipGetLastError()
-// dispatch on the activation type: ACT(kernel, grid, block, lds, args...) launches kernel<float> or kernel<bf16_t>
 // the "same" geometry the pair kernels cover
 static bool pair_geometry(int ch, int t_in, int t_out, int k, int stride, int dil, int pad, int pitch_in, int pitch_out) {
   return stride == 1 && dil == 1 && (k & 1) && pad == (k - 1) / 2 && t_in == t_out && (ch & 1) == 0 && pitch_in == pitch_out && k <= DW_KMAX;
@@ -1675,8 +1087,6 @@ static bool pair_geometry(int ch, int t_in, int t_out, int k, int stride, int di
 static bool phase_geometry(int t_in, int t_out, int k, int stride, int dil, int pad, int pitch_in, int pitch_out) {
   return stride == 1 && dil == 2 && (k & 1) && pad == k - 1 && (pad & 1) == 0 && t_in == t_out && pitch_in == pitch_out && k <= DW_KMAX;
 }
-
-#define TS_ACT(act, expr_f32, expr_bf16) do { if (act) { expr_bf16; } else { expr_f32; } } while (0)
 
 static int dwconv_fwd_impl(const void* x, const int32_t* len_in, const int32_t* len_out, const float* w, void* y, int32_t batch,
                            int32_t ch, int32_t t_in, int32_t t_out, int32_t k, int32_t stride, int32_t dil, int32_t pad,
@@ -1705,11 +1115,11 @@ static int dwconv_fwd_impl(const void* x, const int32_t* len_in, const int32_t* 
     const long long n_pairs = (long long)batch * ch / 2;
     const int ppw = n_pairs >= 32LL * cu_count() ? 2 : 1;
     const dim3 grid2((unsigned)((n_pairs + 4 * ppw - 1) / (4 * ppw)));
-    TS_ACT(act,
-           hipLaunchKernelGGL(dw_fwd_pair_kernel<float>, grid2, dim3(256), lds2, stream, (const float*)x, len_in, len_out, w, (float*)y, batch, ch,
-                              t_in, k, pad, pitch_in, ppw, aff),
-           hipLaunchKernelGGL(dw_fwd_pair_kernel<bf16_t>, grid2, dim3(256), lds2, stream, (const bf16_t*)x, len_in, len_out, w, (bf16_t*)y, batch,
-                              ch, t_in, k, pad, pitch_in, ppw, aff));
+    act_dispatch(act, [&](auto tag) {
+      using T = decltype(tag);
+      hipLaunchKernelGGL(dw_fwd_pair_kernel<T>, grid2, dim3(256), lds2, stream, as<T>(x), len_in, len_out, w, as<T>(y), batch, ch, t_in, k, pad,
+                         pitch_in, ppw, aff);
+    });
     return hip_status(hipGetLastError());
   }
   if (phase_geometry(t_in, t_out, k, stride, dil, pad, pitch_in, pitch_out)) {
@@ -1717,21 +1127,21 @@ static int dwconv_fwd_impl(const void* x, const int32_t* len_in, const int32_t* 
     const long long n_rows = (long long)batch * ch;
     const int ppw = n_rows >= 32LL * cu_count() ? 2 : 1;
     const dim3 grid2((unsigned)((n_rows + 4 * ppw - 1) / (4 * ppw)));
-    TS_ACT(act,
-           { hipLaunchKernelGGL((dw_fwd_pair_kernel<float, true>), grid2, dim3(256), lds2, stream, (const float*)x, len_in, len_out, w, (float*)y, batch, ch,
-                               t_in, k, pad / 2, pitch_in, ppw, aff); },
-           { hipLaunchKernelGGL((dw_fwd_pair_kernel<bf16_t, true>), grid2, dim3(256), lds2, stream, (const bf16_t*)x, len_in, len_out, w, (bf16_t*)y, batch,
-                               ch, t_in, k, pad / 2, pitch_in, ppw, aff); });
+    act_dispatch(act, [&](auto tag) {
+      using T = decltype(tag);
+      hipLaunchKernelGGL((dw_fwd_pair_kernel<T, true>), grid2, dim3(256), lds2, stream, as<T>(x), len_in, len_out, w, as<T>(y), batch, ch, t_in, k,
+                         pad / 2, pitch_in, ppw, aff);
+    });
     return hip_status(hipGetLastError());
   }
   const size_t lds = (DW_KMAX + (size_t)(DW_TILE - 1) * stride + (size_t)(k - 1) * dil + 1 + 32) * sizeof(float);
   if (lds > 64 * 1024) return TS_EUNSUPPORTED;
   const dim3 grid((t_out + DW_TILE - 1) / DW_TILE, batch * ch);
-  TS_ACT(act,
-         hipLaunchKernelGGL(dw_fwd_kernel<float>, grid, dim3(256), lds, stream, (const float*)x, len_in, len_out, w, (float*)y, batch, ch, t_in,
-                            t_out, k, stride, dil, pad, pitch_in, pitch_out),
-         hipLaunchKernelGGL(dw_fwd_kernel<bf16_t>, grid, dim3(256), lds, stream, (const bf16_t*)x, len_in, len_out, w, (bf16_t*)y, batch, ch, t_in,
-                            t_out, k, stride, dil, pad, pitch_in, pitch_out));
+  act_dispatch(act, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(dw_fwd_kernel<T>, grid, dim3(256), lds, stream, as<T>(x), len_in, len_out, w, as<T>(y), batch, ch, t_in, t_out, k, stride,
+                       dil, pad, pitch_in, pitch_out);
+  });
   return hip_status(hipGetLastError());
 }
 
@@ -1868,38 +1278,37 @@ static int dwconv_bwd_impl(const void* dy, const void* x, const int32_t* len_in,
   TS_STREAM;
   if (k > DW_KMAX) return TS_EUNSUPPORTED;
   if (aff.mean_rstd && !pair_geometry(ch, t_in, t_out, k, stride, dil, pad, pitch_in, pitch_out)) return TS_EUNSUPPORTED;
+  const int cpw = batch >= 16 ? (batch + 15) / 16 : 1;          // fused kernels: >= 2 clips per wave, the second clip's loads overlap the first one's FIR
   if (pair_geometry(ch, t_in, t_out, k, stride, dil, pad, pitch_in, pitch_out)) {
     if (act == 1 && g_dw_bwd_mfma) {
       const int st = dw_bwd_mfma_launch(dy, x, len_in, len_out, w, dx, dw, batch, ch, t_in, k, pad, pitch_in, aff, in_dgamma, in_dbeta, stream);
       if (st != TS_EUNSUPPORTED) return st;
     }
     const size_t lds2 = 4 * (size_t)(pair_xl(round_up(k + 7, 8)) + pair_gl(k, pad) + PAIR_TAPS) * sizeof(v2f);
-    const int cpw = batch >= 16 ? (batch + 15) / 16 : 1;        // >= 2 clips per wave: the second clip's loads overlap the first one's FIR
     const dim3 grid2(ch / 2, (batch + 4 * cpw - 1) / (4 * cpw));
     int dst = TS_OK;
     float* const part = det_workspace((int)grid2.y, ch, k, &dst);
     if (dst != TS_OK) return dst;
-    TS_ACT(act,
-           hipLaunchKernelGGL(dw_bwd_pair_kernel<float>, grid2, dim3(256), lds2, stream, (const float*)dy, (const float*)x, len_in, len_out, w,
-                              (float*)dx, dw, batch, ch, t_in, k, pad, pitch_in, cpw, aff, in_dgamma, in_dbeta, part),
-           hipLaunchKernelGGL(dw_bwd_pair_kernel<bf16_t>, grid2, dim3(256), lds2, stream, (const bf16_t*)dy, (const bf16_t*)x, len_in, len_out, w,
-                              (bf16_t*)dx, dw, batch, ch, t_in, k, pad, pitch_in, cpw, aff, in_dgamma, in_dbeta, part));
+    act_dispatch(act, [&](auto tag) {
+      using T = decltype(tag);
+      hipLaunchKernelGGL(dw_bwd_pair_kernel<T>, grid2, dim3(256), lds2, stream, as<T>(dy), as<T>(x), len_in, len_out, w, as<T>(dx), dw, batch, ch,
+                         t_in, k, pad, pitch_in, cpw, aff, in_dgamma, in_dbeta, part);
+    });
     dst = hip_status(hipGetLastError());
     if (dst == TS_OK && part) dst = det_reduce(part, (int)grid2.y, ch, k, dw, aff.mean_rstd ? in_dgamma : nullptr, aff.mean_rstd ? in_dbeta : nullptr, stream);
     return dst;
   }
   if (phase_geometry(t_in, t_out, k, stride, dil, pad, pitch_in, pitch_out)) {
     const size_t lds2 = 4 * (size_t)(pair_xl(round_up(k + 7, 8)) + pair_gl(k, pad / 2) + PAIR_TAPS) * sizeof(v2f);
-    const int cpw = batch >= 16 ? (batch + 15) / 16 : 1;
     const dim3 grid2(ch, (batch + 4 * cpw - 1) / (4 * cpw));
     int dst = TS_OK;
     float* const part = det_workspace((int)grid2.y, ch, k, &dst);
     if (dst != TS_OK) return dst;
-    TS_ACT(act,
-           { hipLaunchKernelGGL((dw_bwd_pair_kernel<float, true>), grid2, dim3(256), lds2, stream, (const float*)dy, (const float*)x, len_in, len_out, w,
-                               (float*)dx, dw, batch, ch, t_in, k, pad / 2, pitch_in, cpw, aff, in_dgamma, in_dbeta, part); },
-           { hipLaunchKernelGGL((dw_bwd_pair_kernel<bf16_t, true>), grid2, dim3(256), lds2, stream, (const bf16_t*)dy, (const bf16_t*)x, len_in, len_out, w,
-                               (bf16_t*)dx, dw, batch, ch, t_in, k, pad / 2, pitch_in, cpw, aff, in_dgamma, in_dbeta, part); });
+    act_dispatch(act, [&](auto tag) {
+      using T = decltype(tag);
+      hipLaunchKernelGGL((dw_bwd_pair_kernel<T, true>), grid2, dim3(256), lds2, stream, as<T>(dy), as<T>(x), len_in, len_out, w, as<T>(dx), dw, batch,
+                         ch, t_in, k, pad / 2, pitch_in, cpw, aff, in_dgamma, in_dbeta, part);
+    });
     dst = hip_status(hipGetLastError());
     if (dst == TS_OK && part) dst = det_reduce(part, (int)grid2.y, ch, k, dw, nullptr, nullptr, stream);
     return dst;
@@ -1910,20 +1319,20 @@ static int dwconv_bwd_impl(const void* dy, const void* x, const int32_t* len_in,
   if (lds_d > 64 * 1024 || lds_w > 64 * 1024) return TS_EUNSUPPORTED;
   const dim3 gd((t_in + DW_TILE - 1) / DW_TILE, batch * ch), gw(ch, batch < 8 ? batch : 8);
   if (dx)
-  TS_ACT(act,
-         hipLaunchKernelGGL(dw_bwd_data_kernel<float>, gd, dim3(256), lds_d, stream, (const float*)dy, len_in, len_out, w, (float*)dx, batch, ch,
-                            t_in, t_out, k, stride, dil, pad, pitch_in, pitch_out),
-         hipLaunchKernelGGL(dw_bwd_data_kernel<bf16_t>, gd, dim3(256), lds_d, stream, (const bf16_t*)dy, len_in, len_out, w, (bf16_t*)dx, batch, ch,
-                            t_in, t_out, k, stride, dil, pad, pitch_in, pitch_out));
+    act_dispatch(act, [&](auto tag) {
+      using T = decltype(tag);
+      hipLaunchKernelGGL(dw_bwd_data_kernel<T>, gd, dim3(256), lds_d, stream, as<T>(dy), len_in, len_out, w, as<T>(dx), batch, ch, t_in, t_out, k,
+                         stride, dil, pad, pitch_in, pitch_out);
+    });
   if (dw) {
     int dst = TS_OK;
     float* const part = det_workspace((int)gw.y, ch, k, &dst);
     if (dst != TS_OK) return dst;
-    TS_ACT(act,
-           hipLaunchKernelGGL(dw_bwd_weight_kernel<float>, gw, dim3(256), lds_w, stream, (const float*)dy, (const float*)x, len_in, len_out, dw, batch,
-                              ch, t_in, t_out, k, stride, dil, pad, pitch_in, pitch_out, part),
-           hipLaunchKernelGGL(dw_bwd_weight_kernel<bf16_t>, gw, dim3(256), lds_w, stream, (const bf16_t*)dy, (const bf16_t*)x, len_in, len_out, dw, batch,
-                              ch, t_in, t_out, k, stride, dil, pad, pitch_in, pitch_out, part));
+    act_dispatch(act, [&](auto tag) {
+      using T = decltype(tag);
+      hipLaunchKernelGGL(dw_bwd_weight_kernel<T>, gw, dim3(256), lds_w, stream, as<T>(dy), as<T>(x), len_in, len_out, dw, batch, ch, t_in, t_out, k,
+                         stride, dil, pad, pitch_in, pitch_out, part);
+    });
     if (part) {
       dst = hip_status(hipGetLastError());
       if (dst != TS_OK) return dst;
@@ -1949,256 +1358,4 @@ extern "C" int ts_train_dwconv_bwd_bn(const void* dy, const void* v, const float
   if (!in_mean_rstd || !in_gamma || !in_beta || !in_dgamma || !in_dbeta) return TS_EINVAL;
   return dwconv_bwd_impl(dy, v, len_in, len_out, w, g, dw, batch, ch, t, t, k, 1, 1, pad, pitch, pitch, act, stream_,
                          PairAffine{in_mean_rstd, in_gamma, in_beta, in_relu}, in_dgamma, in_dbeta);
-}
-
-// BatchNorm(train) batch sums without the apply pass: sums = double [8 clip groups][C][2] (sum v, sum v^2), consumed by
-// ts_train_dwconv_fwd_bn
-extern "C" int ts_train_bn_stats(const void* v, void* sums, int32_t batch, int32_t ch, int32_t t, int32_t pitch, int32_t act, void* stream_) {
-  if (!v || !sums || batch <= 0 || ch <= 0 || t <= 0 || act < 0 || act > 1 || !rows_ok(v, pitch, act) || pitch < t) return TS_EINVAL;
-  TS_STREAM;
-  double* part = static_cast<double*>(sums);
-  TS_ACT(act,
-         hipLaunchKernelGGL((chan_sums_kernel<0, float>), dim3(ch, BN_G), dim3(256), 0, stream, (const float*)v, (const float*)nullptr, (const float*)nullptr,
-                            (const float*)nullptr, part, batch, ch, t, pitch, 0),
-         hipLaunchKernelGGL((chan_sums_kernel<0, bf16_t>), dim3(ch, BN_G), dim3(256), 0, stream, (const bf16_t*)v, (const bf16_t*)nullptr, (const bf16_t*)nullptr,
-                            (const float*)nullptr, part, batch, ch, t, pitch, 0));
-  return hip_status(hipGetLastError());
-}
-
-extern "C" int ts_train_bn2_add_relu_fwd(const void* va, const void* sums_a, const float* gamma_a, const float* beta_a, float eps_a,
-                                         float* mean_rstd_a, float* running_mean_a, float* running_var_a, float momentum_a, int64_t* nbt_a,
-                                         const void* vb, const void* sums_b, const float* gamma_b, const float* beta_b, float eps_b,
-                                         float* mean_rstd_b, float* running_mean_b, float* running_var_b, float momentum_b, int64_t* nbt_b,
-                                         void* out, int32_t batch, int32_t ch, int32_t t, int32_t pitch, int32_t act, void* stream_) {
-  if (!va || !sums_a || !gamma_a || !beta_a || !mean_rstd_a || !vb || !sums_b || !gamma_b || !beta_b || !mean_rstd_b || !out) return TS_EINVAL;
-  if (batch <= 0 || ch <= 0 || t <= 0 || act < 0 || act > 1 || pitch < t) return TS_EINVAL;
-  if ((running_mean_a == nullptr) != (running_var_a == nullptr) || (running_mean_b == nullptr) != (running_var_b == nullptr)) return TS_EINVAL;
-  if (!rows_ok(va, pitch, act) || !rows_ok(vb, pitch, act) || !rows_ok(out, pitch, act)) return TS_EINVAL;
-  TS_STREAM;
-  const BnSide a{va, static_cast<const double*>(sums_a), gamma_a, beta_a, eps_a, mean_rstd_a, running_mean_a, running_var_a, momentum_a,
-                 reinterpret_cast<long long*>(nbt_a)};
-  const BnSide b{vb, static_cast<const double*>(sums_b), gamma_b, beta_b, eps_b, mean_rstd_b, running_mean_b, running_var_b, momentum_b,
-                 reinterpret_cast<long long*>(nbt_b)};
-  const dim3 rg = row_grid((long long)batch * ch, t);
-  TS_ACT(act,
-         hipLaunchKernelGGL(bn2_add_relu_kernel<float>, rg, dim3(256), 0, stream, a, b, (float*)out, batch, ch, t, pitch),
-         hipLaunchKernelGGL(bn2_add_relu_kernel<bf16_t>, rg, dim3(256), 0, stream, a, b, (bf16_t*)out, batch, ch, t, pitch));
-  return hip_status(hipGetLastError());
-}
-
-/* Block tail forward without separate statistics passes (one workgroup per channel, rows in registers); TS_EUNSUPPORTED when the batch does not
- * fit the register budget (callers then run ts_train_bn_stats x 2 + ts_train_bn2_add_relu_fwd).  See include/thunder_speech_amd.h */
-extern "C" int ts_train_bn2_add_relu_chan_fwd(const void* va, const float* gamma_a, const float* beta_a, float eps_a, float* mean_rstd_a,
-                                              float* running_mean_a, float* running_var_a, float momentum_a, int64_t* nbt_a, const void* vb,
-                                              const float* gamma_b, const float* beta_b, float eps_b, float* mean_rstd_b, float* running_mean_b,
-                                              float* running_var_b, float momentum_b, int64_t* nbt_b, void* out, int32_t batch, int32_t ch, int32_t t,
-                                              int32_t pitch, int32_t act, void* stream_) {
-  if (!va || !vb || !gamma_a || !beta_a || !gamma_b || !beta_b || !mean_rstd_a || !mean_rstd_b || !out) return TS_EINVAL;
-  if (batch <= 0 || ch <= 0 || t <= 0 || pitch < t || pitch % 8 || act < 0 || act > 1) return TS_EINVAL;
-  const int units = batch * ((t + ROW_CHUNK - 1) / ROW_CHUNK);
-  if (units > 4 * (act ? ChanRegs<bf16_t>::UMAX : ChanRegs<float>::UMAX) || (long long)batch * ch * pitch >= (1ll << 31)) return TS_EUNSUPPORTED;
-  hipStream_t stream = (hipStream_t)stream_;
-  Bn2FwdArgs g{};
-  g.a = BnSide{va, nullptr, gamma_a, beta_a, eps_a, mean_rstd_a, running_mean_a, running_var_a, momentum_a, (long long*)nbt_a};
-  g.b = BnSide{vb, nullptr, gamma_b, beta_b, eps_b, mean_rstd_b, running_mean_b, running_var_b, momentum_b, (long long*)nbt_b};
-  g.out = out; g.batch = batch; g.ch = ch; g.t = t; g.pitch = pitch;
-  (void)hipGetLastError();
-  TS_ACT(act, hipLaunchKernelGGL(bn2_fwd_chan_kernel<float>, dim3(ch), dim3(256), 0, stream, g),
-         hipLaunchKernelGGL(bn2_fwd_chan_kernel<bf16_t>, dim3(ch), dim3(256), 0, stream, g));
-  return hip_status(hipGetLastError());
-}
-
-/* Backward of the block tail, both branches, one launch (same budget rule) */
-extern "C" int ts_train_bn2_chan_bwd(const void* dout, const void* dout2, const int32_t* len2, const void* out, const void* va, const void* vb, const float* gamma_a, const float* mean_rstd_a,
-                                     const float* gamma_b, const float* mean_rstd_b, void* dva, void* dvb, float* dgamma_a, float* dbeta_a,
-                                     float* dgamma_b, float* dbeta_b, int32_t batch, int32_t ch, int32_t t, int32_t pitch, int32_t act, void* stream_) {
-  if (!dout || !out || !va || !vb || !gamma_a || !gamma_b || !mean_rstd_a || !mean_rstd_b || !dva || !dvb || !dgamma_a || !dbeta_a || !dgamma_b || !dbeta_b)
-    return TS_EINVAL;
-  if (batch <= 0 || ch <= 0 || t <= 0 || pitch < t || pitch % 8 || act < 0 || act > 1) return TS_EINVAL;
-  const int units = batch * ((t + ROW_CHUNK - 1) / ROW_CHUNK);
-  if (units > 4 * (act ? ChanRegs<bf16_t>::UMAX : ChanRegs<float>::UMAX) || (long long)batch * ch * pitch >= (1ll << 31)) return TS_EUNSUPPORTED;
-  hipStream_t stream = (hipStream_t)stream_;
-  const Bn2BwdArgs g{dout, dout2, len2, out, va, vb, gamma_a, mean_rstd_a, gamma_b, mean_rstd_b, dva, dvb, dgamma_a, dbeta_a, dgamma_b, dbeta_b, batch, ch, t, pitch};
-  (void)hipGetLastError();
-  TS_ACT(act, hipLaunchKernelGGL(bn2_bwd_chan_kernel<float>, dim3(ch), dim3(256), 0, stream, g),
-         hipLaunchKernelGGL(bn2_bwd_chan_kernel<bf16_t>, dim3(ch), dim3(256), 0, stream, g));
-  return hip_status(hipGetLastError());
-}
-
-extern "C" int ts_train_bn_bwd_sums(const void* g, const void* v, const float* gamma, const float* mean_rstd, const float* dgamma,
-                                    const float* dbeta, void* dv, int32_t batch, int32_t ch, int32_t t, int32_t pitch, int32_t act, void* stream_) {
-  if (!g || !v || !gamma || !mean_rstd || !dgamma || !dbeta || !dv || batch <= 0 || ch <= 0 || t <= 0 || act < 0 || act > 1) return TS_EINVAL;
-  if (!rows_ok(g, pitch, act) || !rows_ok(v, pitch, act) || !rows_ok(dv, pitch, act) || pitch < t) return TS_EINVAL;
-  TS_STREAM;
-  const dim3 rg = row_grid((long long)batch * ch, t);
-  TS_ACT(act,
-         hipLaunchKernelGGL(bn_bwd_sums_kernel<float>, rg, dim3(256), 0, stream, (const float*)g, (const float*)v, gamma, mean_rstd, dgamma, dbeta, (float*)dv,
-                            batch, ch, t, pitch),
-         hipLaunchKernelGGL(bn_bwd_sums_kernel<bf16_t>, rg, dim3(256), 0, stream, (const bf16_t*)g, (const bf16_t*)v, gamma, mean_rstd, dgamma, dbeta, (bf16_t*)dv,
-                            batch, ch, t, pitch));
-  return hip_status(hipGetLastError());
-}
-
-extern "C" int ts_train_mask_time(const void* x, const int32_t* len, void* y, int32_t batch, int32_t ch, int32_t t, int32_t pitch_x,
-                                  int32_t pitch_y, int32_t act, void* stream_) {
-  if (!x || !len || !y || batch <= 0 || ch <= 0 || t <= 0 || act < 0 || act > 1) return TS_EINVAL;
-  if (!rows_ok(x, pitch_x, act) || !rows_ok(y, pitch_y, act) || pitch_x < t || pitch_y < t) return TS_EINVAL;
-  TS_STREAM;
-  TS_ACT(act,
-         hipLaunchKernelGGL(mask_time_kernel<float>, row_grid((long long)batch * ch, t), dim3(256), 0, stream, (const float*)x, len, (float*)y, batch, ch, t, pitch_x, pitch_y),
-         hipLaunchKernelGGL(mask_time_kernel<bf16_t>, row_grid((long long)batch * ch, t), dim3(256), 0, stream, (const bf16_t*)x, len, (bf16_t*)y, batch, ch, t, pitch_x, pitch_y));
-  return hip_status(hipGetLastError());
-}
-
-extern "C" int ts_train_act_import(const float* src, void* dst, int64_t rows, int32_t t, int32_t pitch, int32_t act, void* stream_) {
-  if (!src || !dst || rows <= 0 || t <= 0 || pitch < t || act < 0 || act > 1 || !rows_ok(dst, pitch, act)) return TS_EINVAL;
-  TS_STREAM;
-  TS_ACT(act,
-         hipLaunchKernelGGL(act_import_kernel<float>, row_grid(rows, t), dim3(256), 0, stream, src, (float*)dst, (long long)rows, t, pitch),
-         hipLaunchKernelGGL(act_import_kernel<bf16_t>, row_grid(rows, t), dim3(256), 0, stream, src, (bf16_t*)dst, (long long)rows, t, pitch));
-  return hip_status(hipGetLastError());
-}
-
-extern "C" int ts_train_act_export(const void* src, float* dst, int64_t rows, int32_t t, int32_t pitch, int32_t act, void* stream_) {
-  if (!src || !dst || rows <= 0 || t <= 0 || pitch < t || act < 0 || act > 1 || !rows_ok(src, pitch, act)) return TS_EINVAL;
-  TS_STREAM;
-  TS_ACT(act,
-         hipLaunchKernelGGL(act_export_kernel<float>, row_grid(rows, t), dim3(256), 0, stream, (const float*)src, dst, (long long)rows, t, pitch),
-         hipLaunchKernelGGL(act_export_kernel<bf16_t>, row_grid(rows, t), dim3(256), 0, stream, (const bf16_t*)src, dst, (long long)rows, t, pitch));
-  return hip_status(hipGetLastError());
-}
-
-// fp32 -> bf16 (round to nearest even): operand copies of the weights for the bf16 GEMMs
-__global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict__ x, unsigned short* __restrict__ y, long long n) {
-  const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
-  if (i + 3 < n) {
-    const float4 v = *reinterpret_cast<const float4*>(x + i);
-    *reinterpret_cast<uint2*>(y + i) = uint2{pack_bf16(v.x, v.y), pack_bf16(v.z, v.w)};
-  } else {
-    for (long long j = i; j < n; ++j) y[j] = (unsigned short)(pack_bf16(x[j], 0.f) & 0xffffu);
-  }
-}
-
-namespace ts {
-// f32-accumulating GEMM on the f32 matrix-core instruction, any operand layout (csrc/gemm_f32.hip)
-int gemm_f32(hipStream_t stream, bool in_bf16, const void* a, long long a_rs, long long a_cs, long long sa, long long ska, const void* b,
-             long long b_rs, long long b_cs, long long sb, long long skb, void* c, long long ldc, long long sc, bool out_bf16, const float* bias,
-             int M, int N, int K, int nkb, int batch, bool beta);
-}
-
-extern "C" int ts_train_cast_bf16(const float* x, void* y, int64_t n, void* stream_) {
-  if (!x || !y || n <= 0) return TS_EINVAL;
-  if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(y) % 8) return TS_EINVAL;
-  TS_STREAM;
-  hipLaunchKernelGGL(cast_bf16_kernel, dim3(blocks((n + 3) / 4)), dim3(256), 0, stream, x, static_cast<unsigned short*>(y), (long long)n);
-  return hip_status(hipGetLastError());
-}
-
-// v[b] = W . u[b]   (W [c_out][c_in] row-major, u [B][c_in][pitch_u], v [B][c_out][pitch_v]); u is expected masked by the caller.
-// precision 0: f32 operands and result; 1: u and w bf16, v f32 (the decoder's logits); 2: u, w and v bf16.  f32 accumulation always.
-extern "C" int ts_train_pwconv_fwd(const void* u, const void* w, void* v, int32_t batch, int32_t c_in, int32_t c_out, int32_t t,
-                                   int32_t pitch_u, int32_t pitch_v, int32_t precision, void* stream_) {
-  if (!u || !w || !v || batch <= 0 || c_in <= 0 || c_out <= 0 || t <= 0 || pitch_u < t || pitch_v < t) return TS_EINVAL;
-  if (precision < 0 || precision > 2) return TS_EUNSUPPORTED;
-  TS_STREAM;
-  // per clip: V[c_out][t] = W[c_out][c_in] . U[c_in][t]  (W's contraction index contiguous, U's frame index contiguous)
-  return gemm_f32(stream, precision != 0, w, c_in, 1, 0, 0, u, pitch_u, 1, (long long)c_in * pitch_u, 0, v, pitch_v, (long long)c_out * pitch_v,
-                  precision == 2, nullptr, c_out, t, c_in, 1, batch, false);
-}
-
-// du[b] = W^T . dv[b];  dW = sum_b dv[b] . u[b]^T  (workspace: batch * c_out * c_in floats, f32 always); precision as above
-// (1: dv, u, w bf16 and du f32; 2: du bf16 as well)
-extern "C" int ts_train_pwconv_bwd(const void* dv, const void* u, const void* w, void* du, float* dw, float* workspace, int32_t batch,
-                                   int32_t c_in, int32_t c_out, int32_t t, int32_t pitch_u, int32_t pitch_v, int32_t precision, void* stream_) {
-  if (!dv || !u || !w || !du || !dw || !workspace || batch <= 0 || c_in <= 0 || c_out <= 0 || t <= 0 || pitch_u < t || pitch_v < t) return TS_EINVAL;
-  if (precision < 0 || precision > 2) return TS_EUNSUPPORTED;
-  TS_STREAM;
-  const bool bf = precision != 0;
-  // per clip: dU[c_in][t] = W^T . dV[c_out][t]  (A(m, k) = W[k][m]: W's output index is the contiguous one here)
-  if (int st = gemm_f32(stream, bf, w, 1, c_in, 0, 0, dv, pitch_v, 1, (long long)c_out * pitch_v, 0, du, pitch_u, (long long)c_in * pitch_u,
-                        precision == 2, nullptr, c_in, t, c_out, 1, batch, false))
-    return st;
-  // per clip: dW_b[c_out][c_in] = dV[c_out][t] . U[c_in][t]^T (both contract over their contiguous frame index) -> workspace, summed below.
-  // One partial per clip keeps every CU busy (16 tiles x 32 clips at 512 x 512); the pitch padding beyond t never enters (K = t).
-  if (int st = gemm_f32(stream, bf, dv, pitch_v, 1, (long long)c_out * pitch_v, 0, u, 1, pitch_u, (long long)c_in * pitch_u, 0, workspace, c_in,
-                        (long long)c_in * c_out, false, nullptr, c_out, c_in, t, 1, batch, false))
-    return st;
-  const long long rows = (long long)c_in * c_out;
-  hipLaunchKernelGGL(sum_parts_kernel, dim3(blocks(rows)), dim3(256), 0, stream, workspace, dw, rows, batch);
-  return hip_status(hipGetLastError());
-}
-
-// workspace: 16 * c doubles (8 clip-group partials of 2 sums).  mean_rstd f32 [c][2] is saved for the backward.
-extern "C" int ts_train_bn_fwd(const void* v, const float* gamma, const float* beta, void* y, float* mean_rstd, void* workspace,
-                               int32_t batch, int32_t ch, int32_t t, int32_t pitch, float eps, int32_t relu, float* running_mean,
-                               float* running_var, float momentum, int64_t* num_batches_tracked, int32_t act, void* stream_) {
-  if (!v || !gamma || !beta || !y || !mean_rstd || !workspace || batch <= 0 || ch <= 0 || t <= 0 || act < 0 || act > 1) return TS_EINVAL;
-  if ((running_mean == nullptr) != (running_var == nullptr)) return TS_EINVAL;
-  if (!rows_ok(v, pitch, act) || !rows_ok(y, pitch, act) || pitch < t) return TS_EINVAL;
-  TS_STREAM;
-  double* sums = static_cast<double*>(workspace);
-  long long* nbt = reinterpret_cast<long long*>(num_batches_tracked);
-  const dim3 rg = row_grid((long long)batch * ch, t);
-  const int ng = BN_G;
-  TS_ACT(act,
-         { hipLaunchKernelGGL((chan_sums_kernel<0, float>), dim3(ch, BN_G), dim3(256), 0, stream, (const float*)v, (const float*)nullptr, (const float*)nullptr,
-                                (const float*)nullptr, sums, batch, ch, t, pitch, 0);
-           hipLaunchKernelGGL(bn_fwd_kernel<float>, rg, dim3(256), 0, stream, (const float*)v, sums, gamma, beta, (float*)y, mean_rstd, batch, ch, t, pitch,
-                              eps, relu, running_mean, running_var, momentum, nbt, ng); },
-         { hipLaunchKernelGGL((chan_sums_kernel<0, bf16_t>), dim3(ch, BN_G), dim3(256), 0, stream, (const bf16_t*)v, (const bf16_t*)nullptr, (const bf16_t*)nullptr,
-                                (const float*)nullptr, sums, batch, ch, t, pitch, 0);
-           hipLaunchKernelGGL(bn_fwd_kernel<bf16_t>, rg, dim3(256), 0, stream, (const bf16_t*)v, sums, gamma, beta, (bf16_t*)y, mean_rstd, batch, ch, t, pitch,
-                              eps, relu, running_mean, running_var, momentum, nbt, ng); });
-  return hip_status(hipGetLastError());
-}
-
-extern "C" int ts_train_bn_bwd(const void* dy, const void* y, const void* v, const float* gamma, const float* mean_rstd, void* dv,
-                               float* dgamma, float* dbeta, void* workspace, int32_t batch, int32_t ch, int32_t t, int32_t pitch, int32_t relu,
-                               int32_t act, void* stream_) {
-  if (!dy || !y || !v || !gamma || !mean_rstd || !dv || !dgamma || !dbeta || !workspace || batch <= 0 || ch <= 0 || t <= 0) return TS_EINVAL;
-  if (act < 0 || act > 1 || !rows_ok(dy, pitch, act) || !rows_ok(y, pitch, act) || !rows_ok(v, pitch, act) || !rows_ok(dv, pitch, act) || pitch < t) return TS_EINVAL;
-  TS_STREAM;
-  double* sums = static_cast<double*>(workspace);
-  const dim3 rg = row_grid((long long)batch * ch, t);
-  TS_ACT(act,
-         { hipLaunchKernelGGL((chan_sums_kernel<1, float>), dim3(ch, BN_G), dim3(256), 0, stream, (const float*)dy, (const float*)y, (const float*)v, mean_rstd, sums,
-                              batch, ch, t, pitch, relu);
-           hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, rg, dim3(256), 0, stream, (const float*)dy, (const float*)y, (const float*)v, sums, gamma, mean_rstd,
-                              (float*)dv, dgamma, dbeta, batch, ch, t, pitch, relu); },
-         { hipLaunchKernelGGL((chan_sums_kernel<1, bf16_t>), dim3(ch, BN_G), dim3(256), 0, stream, (const bf16_t*)dy, (const bf16_t*)y, (const bf16_t*)v, mean_rstd, sums,
-                              batch, ch, t, pitch, relu);
-           hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, rg, dim3(256), 0, stream, (const bf16_t*)dy, (const bf16_t*)y, (const bf16_t*)v, sums, gamma, mean_rstd,
-                              (bf16_t*)dv, dgamma, dbeta, batch, ch, t, pitch, relu); });
-  return hip_status(hipGetLastError());
-}
-
-extern "C" int ts_train_add_relu_fwd(const void* a, const void* b, void* out, int64_t rows, int32_t t, int32_t pitch, int32_t act, void* stream_) {
-  if (!a || !out || rows <= 0 || t <= 0 || pitch < t || act < 0 || act > 1) return TS_EINVAL;
-  if (!rows_ok(a, pitch, act) || !rows_ok(out, pitch, act) || (b && !rows_ok(b, pitch, act))) return TS_EINVAL;
-  TS_STREAM;
-  TS_ACT(act,
-         hipLaunchKernelGGL(add_relu_fwd_kernel<float>, row_grid(rows, t), dim3(256), 0, stream, (const float*)a, (const float*)b, (float*)out, (long long)rows, t, pitch),
-         hipLaunchKernelGGL(add_relu_fwd_kernel<bf16_t>, row_grid(rows, t), dim3(256), 0, stream, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, (long long)rows, t, pitch));
-  return hip_status(hipGetLastError());
-}
-
-extern "C" int ts_train_add(const void* a, const void* b, const int32_t* len_b, int32_t ch, void* out, int64_t rows, int32_t t, int32_t pitch,
-                            int32_t act, void* stream_) {
-  if (!a || !b || !out || rows <= 0 || t <= 0 || pitch < t || act < 0 || act > 1 || (len_b && (ch <= 0 || rows % ch))) return TS_EINVAL;
-  if (!rows_ok(a, pitch, act) || !rows_ok(out, pitch, act) || !rows_ok(b, pitch, act)) return TS_EINVAL;
-  TS_STREAM;
-  TS_ACT(act,
-         hipLaunchKernelGGL(add_fwd_kernel<float>, row_grid(rows, t), dim3(256), 0, stream, (const float*)a, (const float*)b, (float*)out, (long long)rows, t, pitch, len_b, ch),
-         hipLaunchKernelGGL(add_fwd_kernel<bf16_t>, row_grid(rows, t), dim3(256), 0, stream, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, (long long)rows, t, pitch, len_b, ch));
-  return hip_status(hipGetLastError());
-}
-
-extern "C" int ts_train_relu_bwd(const void* dout, const void* out, void* din, int64_t rows, int32_t t, int32_t pitch, int32_t act, void* stream_) {
-  if (!dout || !out || !din || rows <= 0 || t <= 0 || pitch < t || act < 0 || act > 1) return TS_EINVAL;
-  if (!rows_ok(dout, pitch, act) || !rows_ok(out, pitch, act) || !rows_ok(din, pitch, act)) return TS_EINVAL;
-  TS_STREAM;
-  TS_ACT(act,
-         hipLaunchKernelGGL(relu_bwd_kernel<float>, row_grid(rows, t), dim3(256), 0, stream, (const float*)dout, (const float*)out, (float*)din, (long long)rows, t, pitch),
-         hipLaunchKernelGGL(relu_bwd_kernel<bf16_t>, row_grid(rows, t), dim3(256), 0, stream, (const bf16_t*)dout, (const bf16_t*)out, (bf16_t*)din, (long long)rows, t, pitch));
-  return hip_status(hipGetLastError());
 }

@@ -1,4 +1,4 @@
-// Training-mode pieces of the encoder blocks beyond the QuartzNet defaults (same conventions as csrc/train_enc.hip: pitched
+// Training-mode pieces of the encoder blocks beyond the QuartzNet defaults (the conventions of csrc/train_act.hpp: pitched
 // activation rows, `act` = 0 f32 / 1 bf16 storage with f32 arithmetic):
 //   strided 1x1 MaskedConv1d (residual branch of a strided block, quartznet/blocks.py:301-311, citrinet/blocks.py:156-165):
 //     mask + subsample in one pass; the 1x1 conv itself is the pointwise GEMM that follows
@@ -6,28 +6,17 @@
 //     [B, C]-sized bottleneck (two bias-free linears, ReLU, sigmoid) and its backward are one / two small launches (se_gate_*_kernel)
 //   nn.Dropout (quartznet/blocks.py:227-228, blocks.py:238): Philox mask re-drawn in the backward pass
 #include "ts_common.hpp"
+#include "train_act.hpp"
 #include "ts_philox.hpp"
 
 namespace ts {
-
-typedef unsigned short bf16_t;
-__device__ __forceinline__ float ldf(const float* p, size_t i) { return p[i]; }
-__device__ __forceinline__ float ldf(const bf16_t* p, size_t i) { return bf16_to_f32(p[i]); }
-__device__ __forceinline__ void stf(float* p, size_t i, float v) { p[i] = v; }
-__device__ __forceinline__ void stf(bf16_t* p, size_t i, float v) { p[i] = (bf16_t)(pack_bf16(v, 0.f) & 0xffffu); }
-
-__device__ __forceinline__ int clamp_len2(const int* len, int b, int t) {
-  if (!len) return t;
-  const int l = len[b];
-  return l < 0 ? 0 : (l > t ? t : l);
-}
 
 // forward: y[row][j] = x[row][j*s] if j*s < len[b] else 0
 template <class T>
 __global__ __launch_bounds__(256) void subsample_fwd_kernel(const T* __restrict__ x, const int* __restrict__ len, T* __restrict__ y,
                                                              int ch, int t_in, int t_out, int stride, int pitch_in, int pitch_out) {
   const int row = blockIdx.x, b = row / ch;
-  const int l = clamp_len2(len, b, t_in);
+  const int l = clamp_len(len, b, t_in);
   for (int j = blockIdx.y * 1024 + threadIdx.x; j < t_out && j < (int)(blockIdx.y + 1) * 1024; j += 256) {
     const int ti = j * stride;
     stf(y, (size_t)row * pitch_out + j, ti < l ? ldf(x, (size_t)row * pitch_in + ti) : 0.f);
@@ -38,17 +27,11 @@ template <class T>
 __global__ __launch_bounds__(256) void subsample_bwd_kernel(const T* __restrict__ dy, const int* __restrict__ len, T* __restrict__ dx,
                                                              int ch, int t_in, int t_out, int stride, int pitch_in, int pitch_out) {
   const int row = blockIdx.x, b = row / ch;
-  const int l = clamp_len2(len, b, t_in);
+  const int l = clamp_len(len, b, t_in);
   for (int t = blockIdx.y * 1024 + threadIdx.x; t < t_in && t < (int)(blockIdx.y + 1) * 1024; t += 256) {
     const int j = t / stride;
     stf(dx, (size_t)row * pitch_in + t, (t % stride == 0 && t < l && j < t_out) ? ldf(dy, (size_t)row * pitch_out + j) : 0.f);
   }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 // one wave per (clip, channel) row.  MODE 0: out[row] = mean_t a[row][t];  MODE 1: out[row] = sum_t a[row][t] * b[row][t]
@@ -237,24 +220,21 @@ static inline dim3 rgrid(long long rows, int t) { return dim3((unsigned)rows, (u
 }  // namespace ts
 
 using namespace ts;
-#define TS_ACT(act, expr_f32, expr_bf16) do { if (act) { expr_bf16; } else { expr_f32; } } while (0)
 
 extern "C" int ts_train_subsample_mask(const void* x, const int32_t* len, void* y, int32_t batch, int32_t ch, int32_t t_in,
                                        int32_t t_out, int32_t stride, int32_t backward, int32_t pitch_in, int32_t pitch_out, int32_t act,
                                        void* stream_) {
   if (!x || !y || batch <= 0 || ch <= 0 || t_in <= 0 || t_out <= 0 || stride < 1 || (t_out - 1) * stride >= t_in) return TS_EINVAL;
   if (pitch_in < t_in || pitch_out < t_out || act < 0 || act > 1) return TS_EINVAL;
-  hipStream_t stream = (hipStream_t)stream_;
-  (void)hipGetLastError();
+  TS_STREAM;
   const long long rows = (long long)batch * ch;
-  if (!backward)
-    TS_ACT(act,
-           hipLaunchKernelGGL(subsample_fwd_kernel<float>, rgrid(rows, t_out), dim3(256), 0, stream, (const float*)x, len, (float*)y, ch, t_in, t_out, stride, pitch_in, pitch_out),
-           hipLaunchKernelGGL(subsample_fwd_kernel<bf16_t>, rgrid(rows, t_out), dim3(256), 0, stream, (const bf16_t*)x, len, (bf16_t*)y, ch, t_in, t_out, stride, pitch_in, pitch_out));
-  else
-    TS_ACT(act,
-           hipLaunchKernelGGL(subsample_bwd_kernel<float>, rgrid(rows, t_in), dim3(256), 0, stream, (const float*)x, len, (float*)y, ch, t_in, t_out, stride, pitch_in, pitch_out),
-           hipLaunchKernelGGL(subsample_bwd_kernel<bf16_t>, rgrid(rows, t_in), dim3(256), 0, stream, (const bf16_t*)x, len, (bf16_t*)y, ch, t_in, t_out, stride, pitch_in, pitch_out));
+  act_dispatch(act, [&](auto tag) {
+    using T = decltype(tag);
+    if (!backward)
+      hipLaunchKernelGGL(subsample_fwd_kernel<T>, rgrid(rows, t_out), dim3(256), 0, stream, as<T>(x), len, as<T>(y), ch, t_in, t_out, stride, pitch_in, pitch_out);
+    else
+      hipLaunchKernelGGL(subsample_bwd_kernel<T>, rgrid(rows, t_in), dim3(256), 0, stream, as<T>(x), len, as<T>(y), ch, t_in, t_out, stride, pitch_in, pitch_out);
+  });
   return hip_status(hipGetLastError());
 }
 
@@ -262,9 +242,10 @@ extern "C" int ts_train_se_pool(const void* x, float* mean, int64_t rows, int32_
   if (!x || !mean || rows <= 0 || t <= 0 || pitch < t || act < 0 || act > 1) return TS_EINVAL;
   (void)hipGetLastError();
   const dim3 grid((unsigned)((rows + 3) / 4));
-  TS_ACT(act,
-         hipLaunchKernelGGL((se_row_reduce_kernel<0, float>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)x, (const float*)nullptr, mean, (long long)rows, t, pitch),
-         hipLaunchKernelGGL((se_row_reduce_kernel<0, bf16_t>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)nullptr, mean, (long long)rows, t, pitch));
+  act_dispatch(act, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((se_row_reduce_kernel<0, T>), grid, dim3(256), 0, (hipStream_t)stream, as<T>(x), (const T*)nullptr, mean, (long long)rows, t, pitch);
+  });
   return hip_status(hipGetLastError());
 }
 
@@ -272,9 +253,10 @@ extern "C" int ts_train_se_rowdot(const void* a, const void* b, float* out, int6
   if (!a || !b || !out || rows <= 0 || t <= 0 || pitch < t || act < 0 || act > 1) return TS_EINVAL;
   (void)hipGetLastError();
   const dim3 grid((unsigned)((rows + 3) / 4));
-  TS_ACT(act,
-         hipLaunchKernelGGL((se_row_reduce_kernel<1, float>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)a, (const float*)b, out, (long long)rows, t, pitch),
-         hipLaunchKernelGGL((se_row_reduce_kernel<1, bf16_t>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, (const bf16_t*)b, out, (long long)rows, t, pitch));
+  act_dispatch(act, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((se_row_reduce_kernel<1, T>), grid, dim3(256), 0, (hipStream_t)stream, as<T>(a), as<T>(b), out, (long long)rows, t, pitch);
+  });
   return hip_status(hipGetLastError());
 }
 
@@ -282,9 +264,10 @@ extern "C" int ts_train_se_scale(const void* x, const float* gate, const float* 
                                  int32_t act, void* stream) {
   if (!x || !gate || !y || rows <= 0 || t <= 0 || pitch < t || act < 0 || act > 1) return TS_EINVAL;
   (void)hipGetLastError();
-  TS_ACT(act,
-         hipLaunchKernelGGL(se_scale_kernel<float>, rgrid(rows, t), dim3(256), 0, (hipStream_t)stream, (const float*)x, gate, add_mean, 1.0f / (float)t, (float*)y, t, pitch),
-         hipLaunchKernelGGL(se_scale_kernel<bf16_t>, rgrid(rows, t), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, gate, add_mean, 1.0f / (float)t, (bf16_t*)y, t, pitch));
+  act_dispatch(act, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(se_scale_kernel<T>, rgrid(rows, t), dim3(256), 0, (hipStream_t)stream, as<T>(x), gate, add_mean, 1.0f / (float)t, as<T>(y), t, pitch);
+  });
   return hip_status(hipGetLastError());
 }
 
@@ -334,10 +317,10 @@ extern "C" int ts_train_dropout(const void* x, void* y, int64_t rows, int32_t t,
   }
   const long long n_el = (long long)rows * t;
   const dim3 fgrid((unsigned)((n_el + 1023) / 1024));
-  TS_ACT(act,
-         hipLaunchKernelGGL(dropout_kernel<float>, fgrid, dim3(256), 0, (hipStream_t)stream, (const float*)x, (float*)y, n_el, t, pitch, p, scale, (unsigned long long)seed,
-                            (const unsigned long long*)nonce),
-         hipLaunchKernelGGL(dropout_kernel<bf16_t>, fgrid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, n_el, t, pitch, p, scale, (unsigned long long)seed,
-                            (const unsigned long long*)nonce));
+  act_dispatch(act, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(dropout_kernel<T>, fgrid, dim3(256), 0, (hipStream_t)stream, as<T>(x), as<T>(y), n_el, t, pitch, p, scale, (unsigned long long)seed,
+                       (const unsigned long long*)nonce);
+  });
   return hip_status(hipGetLastError());
 }

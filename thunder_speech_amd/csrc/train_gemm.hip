@@ -13,10 +13,10 @@
 // clip-sized products plus a reduction of the B partials (25-33 + 10 us per layer); here clip groups are split over workgroups
 // until every CU has a tile, so the reduction reads 8-16 partials.
 #include "ts_common.hpp"
+#include "train_act.hpp"
 
 namespace ts {
 
-typedef unsigned short bf16_t;
 constexpr int GK = 64;                 // K per step
 constexpr int GTILE = 128;             // tile edge (frames / channels)
 constexpr int AROWB = GTILE * 2;       // bytes per LDS row of an activation / transposed-weight tile

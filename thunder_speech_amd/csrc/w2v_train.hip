@@ -14,6 +14,7 @@
 //   y = a + b                                                                      ts_w2v_add
 // Activations are f32 [rows][c], contiguous (the reference's arithmetic); rows = clips x frames.
 #include "ts_common.hpp"
+#include "train_act.hpp"      // wave_sum, TS_STREAM
 #include "ts_philox.hpp"
 
 namespace ts {
@@ -29,12 +30,6 @@ __device__ __forceinline__ float erf_as(float x) {          // Abramowitz & Steg
 __device__ __forceinline__ float gelu_f(float z) { return 0.5f * z * (1.f + erf_as(z * 0.70710678118654752f)); }
 __device__ __forceinline__ float gelu_df(float z) {
   return 0.5f * (1.f + erf_as(z * 0.70710678118654752f)) + z * 0.3989422804014327f * __expf(-0.5f * z * z);
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 // LayerNorm backward, one wave per row, the row in registers (NV float4 per lane: c <= 256 NV).  s = x (+ res); xhat = (s - mean) rstd;
@@ -239,7 +234,6 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 }  // namespace ts
 
 using namespace ts;
-#define TS_STREAM hipStream_t stream = reinterpret_cast<hipStream_t>(stream_); (void)hipGetLastError()
 
 namespace ts {
 // f32 rows -> bf16 copy and / or TRANSPOSED bf16 copy, the operands of the mixed-precision fine-tuning products (huggingface/train.py LinearMixed):

@@ -1,5 +1,5 @@
 """Training-mode encoder ops (fine-tuning with the encoder unfrozen): one torch.autograd.Function per reference op, each
-forward AND backward a call into csrc/train_enc.hip / train_extra.hip.  PyTorch only chains the Functions; no ATen compute op
+forward AND backward a call into csrc/train_dw.hip / train_bn.hip / train_rows.hip / train_extra.hip.  PyTorch only chains the Functions; no ATen compute op
 touches an activation.
 
 Activation tensors are [B, C, T] views of pitched rows ([B, C, P], P = T rounded up to 192 frames, 32-byte aligned) in ONE of
@@ -1065,7 +1065,7 @@ CHAN_TAIL = True            # False: block tails keep the two-step kernels (clip
 
 
 def chan_fits(batch: int, t: int, dtype) -> bool:
-    """Whether the one-workgroup-per-channel block-tail kernels hold a channel of this batch in registers (csrc/train_enc.hip ChanRegs)."""
+    """Whether the one-workgroup-per-channel block-tail kernels hold a channel of this batch in registers (csrc/train_bn.hip ChanRegs)."""
     return CHAN_TAIL and batch * ((t + 511) // 512) <= (32 if dtype == torch.bfloat16 else 16)
 
 
