@@ -293,6 +293,81 @@ def test_decode_fixture_matches_reference(golden):
     assert np.array_equal(ids.numpy(), g["enc_ids"]) and np.array_equal(lens.numpy(), g["enc_len"])
 
 
+def _w2v_host_cases():
+    """(entry point, arguments, expected status) of calls that return before any launch.  Pointers are made-up addresses (never dereferenced on these
+    paths): A is 16-byte aligned, A + 4 / A + 8 are not; 0 is an absent optional argument."""
+    A, E, U = 0x10000, -1, -2
+    ln = lambda x=A, res=0, xb=0, w=A, b=A, rows=4, c=512, y=A, y16=0: ("ts_w2v_layernorm_fwd", (x, res, xb, w, b, 1e-5, rows, c, 0, y, y16, None))
+    lnb = lambda name, x=A, res=0, g=A, dy=A, c=512, dx=A, ws=A: (name, (x, res, g, dy, 1e-5, 4, c, dx, A, A, ws, None))
+    glu = lambda x=A, rows=4, c=8, y=A, y16=0: ("ts_w2v_glu_fwd", (x, rows, c, y, y16, None))
+    wg = lambda dz=A, x=A, c=128, k=4, groups=2, dw=A, ws=A: ("ts_w2v_posconv_wgrad", (dz, x, 1, 8, c, k, groups, dw, ws, None))
+    tr = lambda src=A, res=A, c=128, bias=A, k=4, groups=2, bwd=0, ws=A: ("ts_w2v_posconv_train", (src, res, 1, 8, c, A, bias, k, groups, bwd, A, 0, ws, None))
+    pc = lambda name, x=A, c=128, groups=2, prec=0, tail=(A, None): (name, (x, 1, 8, c, A, A, 4, groups, prec, A) + tail)
+    rot = lambda x=A, w=A, b=A, t=4, c=128, heads=2, cs=A, prec=1, y=A, yr=A: (
+        "ts_conformer_layernorm_rotary_fwd", (x, w, b, 1e-5, 1, t, c, heads, cs, 8, prec, y, yr, None))
+    gd = lambda u=A, c=64, k=31, act=2, prec=1: ("ts_conformer_glu_dwconv_fwd", (u, 1, 8, c, A, k, A, A, act, prec, A, None))
+    cl = lambda x=A, res=0, y=A, y_op=0, n=64, act=0, prec=0, bias=0, ldc=64: (
+        "ts_conformer_linear_fwd", (x, 64, A, 0, bias, res, 64, y, ldc, y_op, 64, 4, n, 64, act, prec, None))
+    cases = [
+        (("ts_w2v_conv0_workspace_bytes", (0, 16000, 512, 10, 5)), E), (("ts_w2v_conv0_workspace_bytes", (1, 9, 512, 10, 5)), E),
+        (("ts_w2v_conv0_fwd", (0, 1, 16000, A, A, A, 512, 10, 5, 1e-5, A, 0, A, None)), E),
+        (("ts_w2v_conv0_fwd", (A, 1, 16000, A, A, 0, 512, 10, 5, 1e-5, A, 0, A, None)), E),          # GroupNorm weight without its bias
+        (("ts_w2v_conv0_fwd", (A, 1, 16000, A, A, A, 512, 10, 5, 1e-5, 0, 0, A, None)), E),          # no output at all
+        (("ts_w2v_conv0_fwd", (A, 1, 16000, A, A, A, 512, 17, 5, 1e-5, A, 0, A, None)), U),          # kernel > 16
+        (("ts_w2v_conv_fwd", (A, 1, 2, 512, A, 0, 512, 3, 2, 1, 0, A, 0, 0, None)), E),              # t_in < kernel
+        (("ts_w2v_conv_fwd", (A, 1, 50, 512, A, 0, 510, 3, 2, 1, 0, A, 0, 0, None)), U),             # c_out % 4
+        (("ts_w2v_conv_fwd", (A, 1, 50, 512, A, 0, 512, 3, 2, 1, 2, A, 0, 0, None)), U),             # precision
+        (("ts_w2v_linear_fwd", (A, 63, A, 0, 0, 0, A, 64, 0, 4, 64, 64, 0, 0, 0, None)), E),         # lda < k
+        (("ts_w2v_linear_fwd", (A, 64, A, 0, 0, 0, A, 66, 0, 4, 62, 64, 0, 0, 0, None)), U),         # n % 4
+        (("ts_w2v_linear_fwd", (A, 64, A, 0, 0, 0, A, 64, 0, 4, 64, 64, 4, 0, 0, None)), U),         # act
+        (("ts_w2v_linear_fwd", (A, 64, A, 0, 0, 0, A, 64, 0, 4, 64, 64, 2, 1, 0, None)), E),         # bf16-only result without a bf16 buffer
+        (ln(x=0), E), (ln(y=0), E), (ln(rows=0), E), (ln(c=510), U), (ln(c=4100), U),
+        (ln(x=A + 4), U), (ln(res=A + 8), U), (ln(xb=A + 4), U), (ln(w=A + 8), U), (ln(b=A + 4), U), (ln(y=A + 8), U), (ln(y16=A + 4), U),
+        (ln(y=0, y16=A + 4), U),
+        (("ts_w2v_mask_rows", (A, 1, 8, 64, 0, None)), E), (("ts_w2v_mask_rows", (A, 1, 0, 64, A, None)), E),
+        (glu(x=0), E), (glu(rows=0), E), (glu(c=6), U), (glu(x=A + 4), U), (glu(y=A + 8), U), (glu(y16=A + 4), U),
+        (("ts_w2v_posconv_workspace_bytes", (1, 8, 128, 0)), E),
+        (pc("ts_w2v_posconv_fwd", x=0, tail=(0, A, None)), E), (pc("ts_w2v_posconv_fwd", c=130, groups=4, tail=(0, A, None)), E),
+        (pc("ts_w2v_posconv_fwd", prec=2, tail=(0, A, None)), U),
+        (pc("ts_w2v_groupconv_fwd", x=0), E), (pc("ts_w2v_groupconv_fwd", tail=(0, None)), E), (pc("ts_w2v_groupconv_fwd", prec=-1), U),
+        (("ts_w2v_posconv_wgrad_workspace", (1, 8, 0, 4)), E), (("ts_w2v_posconv_train_workspace", (0, 8, 128, 4)), E),
+        (wg(dz=0), E), (wg(c=130, groups=4), E), (wg(c=96, groups=2), U), (wg(ws=A + 8), U), (wg(dz=A + 4), U), (wg(x=A + 8), U),
+        (tr(src=0), E), (tr(k=1), E), (tr(bias=0), E), (tr(c=96), U), (tr(k=330), U), (tr(ws=A + 8), U), (tr(src=A + 4), U),
+        (tr(bias=0, bwd=1, ws=A + 8), U),                                                            # the data gradient takes no bias
+        (("ts_w2v_attention_workspace_bytes", (1, 0, 12, 0)), E),
+        (("ts_w2v_attention_fwd", (A, 1, 8, 770, 12, 0, 0, A, A, None)), E),                         # c % heads
+        (("ts_w2v_attention_fwd", (A, 1, 8, 768, 12, 0, 0, A, 0, None)), E),                         # no workspace
+        (("ts_w2v_attention_fwd", (A, 1, 8, 768, 12, 0, 2, A, A, None)), U),
+        (lnb("ts_w2v_layernorm_bwd", x=0), E), (lnb("ts_w2v_layernorm_bwd", c=4100), U), (lnb("ts_w2v_layernorm_bwd", x=A + 4), U),
+        (lnb("ts_w2v_layernorm_bwd", res=A + 8), U), (lnb("ts_w2v_layernorm_bwd", g=A + 4), U), (lnb("ts_w2v_layernorm_bwd", dy=A + 8), U),
+        (lnb("ts_w2v_layernorm_bwd", dx=A + 4), U), (lnb("ts_w2v_layernorm_bwd", ws=A + 8), U),
+        (lnb("ts_w2v_layernorm_bwd_set", ws=0), E), (lnb("ts_w2v_layernorm_bwd_set", res=A + 4), U), (lnb("ts_w2v_layernorm_bwd_set", dx=A + 8), U),
+        (("ts_w2v_gelu_fwd", (A + 4, 0, 0, A, 8, None)), U), (("ts_w2v_gelu_fwd", (A, A + 8, 4, A, 8, None)), U), (("ts_w2v_gelu_fwd", (A, A, 3, A, 9, None)), U),
+        (("ts_w2v_gelu_bwd", (A, 0, 0, A, A + 8, 8, None)), U), (("ts_w2v_gelu_bwd", (A, 0, 0, 0, A, 8, None)), E),
+        (("ts_w2v_add", (A, A + 4, A, 8, None)), U), (("ts_w2v_add", (A, A, 0, 8, None)), E),
+        (("ts_w2v_ffn_act_cast", (A, 0, 4, 64, 0.0, 1, A + 4, 0, 0, 0, None)), U), (("ts_w2v_ffn_act_cast", (A, A + 8, 4, 64, 0.0, 1, A, 0, 0, 0, None)), U),
+        (("ts_w2v_ffn_act_cast", (A, 0, 4, 64, 0.0, 1, 0, A + 2, 32, 32, None)), U), (("ts_w2v_ffn_act_cast", (A, 0, 4, 64, 1.0, 1, A, 0, 0, 0, None)), E),
+        (("ts_w2v_ffn_act_bwd", (A, A + 4, 64, A, 0.0, 1, A, 256, None)), U), (("ts_w2v_ffn_act_bwd", (A, 0, 64, A, 0.0, 1, A + 8, 256, None)), U),
+        (("ts_w2v_sum_parts", (A + 4, A, 8, 2, None)), E), (("ts_w2v_sum_parts_bias", (A, A + 8, 4, A, 8, 2, None)), E),
+        (("ts_w2v_pad_rows", (A, A + 4, 1, 4, 8, 2, 64, 0, None)), U), (("ts_w2v_mask_embed", (A, A, A + 4, 0, 4, 64, None)), U),
+        (gd(u=0), E), (gd(u=A + 8), U), (gd(k=30), U), (gd(act=0), U),
+        (rot(x=0), E), (rot(t=9), E), (rot(c=130), U), (rot(x=A + 4), U), (rot(w=A + 8), U), (rot(b=A + 4), U), (rot(cs=A + 8), U),
+        (rot(y=A + 4), U), (rot(yr=A + 4), U), (rot(prec=0, y=A + 8), U), (rot(prec=0, yr=A + 8), U),
+        (cl(x=0), E), (cl(act=3), U), (cl(prec=1, y=0), E), (cl(y_op=A), E), (cl(n=62, ldc=62), U), (cl(y=A + 8), U), (cl(res=A + 4), U),
+        (cl(bias=A + 8), U), (cl(res=A, y=A, act=1), U),                                             # activation into the residual stream in place
+    ]
+    return [(name, args, want) for (name, args), want in cases]
+
+
+@pytest.mark.parametrize("name,args,want", _w2v_host_cases(), ids=lambda v: v if isinstance(v, str) else None)
+def test_w2v_launchers_refuse_bad_arguments_before_any_launch(name, args, want):
+    """The argument checks of the wav2vec2 / conformer launchers: TS_EINVAL for missing or inconsistent arguments, TS_EUNSUPPORTED for shapes,
+    precisions and pointer alignments no kernel takes (an absent optional pointer is never misaligned)."""
+    from thunder_speech_amd import _lib
+    assert (_lib.TS_EINVAL, _lib.TS_EUNSUPPORTED) == (-1, -2)
+    assert getattr(_lib.lib(), name)(*args) == want
+
+
 _ASAN_DRIVER = r'''
 import ctypes as C, sys
 L = C.CDLL(sys.argv[1])

@@ -55,7 +55,7 @@ def test_contraction_loop_batches_and_epilogue(kw):
 
 
 def test_overlapping_rows_like_the_wav2vec2_conv_layers():
-    """A(m, k) = x[m * lda + k] with K > lda: the im2col matrix of a strided conv over a time-major input IS the input (w2v_enc.hip)."""
+    """A(m, k) = x[m * lda + k] with K > lda: the im2col matrix of a strided conv over a time-major input IS the input (w2v_conv.hip)."""
     from thunder_speech_amd import _lib
     c_in, kernel, stride, t_in, c_out = 64, 3, 2, 201, 96
     t_out = (t_in - kernel) // stride + 1

@@ -1,4 +1,4 @@
-"""GPU parity: wav2vec2 encoder (csrc/w2v_enc.hip through the C ABI) vs the oracle and the transformers-generated fixture.
+"""GPU parity: wav2vec2 encoder (csrc/w2v_conv.hip, w2v_rows.hip, w2v_posconv.hip and w2v_attn.hip through the C ABI) vs the oracle and the transformers-generated fixture.
 fp32 activations, fp32 GEMMs on the library's own matrix-core kernel (csrc/gemm_f32.hip): tolerances are fp32 summation-order noise."""
 from types import SimpleNamespace
 

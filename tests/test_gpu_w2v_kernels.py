@@ -1,4 +1,4 @@
-"""Every wav2vec2 encoder and fine-tuning kernel of csrc/w2v_enc.hip, csrc/w2v_train.hip and csrc/w2v_attn_train.hip through the C ABI against a plain
+"""Every wav2vec2 encoder and fine-tuning kernel of csrc/w2v_conv.hip, w2v_rows.hip, w2v_posconv.hip, w2v_attn.hip, csrc/w2v_train.hip and csrc/w2v_attn_train.hip through the C ABI against a plain
 float64 restatement on the CPU, at the shapes where the dispatch changes: the four register widths of the LayerNorms and a row that fills the last
 register slot with one lane, the strided row loop of the LayerNorm backward, the generic conv-layer-0 instantiation, odd channel counts, the scalar
 tails of the elementwise kernels, key lengths on and next to the 32- and 64-key tiles of both attention kernels.  Every output buffer starts as NaN (or

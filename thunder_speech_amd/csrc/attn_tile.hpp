@@ -1,4 +1,4 @@
-// The tile code shared by the fused (flash-style) attention kernels for head_dim 64: w2v_flash_attn_kernel (csrc/w2v_enc.hip),
+// The tile code shared by the fused (flash-style) attention kernels for head_dim 64: w2v_flash_attn_kernel (csrc/w2v_attn.hip),
 // wavlm_flash_attn_kernel (csrc/wavlm.hip), attn_fwd_train_kernel / attn_bwd_dq_kernel / attn_bwd_dkv_kernel (csrc/w2v_attn_train.hip) and
 // wt_fwd_kernel / wt_bwd_dq_kernel / wt_bwd_dkv_kernel (csrc/wavlm_train.hip).  Each kernel is a sequence of these helpers plus what is its own.
 //

@@ -6,32 +6,17 @@
 //   ts_conformer_layernorm_rotary_fwd  LN(x) and its rotary-rotated copy from one read of the row (w2v_layernorm_kernel's layout)
 //   ts_conformer_linear_fwd            the bf16 GEMM of csrc/gemm_nt.hip with its GELU / SiLU epilogue, column slices of a wider output;
 //                                      f32: the f32 GEMM and one epilogue pass
-#include "ts_common.hpp"
+#include "w2v_rows.hpp"
 #include "thunder_speech_amd_conformer.h"
 
 namespace ts {
 
-int gemm_f32(hipStream_t stream, bool in_bf16, const void* a, long long a_rs, long long a_cs, long long sa, long long ska, const void* b,
-             long long b_rs, long long b_cs, long long sb, long long skb, void* c, long long ldc, long long sc, bool out_bf16, const float* bias,
-             int M, int N, int K, int nkb, int batch, bool beta);
-int gemm_nt_bf16_act(hipStream_t stream, const void* x, long long lda, long long sx, const void* w, long long ldw, const float* bias,
-                     const float* res, long long ld_res, float* y, long long ldc, void* y16, long long ld16, long long sy, long long M, int N, int K,
-                     int act, int batch, const void* wf);
-
 namespace {
 
-// erf by Abramowitz & Stegun 7.1.26, the form of the encoder's other GELU sites (csrc/w2v_enc.hip, csrc/gemm_nt.hip)
-__device__ __forceinline__ float erf_cf(float x) {
-  const float ax = fabsf(x);
-  const float t = __frcp_rn(fmaf(0.3275911f, ax, 1.f));
-  const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f), 0.254829592f);
-  const float r = 1.f - poly * __expf(-ax * ax);
-  return copysignf(r, x);
-}
 // act 1: GELU (erf), 2: SiLU (swish), else identity
 __device__ __forceinline__ float act_cf(float x, int act) {
-  if (act == 1) return 0.5f * x * (1.f + erf_cf(x * 0.70710678118654752f));
-  if (act == 2) return x / (1.f + __expf(-x));
+  if (act == 1) return gelu_erf(x);
+  if (act == 2) return silu(x);
   return x;
 }
 __device__ __forceinline__ float glu_cf(float a, float g) { return a / (1.f + __expf(-g)); }
@@ -167,8 +152,7 @@ __global__ __launch_bounds__(256) void conformer_ln_rotary_kernel(const float* _
       s += (v[it][0] + v[it][1]) + (v[it][2] + v[it][3]);
     }
   }
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  const float mu = s / c;
+  const float mu = wave_sum(s) / c;
   float q = 0.f;
 #pragma unroll
   for (int it = 0; it < NV; ++it) {
@@ -178,8 +162,7 @@ __global__ __launch_bounds__(256) void conformer_ln_rotary_kernel(const float* _
       q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
     }
   }
-  for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-  const float rs = rsqrtf(q / c + eps);
+  const float rs = rsqrtf(wave_sum(q) / c + eps);
   const int pos = (int)(row % t);
   const f32x4 cv = *reinterpret_cast<const f32x4*>(cos_sin + (size_t)pos * 32 + 4 * (lane & 7));
   const f32x4 sv = *reinterpret_cast<const f32x4*>(cos_sin + ((size_t)t_table + pos) * 32 + 4 * (lane & 7));
@@ -227,8 +210,6 @@ __global__ __launch_bounds__(256) void conformer_bias_act_kernel(float* __restri
   *reinterpret_cast<f32x4*>(y + r * ldc + col) = v;
 }
 
-inline bool mis16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
-
 }  // namespace
 }  // namespace ts
 
@@ -239,10 +220,9 @@ extern "C" int ts_conformer_abi_version(void) { return TS_CONFORMER_ABI_VERSION;
 extern "C" int ts_conformer_glu_dwconv_fwd(const void* u, int32_t batch, int32_t t, int32_t c, const float* dw_w, int32_t kernel, const float* bn_scale,
                                            const float* bn_shift, int32_t act, int32_t precision, void* y, void* stream_) {
   if (!u || !dw_w || !bn_scale || !bn_shift || !y || batch <= 0 || t <= 0 || c <= 0) return TS_EINVAL;
-  if (kernel < 1 || kernel > 63 || !(kernel & 1) || c % 8 || mis16(u) || (act != 1 && act != 2) || precision < 0 || precision > 1 || batch > 65535)
+  if (kernel < 1 || kernel > 63 || !(kernel & 1) || c % 8 || misaligned(u) || (act != 1 && act != 2) || precision < 0 || precision > 1 || batch > 65535)
     return TS_EUNSUPPORTED;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  (void)hipGetLastError();
+  TS_STREAM;
   const dim3 grid((unsigned)((t + GD_TF - 1) / GD_TF), (unsigned)((c + GD_CW - 1) / GD_CW), (unsigned)batch);
 #define TS_GD(KT_)                                                                                                                       \
   do {                                                                                                                                   \
@@ -265,11 +245,10 @@ extern "C" int ts_conformer_layernorm_rotary_fwd(const float* x, const float* w,
                                                  void* stream_) {
   if (!x || !w || !b || !cos_sin || !y || !y_rot || batch <= 0 || t <= 0 || t > t_table) return TS_EINVAL;
   if (heads <= 0 || c != 64 * heads || c > 4096 || precision < 0 || precision > 1) return TS_EUNSUPPORTED;
-  if (mis16(x) || mis16(w) || mis16(b) || mis16(cos_sin) || (reinterpret_cast<uintptr_t>(y) & 7) || (reinterpret_cast<uintptr_t>(y_rot) & 7) ||
-      (!precision && (mis16(y) || mis16(y_rot))))
+  if (misaligned(x) || misaligned(w) || misaligned(b) || misaligned(cos_sin) || misaligned(y, 7) || misaligned(y_rot, 7) ||
+      (!precision && (misaligned(y) || misaligned(y_rot))))
     return TS_EUNSUPPORTED;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  (void)hipGetLastError();
+  TS_STREAM;
   const long long rows = (long long)batch * t;
   const dim3 grid((unsigned)((rows + 3) / 4));
 #define TS_LNR(NV_)                                                                                                                             \
@@ -289,14 +268,13 @@ extern "C" int ts_conformer_linear_fwd(const void* x, int64_t lda, const void* w
                                        void* stream_) {
   if (!x || !w || rows <= 0 || n <= 0 || k <= 0 || lda < k || (y && ldc < n) || (y_op && ld_op < n) || (res && ld_res < n)) return TS_EINVAL;
   if (act < 0 || act > 2 || precision < 0 || precision > 1) return TS_EUNSUPPORTED;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  (void)hipGetLastError();
+  TS_STREAM;
   if (precision) {
     if (!y && !y_op) return TS_EINVAL;
     return gemm_nt_bf16_act(stream, x, lda, 0, w, k, bias, res, ld_res, y, ldc, y_op, ld_op, 0, rows, n, k, act, 1, w_frag);
   }
   if (!y || y_op) return TS_EINVAL;                 // f32: the f32 result is the operand of the next product
-  if (n % 4 || ldc % 4 || mis16(y) || (res && (ld_res % 4 || mis16(res))) || (bias && mis16(bias))) return TS_EUNSUPPORTED;
+  if (n % 4 || ldc % 4 || misaligned(y) || (res && (ld_res % 4 || misaligned(res))) || (bias && misaligned(bias))) return TS_EUNSUPPORTED;
   // res == y: accumulate into the residual stream in place (beta = 1 inside the GEMM); the activation comes before the residual, so an
   // activated product needs a result buffer of its own
   const bool inplace = res && static_cast<const void*>(res) == static_cast<const void*>(y) && ld_res == ldc;
@@ -304,7 +282,7 @@ extern "C" int ts_conformer_linear_fwd(const void* x, int64_t lda, const void* w
   if (int st = gemm_f32(stream, false, x, lda, 1, 0, 0, w, 1, k, 0, 0, y, ldc, 0, false, nullptr, (int)rows, n, k, 1, 1, inplace)) return st;
   const float* res_e = inplace ? nullptr : res;
   if (bias || res_e || act)
-    hipLaunchKernelGGL(conformer_bias_act_kernel, dim3((unsigned)((rows * (n / 4) + 255) / 256)), dim3(256), 0, stream, y, (long long)ldc, bias, res_e,
+    hipLaunchKernelGGL(conformer_bias_act_kernel, dim3(nblk(rows * (n / 4))), dim3(256), 0, stream, y, (long long)ldc, bias, res_e,
                        (long long)ld_res, (long long)rows, n, act);
   return hip_status(hipGetLastError());
 }

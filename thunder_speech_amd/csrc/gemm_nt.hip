@@ -20,7 +20,7 @@
 //    or bf16 result; rows beyond M are clamped on the way in and
 //    masked on the way out; N % 32 == 0 and K % 32 == 0 (every linear of the supported checkpoints).
 //  * workgroup -> tile map keeps the column tiles of one row panel on one XCD (they share the A rows in that XCD's L2).
-#include "ts_common.hpp"
+#include "w2v_rows.hpp"      // gelu_erf, silu; the prototypes of gemm_nt_bf16 / gemm_nt_bf16_act are csrc/ts_common.hpp's
 
 #include <cstdlib>
 
@@ -56,18 +56,6 @@ __device__ __forceinline__ void vmw() {
   __builtin_amdgcn_s_waitcnt(0x0F70 | (N & 15) | ((N >> 4) << 14));
   asm volatile("" ::: "memory");
 }
-
-// erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7, below f32 GELU noise; a third of the instructions of ocml's erff) -- the same
-// form as the other GELU sites of the encoder (csrc/w2v_enc.hip)
-__device__ __forceinline__ float erf_as_g(float x) {
-  const float ax = fabsf(x);
-  const float t = __frcp_rn(fmaf(0.3275911f, ax, 1.f));
-  const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f), 0.254829592f);
-  const float r = 1.f - poly * __expf(-ax * ax);
-  return copysignf(r, x);
-}
-__device__ __forceinline__ float gelu_g(float x) { return 0.5f * x * (1.f + erf_as_g(x * 0.70710678118654752f)); }
-__device__ __forceinline__ float silu_g(float x) { return x / (1.f + __expf(-x)); }
 
 }  // namespace
 
@@ -302,8 +290,8 @@ __global__ __launch_bounds__(256 * WMR) __attribute__((amdgpu_waves_per_eu(2, 2)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float v = acc[i][j][r] + bv;
-          if (a.act & 1) v = gelu_g(v);
-          if constexpr (SILU) v = silu_g(v);
+          if (a.act & 1) v = gelu_erf(v);
+          if constexpr (SILU) v = silu(v);
           *reinterpret_cast<unsigned short*>(ep16 + (16 * i + 4 * fc + r) * EP16 + (16 * j + fr) * 2) = (unsigned short)pack_bf16(v, 0.f);
         }
     }
@@ -335,8 +323,8 @@ __global__ __launch_bounds__(256 * WMR) __attribute__((amdgpu_waves_per_eu(2, 2)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float v = acc[i][2 * j + jj][r] + bv[jj];
-          if (a.act & 1) v = gelu_g(v);
-          if constexpr (SILU) v = silu_g(v);
+          if (a.act & 1) v = gelu_erf(v);
+          if constexpr (SILU) v = silu(v);
           ep[(16 * i + 4 * fc + r) * 32 + 16 * jj + fr] = v;
         }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                    // wave-private tile: LDS operations of one wave are in order

@@ -4,7 +4,7 @@
 // f32 arithmetic inside every kernel (mixed precision: half the activation traffic, bf16 MFMA GEMMs; parameters, gradients of parameters,
 // statistics stay f32).
 #pragma once
-#include "ts_common.hpp"
+#include "ts_common.hpp"      // wave_sum, TS_STREAM
 
 namespace ts {
 
@@ -58,14 +58,6 @@ __device__ __forceinline__ void store8(bf16_t* p, const float (&v)[8]) {
   st16(reinterpret_cast<u32x4*>(p), u32x4{pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]), pack_bf16(v[6], v[7])});
 }
 
-// the sum over the 64 lanes of a wave, in every lane; V = float, or double (chan_reduce of csrc/train_bn.hip)
-template <class V>
-__device__ __forceinline__ V wave_sum(V v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // ----------------------------------------------------------------------------------------------------------------------
 // Row-wise streaming kernels: one WAVE = one (row, 512-frame chunk) unit, 64 lanes x 8 elements (16 / 32 bytes per lane), four
 // units per 256-thread workgroup (a 10 s clip is 501 frames: with one workgroup per row three of its four waves had nothing to do).
@@ -116,5 +108,3 @@ template <class T> static inline const T* as(const void* p) { return static_cast
 template <class T> static inline T* as(void* p) { return static_cast<T*>(p); }
 
 }  // namespace ts
-
-#define TS_STREAM hipStream_t stream = reinterpret_cast<hipStream_t>(stream_); (void)hipGetLastError()

@@ -141,13 +141,6 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict_
   }
 }
 
-namespace ts {
-// f32-accumulating GEMM on the f32 matrix-core instruction, any operand layout (csrc/gemm_f32.hip)
-int gemm_f32(hipStream_t stream, bool in_bf16, const void* a, long long a_rs, long long a_cs, long long sa, long long ska, const void* b,
-             long long b_rs, long long b_cs, long long sb, long long skb, void* c, long long ldc, long long sc, bool out_bf16, const float* bias,
-             int M, int N, int K, int nkb, int batch, bool beta);
-}
-
 extern "C" int ts_train_cast_bf16(const float* x, void* y, int64_t n, void* stream_) {
   if (!x || !y || n <= 0) return TS_EINVAL;
   if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(y) % 8) return TS_EINVAL;

@@ -66,9 +66,50 @@ __device__ __forceinline__ void lds_dma16(i32x4 rsrc, const void* lds_dst, int v
                :: "s"(addr), "v"(voff), "s"(rsrc), "s"(soff), "v"(after) : "memory");
 }
 
+// the sum / maximum over the 64 lanes of a wave, in every lane; V = float, or double (chan_reduce of csrc/train_bn.hip)
+template <class V>
+__device__ __forceinline__ V wave_sum(V v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+
 __host__ __device__ constexpr int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 inline int hip_status(hipError_t e) { return e == hipSuccess ? TS_OK : (int)e; }
+
+// ---- host side of the launchers ----
+// first statements of a launcher taking `void* stream_`: the stream, and a clean error state for the hip_status(hipGetLastError()) it ends with
+#define TS_STREAM hipStream_t stream = reinterpret_cast<hipStream_t>(stream_); (void)hipGetLastError()
+
+static inline unsigned nblk(long long n) { return (unsigned)((n + 255) / 256); }       // 256-thread workgroups for n threads
+// p is set and not aligned to mask + 1 bytes (a null pointer is an absent optional argument: aligned)
+static inline bool misaligned(const void* p, uintptr_t mask = 15) { return p && (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+
+// The library's own GEMMs, called by the launchers of the other files.
+// csrc/gemm_f32.hip: f32-accumulating GEMM on the f32 matrix-core instruction, any operand layout -- the f32 mode and the shapes without a kernel
+// of their own
+int gemm_f32(hipStream_t stream, bool in_bf16, const void* a, long long a_rs, long long a_cs, long long sa, long long ska, const void* b,
+             long long b_rs, long long b_cs, long long sb, long long skb, void* c, long long ldc, long long sc, bool out_bf16, const float* bias,
+             int M, int N, int K, int nkb, int batch, bool beta);
+// csrc/gemm_nt.hip: token-major bf16 GEMM with the fused epilogue (bias, GELU, residual; _act: act 1 = GELU, 2 = SiLU)
+int gemm_nt_bf16(hipStream_t stream, const void* x, long long lda, long long sx, const void* w, long long ldw, const float* bias,
+                 const float* res, long long ld_res, float* y, long long ldc, void* y16, long long ld16, long long sy, long long M, int N, int K,
+                 int gelu, int batch, const void* wf);
+int gemm_nt_bf16_act(hipStream_t stream, const void* x, long long lda, long long sx, const void* w, long long ldw, const float* bias,
+                     const float* res, long long ld_res, float* y, long long ldc, void* y16, long long ld16, long long sy, long long M, int N, int K,
+                     int act, int batch, const void* wf);
+// row-major y[M][N] (ldc) = x[M][K] (lda) W[N][K]^T (ldw) + beta y on gemm_f32, batched with element strides.  bf16 = x and W are bf16;
+// y is f32 (or bf16 when y16 is set), accumulation f32 either way.
+static inline int gemm_nt(hipStream_t stream, bool bf16, long long m, int n, int k, const void* x, long long lda, long long sx, const void* w,
+                          long long ldw, long long sw, void* y, long long ldc, long long sy, float beta, int batch, bool y16 = false) {
+  return gemm_f32(stream, bf16, x, lda, 1, sx, 0, w, 1, ldw, sw, 0, y, ldc, sy, y16, nullptr, (int)m, n, k, 1, batch, beta != 0.f);
+}
 
 // compute units of the current device (one process per GPU: looked up once)
 inline int cu_count() {

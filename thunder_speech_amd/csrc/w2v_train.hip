@@ -13,23 +13,16 @@
 //   train-time masking with the learned embedding (mask_time_prob)                  ts_w2v_mask_embed_fwd / _bwd
 //   y = a + b                                                                      ts_w2v_add
 // Activations are f32 [rows][c], contiguous (the reference's arithmetic); rows = clips x frames.
-#include "ts_common.hpp"
-#include "train_act.hpp"      // wave_sum, TS_STREAM
+#include "w2v_rows.hpp"       // erf_as_div, the row softmax
 #include "ts_philox.hpp"
 
 namespace ts {
 
 namespace {
 
-__device__ __forceinline__ float erf_as(float x) {          // Abramowitz & Stegun 7.1.26, |error| <= 1.5e-7 (the inference kernels' erf)
-  const float ax = fabsf(x);
-  const float t = 1.f / (1.f + 0.3275911f * ax);
-  const float y = 1.f - (((((1.061405429f * t - 1.453152027f) * t) + 1.421413741f) * t - 0.284496736f) * t + 0.254829592f) * t * __expf(-ax * ax);
-  return x < 0.f ? -y : y;
-}
-__device__ __forceinline__ float gelu_f(float z) { return 0.5f * z * (1.f + erf_as(z * 0.70710678118654752f)); }
+__device__ __forceinline__ float gelu_f(float z) { return 0.5f * z * (1.f + erf_as_div(z * 0.70710678118654752f)); }      // why _div: csrc/w2v_rows.hpp
 __device__ __forceinline__ float gelu_df(float z) {
-  return 0.5f * (1.f + erf_as(z * 0.70710678118654752f)) + z * 0.3989422804014327f * __expf(-0.5f * z * z);
+  return 0.5f * (1.f + erf_as_div(z * 0.70710678118654752f)) + z * 0.3989422804014327f * __expf(-0.5f * z * z);
 }
 
 // LayerNorm backward, one wave per row, the row in registers (NV float4 per lane: c <= 256 NV).  s = x (+ res); xhat = (s - mean) rstd;
@@ -160,16 +153,8 @@ __global__ __launch_bounds__(256) void softmax_fwd_kernel(float* __restrict__ s,
   const int b = blockIdx.y;
   if (row >= (long long)heads * t) return;
   float* p = s + ((long long)b * heads * t + row) * pitch;
-  const int nk = key_len ? min(key_len[b], t) : t;
-  float mx = -3.0e38f;
-  for (int j = lane; j < nk; j += 64) mx = fmaxf(mx, p[j] * scale);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-  float sum = 0.f;
-  for (int j = lane; j < nk; j += 64) sum += __expf(p[j] * scale - mx);
-  sum = wave_sum(sum);
-  const float inv = 1.f / sum;
-  for (int j = lane; j < pitch; j += 64) p[j] = j < nk ? __expf(p[j] * scale - mx) * inv : 0.f;
+  const int nk = key_len ? min(key_len[b], t) : t;          // as it is: a clip without a valid key gets probability 0 everywhere
+  softmax_row_finish(p, nk, pitch, scale, softmax_row_max(p, nk, scale, lane), lane, [p](int j, float v) { p[j] = v; });
 }
 
 // ds = scale p (dp - sum_k dp_k p_k), in place over dp; one wave per row
@@ -227,8 +212,7 @@ __global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ a, c
   else for (long long k = i; k < n; ++k) y[k] = a[k] + b[k];
 }
 
-inline unsigned blk4(long long n) { return (unsigned)(((n + 3) / 4 + 255) / 256); }
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline unsigned blk4(long long n) { return nblk((n + 3) / 4); }
 
 }  // namespace
 }  // namespace ts
@@ -286,19 +270,18 @@ __global__ __launch_bounds__(256) void w2v_sum_parts_kernel(const float* __restr
 
 /* out[r][j] = sum_p parts[p][r][j] + bias[j]  (rows of c floats, c % 4 == 0): the split-K form of a linear layer's forward product */
 extern "C" int ts_w2v_sum_parts_bias(const float* parts, const float* bias, int32_t c, float* out, int64_t n, int32_t n_parts, void* stream_) {
-  if (!parts || !bias || !out || n <= 0 || c <= 0 || c % 4 || n % c || n_parts < 1 || (reinterpret_cast<uintptr_t>(parts) & 15) || (reinterpret_cast<uintptr_t>(out) & 15) ||
-      (reinterpret_cast<uintptr_t>(bias) & 15))
+  if (!parts || !bias || !out || n <= 0 || c <= 0 || c % 4 || n % c || n_parts < 1 || misaligned(parts) || misaligned(out) || misaligned(bias))
     return TS_EINVAL;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(ts::w2v_sum_parts_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream_), parts, out, (long long)(n / 4), (int)n_parts,
+  TS_STREAM;
+  hipLaunchKernelGGL(ts::w2v_sum_parts_kernel, dim3(nblk(n / 4)), dim3(256), 0, stream, parts, out, (long long)(n / 4), (int)n_parts,
                      (long long)(n / 4), bias, (int)(c / 4));
   return ts::hip_status(hipGetLastError());
 }
 
 extern "C" int ts_w2v_sum_parts(const float* parts, float* out, int64_t n, int32_t n_parts, void* stream_) {
-  if (!parts || !out || n <= 0 || n % 4 || n_parts < 1 || (reinterpret_cast<uintptr_t>(parts) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) return TS_EINVAL;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(ts::w2v_sum_parts_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream_), parts, out, (long long)(n / 4), (int)n_parts,
+  if (!parts || !out || n <= 0 || n % 4 || n_parts < 1 || misaligned(parts) || misaligned(out)) return TS_EINVAL;
+  TS_STREAM;
+  hipLaunchKernelGGL(ts::w2v_sum_parts_kernel, dim3(nblk(n / 4)), dim3(256), 0, stream, parts, out, (long long)(n / 4), (int)n_parts,
                      (long long)(n / 4), (const float*)nullptr, 1);
   return ts::hip_status(hipGetLastError());
 }
@@ -372,7 +355,7 @@ extern "C" int ts_w2v_ffn_act_cast(const float* z, const float* bias, int64_t ro
                                    void* stream_) {
   if (!z || (!y && !yt) || rows <= 0 || c <= 0 || rows >= (1ll << 31) || !(p_drop >= 0.f && p_drop < 1.f)) return TS_EINVAL;
   if (yt && (rows_pad < rows || ldt < rows_pad || rows_pad >= (1ll << 31))) return TS_EINVAL;
-  if (c % 4 || !al16(z) || (bias && !al16(bias)) || (y && (reinterpret_cast<uintptr_t>(y) & 7)) || (yt && (ldt % 2 || (reinterpret_cast<uintptr_t>(yt) & 3)))) return TS_EUNSUPPORTED;
+  if (c % 4 || misaligned(z) || misaligned(bias) || misaligned(y, 7) || (yt && (ldt % 2 || misaligned(yt, 3)))) return TS_EUNSUPPORTED;
   TS_STREAM;
   const long long rp = yt ? rows_pad : rows;
   hipLaunchKernelGGL(ts::ffn_act_cast_kernel, dim3((unsigned)((c + 63) / 64), (unsigned)((rp + 63) / 64)), dim3(256), 0, stream, z, bias, (int)rows, (int)c, p_drop,
@@ -383,9 +366,9 @@ extern "C" int ts_w2v_ffn_act_cast(const float* z, const float* bias, int64_t ro
 /* dz = dropout_backward(da) * gelu'(z + bias), n = rows * c elements; see include/thunder_speech_amd.h */
 extern "C" int ts_w2v_ffn_act_bwd(const float* z, const float* bias, int32_t c, const float* da, float p_drop, uint64_t seed, float* dz, int64_t n, void* stream_) {
   if (!z || !da || !dz || n <= 0 || c <= 0 || n % c || !(p_drop >= 0.f && p_drop < 1.f)) return TS_EINVAL;
-  if (c % 4 || !al16(z) || !al16(da) || !al16(dz) || (bias && !al16(bias))) return TS_EUNSUPPORTED;
+  if (c % 4 || misaligned(z) || misaligned(da) || misaligned(dz) || misaligned(bias)) return TS_EUNSUPPORTED;
   TS_STREAM;
-  hipLaunchKernelGGL(ts::ffn_act_bwd_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, stream, z, bias, c, da, p_drop, 1.f / (1.f - p_drop), (unsigned long long)seed, dz,
+  hipLaunchKernelGGL(ts::ffn_act_bwd_kernel, dim3(nblk(n / 4)), dim3(256), 0, stream, z, bias, c, da, p_drop, 1.f / (1.f - p_drop), (unsigned long long)seed, dz,
                      (long long)(n / 4));
   return ts::hip_status(hipGetLastError());
 }
@@ -446,11 +429,10 @@ extern "C" int ts_w2v_cast_bf16_t_colsum(const float* x, int64_t ldx, int64_t ro
   if (!x || (!y && !yt) || rows <= 0 || c <= 0 || ldx < c || rows >= (1ll << 31)) return TS_EINVAL;
   if (y && ldy < c) return TS_EINVAL;
   if (yt && (rows_pad < rows || ldt < rows_pad || rows_pad >= (1ll << 31))) return TS_EINVAL;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  TS_STREAM;
   const long long rp = yt ? rows_pad : rows;
-  (void)hipGetLastError();
-  const bool vec = c % 4 == 0 && ldx % 4 == 0 && al16(x) && (!y || (ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 7) == 0)) &&
-                   (!yt || (ldt % 2 == 0 && (reinterpret_cast<uintptr_t>(yt) & 3) == 0));
+  const bool vec = c % 4 == 0 && ldx % 4 == 0 && !misaligned(x) && (!y || (ldy % 4 == 0 && !misaligned(y, 7))) &&
+                   (!yt || (ldt % 2 == 0 && !misaligned(yt, 3)));
   if (vec)
     hipLaunchKernelGGL(ts::cast_bf16_t4_kernel, dim3((unsigned)((c + 63) / 64), (unsigned)((rp + 63) / 64)), dim3(256), 0, stream, x, (long long)ldx, (int)rows, (int)c,
                        static_cast<unsigned short*>(y), (long long)ldy, static_cast<unsigned short*>(yt), (long long)ldt, (int)rows_pad, colsum);
@@ -475,7 +457,7 @@ extern "C" int64_t ts_w2v_layernorm_bwd_workspace(int64_t rows, int32_t c) {
 extern "C" int ts_w2v_layernorm_bwd(const float* x, const float* res, const float* gamma, const float* dy, float eps, int64_t rows, int32_t c, float* dx,
                                     float* dgamma, float* dbeta, void* workspace, void* stream_) {
   if (!x || !gamma || !dy || !dx || !dgamma || !dbeta || !workspace || rows <= 0 || c <= 0) return TS_EINVAL;
-  if (c % 4 || c > 4096 || !al16(x) || !al16(dy) || !al16(dx) || !al16(gamma) || (res && !al16(res)) || !al16(workspace)) return TS_EUNSUPPORTED;
+  if (c % 4 || c > 4096 || misaligned(x) || misaligned(dy) || misaligned(dx) || misaligned(gamma) || misaligned(res) || misaligned(workspace)) return TS_EUNSUPPORTED;
   TS_STREAM;
   const long long waves = (rows < 4096 ? (rows + 3) / 4 * 4 : 4096);
   float* part = static_cast<float*>(workspace);
@@ -511,7 +493,7 @@ __global__ __launch_bounds__(256) void ln_bwd_reduce_kernel(const float* __restr
 extern "C" int ts_w2v_layernorm_bwd_set(const float* x, const float* res, const float* gamma, const float* dy, float eps, int64_t rows, int32_t c, float* dx,
                                         float* dgamma, float* dbeta, void* workspace, void* stream_) {
   if (!x || !gamma || !dy || !dx || !dgamma || !dbeta || !workspace || rows <= 0 || c <= 0) return TS_EINVAL;
-  if (c % 4 || c > 4096 || !al16(x) || !al16(dy) || !al16(dx) || !al16(gamma) || (res && !al16(res)) || !al16(workspace)) return TS_EUNSUPPORTED;
+  if (c % 4 || c > 4096 || misaligned(x) || misaligned(dy) || misaligned(dx) || misaligned(gamma) || misaligned(res) || misaligned(workspace)) return TS_EUNSUPPORTED;
   TS_STREAM;
   const long long waves = (rows < 4096 ? (rows + 3) / 4 * 4 : 4096);
   float* part = static_cast<float*>(workspace);
@@ -535,7 +517,7 @@ extern "C" int ts_w2v_colsum(const float* x, int64_t rows, int32_t c, int64_t ld
 /* y = gelu(z + bias[col]) over [rows][c] (n = rows * c elements); bias may be NULL */
 extern "C" int ts_w2v_gelu_fwd(const float* z, const float* bias, int32_t c, float* y, int64_t n, void* stream_) {
   if (!z || !y || n <= 0 || (bias && (c <= 0 || n % c))) return TS_EINVAL;
-  if (!al16(z) || !al16(y) || (bias && (c % 4 || !al16(bias)))) return TS_EUNSUPPORTED;
+  if (misaligned(z) || misaligned(y) || (bias && (c % 4 || misaligned(bias)))) return TS_EUNSUPPORTED;
   TS_STREAM;
   hipLaunchKernelGGL(gelu_kernel, dim3(blk4(n)), dim3(256), 0, stream, z, bias, c, (const float*)nullptr, y, (long long)n);
   return hip_status(hipGetLastError());
@@ -543,7 +525,7 @@ extern "C" int ts_w2v_gelu_fwd(const float* z, const float* bias, int32_t c, flo
 
 extern "C" int ts_w2v_gelu_bwd(const float* z, const float* bias, int32_t c, const float* dy, float* dz, int64_t n, void* stream_) {
   if (!z || !dy || !dz || n <= 0 || (bias && (c <= 0 || n % c))) return TS_EINVAL;
-  if (!al16(z) || !al16(dy) || !al16(dz) || (bias && (c % 4 || !al16(bias)))) return TS_EUNSUPPORTED;
+  if (misaligned(z) || misaligned(dy) || misaligned(dz) || (bias && (c % 4 || misaligned(bias)))) return TS_EUNSUPPORTED;
   TS_STREAM;
   hipLaunchKernelGGL(gelu_kernel, dim3(blk4(n)), dim3(256), 0, stream, z, bias, c, dy, dz, (long long)n);
   return hip_status(hipGetLastError());
@@ -569,7 +551,7 @@ extern "C" int ts_w2v_softmax_bwd(const float* p, float* dp, int64_t rows, int32
 extern "C" int ts_w2v_pad_rows(const float* src, float* dst, int32_t batch, int32_t t, int32_t t_dst, int32_t left, int32_t c, int32_t extract,
                                void* stream_) {
   if (!src || !dst || batch <= 0 || t <= 0 || t_dst < t + left || left < 0 || c <= 0) return TS_EINVAL;
-  if (c % 4 || !al16(src) || !al16(dst)) return TS_EUNSUPPORTED;
+  if (c % 4 || misaligned(src) || misaligned(dst)) return TS_EUNSUPPORTED;
   TS_STREAM;
   const long long n = (long long)(extract ? t : t_dst) * c;
   hipLaunchKernelGGL(pad_rows_kernel, dim3(blk4(n), batch), dim3(256), 0, stream, src, dst, t, t_dst, left, c, extract);
@@ -579,7 +561,7 @@ extern "C" int ts_w2v_pad_rows(const float* src, float* dst, int32_t batch, int3
 /* forward (dembed NULL): x[r][:] = embed for every row with mask[r] != 0.  backward (embed NULL): x is dy: dembed += its masked rows, which become 0 */
 extern "C" int ts_w2v_mask_embed(float* x, const uint8_t* mask, const float* embed, float* dembed, int64_t rows, int32_t c, void* stream_) {
   if (!x || !mask || (!embed == !dembed) || rows <= 0 || c <= 0) return TS_EINVAL;
-  if (c % 4 || !al16(x) || (embed && !al16(embed))) return TS_EUNSUPPORTED;
+  if (c % 4 || misaligned(x) || misaligned(embed)) return TS_EUNSUPPORTED;
   TS_STREAM;
   hipLaunchKernelGGL(mask_embed_kernel, dim3(blk4((long long)rows * c)), dim3(256), 0, stream, x, mask, embed, dembed, (long long)rows, c);
   return hip_status(hipGetLastError());
@@ -587,7 +569,7 @@ extern "C" int ts_w2v_mask_embed(float* x, const uint8_t* mask, const float* emb
 
 extern "C" int ts_w2v_add(const float* a, const float* b, float* y, int64_t n, void* stream_) {
   if (!a || !b || !y || n <= 0) return TS_EINVAL;
-  if (!al16(a) || !al16(b) || !al16(y)) return TS_EUNSUPPORTED;
+  if (misaligned(a) || misaligned(b) || misaligned(y)) return TS_EUNSUPPORTED;
   TS_STREAM;
   hipLaunchKernelGGL(add_kernel, dim3(blk4(n)), dim3(256), 0, stream, a, b, y, (long long)n);
   return hip_status(hipGetLastError());

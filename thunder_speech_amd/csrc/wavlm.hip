@@ -1,6 +1,6 @@
 // WavLM's gated relative-position attention (transformers modeling_wavlm.py WavLMAttention.forward / compute_bias /
 // _relative_positions_bucket, reached from huggingface/compatibility.py:31-42 for a WavLM checkpoint).  Declared in
-// include/thunder_speech_amd_wavlm.h; everything around the attention core is the wav2vec2 sequence of csrc/w2v_enc.hip.
+// include/thunder_speech_amd_wavlm.h; everything around the attention core is the wav2vec2 sequence of csrc/w2v_attn.hip.
 //
 //   ts_wavlm_rel_bias        rb[h][d + t - 1] = E[bucket(d)][h] for d in [-(t - 1), t - 1]: the [H][2t - 1] diagonals of the
 //                            position bias, never the [T][T] matrix; the bucket table is built on the host (float32 log there)
@@ -10,13 +10,10 @@
 //                            tile staged in LDS next to K / V; the [T][T] scores are never stored
 //     precision 0:          scores from the f32 GEMM, one row kernel (gate, bias, mask, softmax), P V on the f32 GEMM
 #include "attn_tile.hpp"
+#include "w2v_rows.hpp"
 #include "thunder_speech_amd_wavlm.h"
 
 namespace ts {
-
-int gemm_f32(hipStream_t stream, bool in_bf16, const void* a, long long a_rs, long long a_cs, long long sa, long long ska, const void* b,
-             long long b_rs, long long b_cs, long long sb, long long skb, void* c, long long ldc, long long sc, bool out_bf16, const float* bias,
-             int M, int N, int K, int nkb, int batch, bool beta);
 
 // ---------------------------------------------------------------------------------------------------------------------
 // position bias diagonals: one thread per (head, d)
@@ -61,13 +58,13 @@ __global__ __launch_bounds__(256) void wavlm_softmax_kernel(const WlRowArgs a) {
   }
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
-    for (int o = 32; o > 0; o >>= 1) p[r] += __shfl_xor(p[r], o);
+    for (int o = 32; o > 0; o >>= 1) p[r] += __shfl_xor(p[r], o);      // written out: wave_sum here changes how the eight reductions interleave
     p[r] += a.bg[r];
   }
   const float gate = wavlm_gate(p, a.cst[h]);
   const float* bias = a.rb + (size_t)h * (2 * a.t - 1) + (a.t - 1 - i);     // bias[j] = rb[h][j - i + t - 1]
   float* s = a.s + ((size_t)b * a.heads * a.t + row) * a.t;
-  const int n = a.key_len ? (a.key_len[b] < a.t ? (a.key_len[b] < 0 ? 0 : a.key_len[b]) : a.t) : a.t;
+  const int n = a.key_len ? key_limit(a.key_len, b, a.t) : a.t;
   const int lim = n > 0 ? n : a.t;                    // no valid key: the softmax runs over all keys (as ts_w2v_attention_fwd)
   float m = -3.0e38f;
   for (int j = lane; j < lim; j += 64) {
@@ -75,12 +72,7 @@ __global__ __launch_bounds__(256) void wavlm_softmax_kernel(const WlRowArgs a) {
     s[j] = v;
     m = fmaxf(m, v);
   }
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  float z = 0.f;
-  for (int j = lane; j < lim; j += 64) z += __expf(s[j] - m);
-  for (int o = 32; o > 0; o >>= 1) z += __shfl_xor(z, o);
-  const float rz = 1.f / z;
-  for (int j = lane; j < a.t; j += 64) s[j] = j < lim ? __expf(s[j] - m) * rz : 0.f;
+  softmax_row_finish(s, lim, a.t, 1.f, wave_max(m), lane, [s](int j, float v) { s[j] = v; });      // the logits are formed: scale 1
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -185,9 +177,8 @@ extern "C" int ts_wavlm_abi_version(void) { return TS_WAVLM_ABI_VERSION; }
 extern "C" int ts_wavlm_rel_bias(const float* embed, const int32_t* abs_bucket, int32_t num_buckets, int32_t max_distance, int32_t heads,
                                  int32_t t, float* rel_bias, void* stream_) {
   if (!embed || !abs_bucket || !rel_bias || num_buckets < 2 || max_distance < 0 || heads <= 0 || t <= 0) return TS_EINVAL;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(wavlm_rel_bias_kernel, dim3((unsigned)((2LL * t - 1 + 255) / 256), heads), dim3(256), 0, stream, embed, abs_bucket,
+  TS_STREAM;
+  hipLaunchKernelGGL(wavlm_rel_bias_kernel, dim3(nblk(2LL * t - 1), heads), dim3(256), 0, stream, embed, abs_bucket,
                      num_buckets, max_distance, heads, t, rel_bias);
   return hip_status(hipGetLastError());
 }
@@ -205,13 +196,10 @@ extern "C" int ts_wavlm_attention_fwd(const void* qkv, int32_t batch, int32_t t,
       ld_gate_x < c)
     return TS_EINVAL;
   if (precision < 0 || precision > 1) return TS_EUNSUPPORTED;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  (void)hipGetLastError();
+  TS_STREAM;
   const int hd = c / heads;
   if (precision) {
-    if (hd != 64 || ld_gate_x % 8 || (reinterpret_cast<uintptr_t>(gate_x) & 15) || (reinterpret_cast<uintptr_t>(qkv) & 15) ||
-        (reinterpret_cast<uintptr_t>(gate_w) & 7))
-      return TS_EUNSUPPORTED;
+    if (hd != 64 || ld_gate_x % 8 || misaligned(gate_x) || misaligned(qkv) || misaligned(gate_w, 7)) return TS_EUNSUPPORTED;
     WaArgs w{};
     w.qkv = static_cast<const unsigned short*>(qkv); w.ctx = static_cast<unsigned short*>(ctx); w.key_len = key_len;
     w.gx = static_cast<const unsigned short*>(gate_x); w.ld = ld_gate_x;

@@ -1,4 +1,4 @@
-"""wav2vec2-conformer encoder (rotary position embeddings) on the HIP kernels of csrc/conformer.hip and csrc/w2v_enc.hip.
+"""wav2vec2-conformer encoder (rotary position embeddings) on the HIP kernels of csrc/conformer.hip and the wav2vec2 files (csrc/w2v_conv.hip, w2v_rows.hip, w2v_posconv.hip, w2v_attn.hip).
 
 transformers modeling_wav2vec2_conformer.py, reached from the reference's `_HuggingFaceEncoderAdapt.forward` (huggingface/compatibility.py:31-42)
 for a wav2vec2-conformer checkpoint.  The feature extractor, the feature projection and the adapter are wav2vec2's (`Wav2Vec2Plan`); the encoder

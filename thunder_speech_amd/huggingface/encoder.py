@@ -1,4 +1,4 @@
-"""wav2vec2 encoder on the HIP kernels of csrc/w2v_enc.hip.
+"""wav2vec2 encoder on the HIP kernels of csrc/w2v_conv.hip, w2v_rows.hip, w2v_posconv.hip and w2v_attn.hip.
 
 The reference hands the whole encoder to transformers (`_HuggingFaceEncoderAdapt.forward`,
 src/thunder/huggingface/compatibility.py:31-42: `self.original_encoder(audio, attention_mask=...)`, then

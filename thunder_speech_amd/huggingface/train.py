@@ -600,7 +600,7 @@ class PosConvGelu(torch.autograd.Function):
         tp = t + k
         ctx.mixed = PosConvGelu._mixed_ok(k, cg)
         if ctx.mixed:
-            # mixed precision: the conv on the inference path's matrix-core kernel (bf16 operands, f32 accumulation; csrc/w2v_enc.hip w2v_posconv_mfma_kernel),
+            # mixed precision: the conv on the inference path's matrix-core kernel (bf16 operands, f32 accumulation; csrc/w2v_posconv.hip w2v_posconv_mfma_kernel),
             # which also leaves the pre-activation z for the backward; bias + GELU + residual in its epilogue
             w16 = wk.to(torch.bfloat16)
             ws = torch.empty(L.ts_w2v_posconv_train_workspace(b, t, c, k), dtype=torch.uint8, device=x.device)
