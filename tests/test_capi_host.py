@@ -39,7 +39,7 @@ def test_library_builds_and_exports_every_declared_symbol():
 def test_library_loads_and_answers_version_queries():
     from thunder_speech_amd import _lib
     L = _lib.lib()
-    assert L.ts_abi_version() == _lib.ABI_VERSION == 11
+    assert L.ts_abi_version() == _lib.ABI_VERSION == 12
     assert L.ts_build_target() == b"gfx950"
     for t in (1, 127, 128, 129, 751, 1501, 2001):
         assert L.ts_time_pitch(t) == _lib.time_pitch(t) and _lib.time_pitch(t) % 128 == 0 and _lib.time_pitch(t) >= t
@@ -120,7 +120,7 @@ def test_derived_signatures_pin_every_type_mapping():
     from thunder_speech_amd import _lib
     S, P = _lib.SIGNATURES, ctypes.POINTER
     i32, i64, u64, f32, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_void_p
-    assert len(S) == 119 and list(S) == _lib.EXPORTED_SYMBOLS
+    assert len(S) == 118 and list(S) == _lib.EXPORTED_SYMBOLS
     assert S["ts_abi_version"] == (ctypes.c_int, [])
     assert S["ts_build_target"][0] is ctypes.c_char_p
     assert S["ts_time_pitch"] == (ctypes.c_int, [i32])                                      # int
@@ -134,7 +134,7 @@ def test_derived_signatures_pin_every_type_mapping():
     assert len(S["ts_gemm_f32"][1]) == 23 and S["ts_gemm_f32"][1][:2] == [vp, i64]
     assert S["ts_train_wgrad_reduce_multi"][1] == [vp, vp, vp, vp, i32, vp]                   # void* const*, const int64_t*
     assert S["ts_w2v_mask_embed"][1][1] is vp                                               # const uint8_t*
-    assert (_lib.ABI_VERSION, _lib.TS_EINVAL, _lib.TS_EUNSUPPORTED, _lib.GUARD_BYTES) == (11, -1, -2, 1024)
+    assert (_lib.ABI_VERSION, _lib.TS_EINVAL, _lib.TS_EUNSUPPORTED, _lib.GUARD_BYTES) == (12, -1, -2, 1024)
     assert (_lib.TCS_IN_TAILZERO, _lib.TCS_OUT_ZERO_TAIL, _lib.TCS_TAPS_PHASE) == (1, 2, 4)
 
 
@@ -368,11 +368,64 @@ def test_w2v_launchers_refuse_bad_arguments_before_any_launch(name, args, want):
     assert getattr(_lib.lib(), name)(*args) == want
 
 
+
+def _tcs_host_cases():
+    """(descriptor fields, call arguments, expected status) of ts_tcs_subblock_fwd calls that return before any launch: every field of a valid
+    layer plus the change that must be refused.  Pointers are made-up addresses, never dereferenced on these paths."""
+    A, E, U = 0x10000, -1, -2
+    IN0, OUT0, PHASE = 1, 2, 4                                                                  # TS_TCS_IN_TAILZERO, _OUT_ZERO_TAIL, _TAPS_PHASE
+    pw = dict(batch=2, c_in=64, c_out=64, t_in=100, t_out=100, pitch_in=512, pitch_out=512, kernel=1, stride=1, dilation=1, padding=0,
+              pw_w=A, bias=A)
+    dw = dict(pw, depthwise=1, kernel=5, padding=2, dw_taps=A, dw_ksteps=3)
+    res = dict(c_res=64, pitch_res=512, t_res=100, res_stride=1, res_w=A)
+    with_res = dict(x_res=A, len_res=A)
+    se = dict(pw, flags=IN0 | OUT0, se_y=A, se_gate=A)
+    phase = dict(dw, c_out=512, dilation=2, padding=4, flags=IN0 | OUT0 | PHASE)
+    cases = [
+        # TS_EINVAL: sizes, pitches, conv geometry
+        (dict(pw, batch=0), {}, E), (dict(pw, batch=-2), {}, E), (dict(pw, c_in=0), {}, E), (dict(pw, c_in=-64), {}, E),
+        (dict(pw, c_out=0), {}, E), (dict(pw, c_out=-1), {}, E), (dict(pw, t_out=0), {}, E), (dict(pw, t_out=-100), {}, E),
+        (dict(pw, pitch_out=516), {}, E), (dict(pw, pitch_out=96), {}, E),
+        (dict(pw, stride=0), {}, E), (dict(pw, dilation=0), {}, E), (dict(pw, kernel=0), {}, E),
+        # ... a residual branch without one of its arguments
+        (dict(pw, **res), dict(len_res=A), E), (dict(pw, **res), dict(x_res=A), E), (dict(pw, **dict(res, res_w=0)), with_res, E),
+        (dict(pw, **dict(res, pitch_res=516)), with_res, E),
+        # ... a depthwise stage without its taps
+        (dict(dw, dw_taps=0), {}, E), (dict(dw, dw_ksteps=0), {}, E), (dict(dw, dw_ksteps=-3), {}, E), (dict(dw, dw_ksteps=4), {}, E),
+        # TS_EUNSUPPORTED: configurations no kernel takes
+        (dict(dw, stride=3), {}, U), (dict(dw, out_fp32=1), {}, U), (dict(pw, out_fp32=1, stride=2), {}, U), (dict(pw, stride=3), {}, U),
+        # ... per-tile statistics come out of the masked, stride-1, bf16 pointwise-only launch alone
+        (dict(dw, stats=A), {}, U), (dict(pw, stats=A, out_fp32=1), {}, U), (dict(pw, stats=A, stride=2), {}, U),
+        (dict(pw, stats=A, **res), with_res, U), (dict(pw, stats=A, flags=IN0), {}, U),
+        # ... the squeeze-excite tail lives in the tail-zero, stride-1, bf16 pointwise-only launch without a residual alone
+        (dict(se, se_gate=0), {}, U), (dict(dw, flags=IN0 | OUT0, se_y=A, se_gate=A), {}, U), (dict(se, stride=2), {}, U),
+        (dict(se, out_fp32=1), {}, U), (dict(se, **res), with_res, U), (dict(se, flags=OUT0), {}, U), (dict(se, flags=IN0), {}, U),
+        (dict(se, c_in=80), {}, U), (dict(se, se_y=A + 8), {}, U),
+        # ... the phase-split taps belong to dilation-2 layers of more than 256 output channels without a residual
+        (dict(phase, dilation=1), {}, U), (dict(phase, **res), with_res, U), (dict(phase, c_out=256), {}, U),
+        # ... a depthwise layer whose staged row exceeds 320 elements
+        (dict(dw, c_out=256, kernel=229, padding=114, dw_ksteps=60), {}, U),
+    ]
+    return [pytest.param(fields, args, want, id=f"{i}-{'einval' if want == E else 'eunsupported'}") for i, (fields, args, want) in enumerate(cases)]
+
+
+@pytest.mark.parametrize("fields,args,want", _tcs_host_cases())
+def test_tcs_subblock_refuses_bad_descriptors_before_any_launch(fields, args, want):
+    """Every return of ts_tcs_subblock_fwd that precedes a launch (csrc/tcs_dispatch.hip): TS_EINVAL for missing or inconsistent arguments,
+    TS_EUNSUPPORTED for valid configurations no kernel takes."""
+    from thunder_speech_amd import _lib
+    A = 0x10000
+    assert (_lib.TS_EINVAL, _lib.TS_EUNSUPPORTED) == (-1, -2)
+    d = _lib.TcsDesc(**fields)
+    got = _lib.lib().ts_tcs_subblock_fwd(ctypes.byref(d), A, A, args.get("x_res"), args.get("len_res"), A, None)
+    assert got == want
+
+
 _ASAN_DRIVER = r'''
 import ctypes as C, sys
 L = C.CDLL(sys.argv[1])
 i32, i64, vp = C.c_int32, C.c_int64, C.c_void_p
-assert L.ts_abi_version() == 11
+assert L.ts_abi_version() == 12
 L.ts_build_target.restype = C.c_char_p
 assert L.ts_build_target() == b"gfx950"
 assert [L.ts_time_pitch(t) for t in (1, 128, 751, 1501)] == [512, 512, 1152, 1920]

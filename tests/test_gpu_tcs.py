@@ -190,3 +190,34 @@ def test_pointwise_only_tail_zero_input_keeps_reference_values_beyond_length(cin
     scale = max(1.0, float(ref.abs().max()))
     assert float((got - ref).abs().max()) <= 0.012 * scale
     assert float(got[1, :, lens[1]:].abs().max()) > 0          # relu(shift) beyond the length, as in the reference
+
+
+def test_pointwise_only_tail_zero_layer_with_a_clamped_channel_split_zeroes_its_tail():
+    """A tail-zero pointwise-only layer that also zeroes its output tail (the Citrinet residual 1x1 launches): 640 output channels are no multiple
+    of the split kernel's 512-channel workgroup tile -- two output-channel splits, the second one clamped to the last weight tiles and storing
+    128 of its 512 rows.  Values up to each length against the oracle, exactly 0 beyond it."""
+    from thunder_speech_amd import plan, tensors as TS
+    b, cin, cout, t, lens = 3, 512, 640, 333, [333, 200, 170]
+    spec = otcs.BlockSpec(cin, cout, repeat=1, kernel=1, stride=1, dilation=1, residual=False, separable=False)
+    sd = {key[2:]: v for key, v in otcs.synth_encoder_state([spec], seed=6).items()}
+    g = torch.Generator().manual_seed(6)
+    x = bf16_round(torch.randn(b, cin, t, generator=g))
+    lengths = torch.tensor(lens)
+    ref, _ = otcs.block_forward(spec, sd, "", x, lengths, emulate_bf16=True)
+    bn = [sd["mconv.1.layer.0." + n] for n in ("weight", "bias", "running_mean", "running_var")]
+    layer = plan.make_tcs_layer("cuda", dw_w=None, pw_w=sd["mconv.0.conv.weight"], bn=bn, kernel=1, stride=1, dilation=1,
+                                padding=0, relu=True)
+    li = lengths.to(torch.int32).cuda()
+    xb = TS.backing(TS.pack(x.cuda(), li, slot=("pwtz0", cin)))
+    out = TS.arena(("pwtz0o", cout), b, cout, t, "cuda")
+    out.fill_(7.0)                                     # stale data must be overwritten, zeros included
+    y, t_out = layer.run(xb, t, li, out=out, in_tail_zero=True, zero_tail=True)
+    torch.cuda.synchronize()
+    assert t_out == t
+    got = y[:, :, :t].float().cpu()
+    scale = max(1.0, float(ref.abs().max()))
+    for i, n in enumerate(lens):
+        assert float((got[i, :, :n] - ref[i, :, :n]).abs().max()) <= 0.012 * scale
+        assert float(got[i, :, :n].abs().max()) > 0
+        if n < t:
+            assert float(got[i, :, n:].abs().max()) == 0.0

@@ -1,4 +1,6 @@
-// Fused time-channel-separable sub-block for gfx950 (MI355X), inference.
+// Generic kernel of the fused time-channel-separable sub-block for gfx950 (MI355X), inference: the first design, and what runs whatever the
+// split kernel (csrc/tcs_split.hip) does not take -- masked caller tensors, the stride-2 stem, odd shapes, the fp32 decoder, the training
+// path's pointwise products with per-tile statistics.  csrc/tcs_dispatch.hip chooses between them; launch_tcs_generic below is its way in.
 //
 //   y[b, co, t] = act( sum_ci Wf[co, ci] * mask(dw[b, ci, t]) + bias[co] + sum_cr Wr[co, cr] * mask(xres[b, cr, t*rs]) )
 //   dw[b, ci, t] = sum_u taps[ci, u] * mask(x)[b, ci, t*stride + u*dil - pad]
@@ -6,13 +8,8 @@
 // Replaces the reference's per-sub-block ATen chain (quartznet/blocks.py:166-182 masked_fill + conv1d
 // (groups=C) + masked_fill + conv1d(k=1), :222 batch_norm, :332-337 residual add + relu).
 //
-// Two kernels live in this file (DESIGN.md section 3.1 has the measurements behind each step; the single-stream pipelined
-// kernel that sat between them in round 1 is gone):
-//   tcs_kernel        first design and generic fallback: 4 producer + 4 consumer waves, 64/128-frame tiles, masked
-//                     producers for caller tensors; still runs the stride-2 stem, odd shapes and the fp32 decoder.
-//   tcs_split_kernel  12 waves = 8 pointwise consumers + 4 depthwise producers, 96/192-frame tiles: the default for every
-//                     depthwise / pointwise-only layer with tail-zero tensors.
-// Common to all of them:
+// tcs_kernel: 4 producer + 4 consumer waves, 64/128-frame tiles, masked producers for caller tensors and mask-free ones (TZ) for
+// tail-zero tensors (DESIGN.md section 3.1 has the measurements behind each step).
 //  * layout NCT-p: bf16 [B][C][Tp], time contiguous.  A tile = TT output frames x CO_WG output channels of one
 //    clip; the input channels are walked in stages of 64; PERSISTENT workgroups (one per CU) stride over the tiles.
 //  * depthwise FIR on the matrix cores: v_mfma_f32_4x4x4_16b_bf16 computes 16 independent 4x4x4
@@ -28,17 +25,9 @@
 //  * a lone wave issues an instruction only every ~8 cycles on this chip, so the steady state is kept almost VALU-free.
 #include "tcs_shared.hpp"
 
-#ifndef TS_TCS_STORE_AUX
-#define TS_TCS_STORE_AUX 0       // experiment: cache policy of the generic kernel's bf16 result stores (raw buffer aux: 16 = sc1); see profiles/round6_c4_pointwise.md
-#endif
-
-
 namespace ts {
 
-constexpr int XMAX = 5;        // staged row length <= 64 * XMAX elements
-constexpr int NKMAX = 24;      // taps are cached in LDS up to this many k-steps
 constexpr int RING_BYTES = 8;   // weight-fragment prefetch depth: RING_BYTES KiB per wave in flight
-
 
 template <int TT, int NT, int STRIDE, bool DW, bool OUT_F32, bool TLDS, bool TZ, int XJ, int NPASS>
 __global__ __launch_bounds__(512, 2) void tcs_kernel(const TcsArgs a) {
@@ -532,9 +521,6 @@ __global__ __launch_bounds__(512, 2) void tcs_kernel(const TcsArgs a) {
       // 32-channel output tile so that the global stores are whole 16-B-per-lane row segments (the accumulator
       // layout gives 8 B per lane in 64 different rows per instruction, which is TA-issue-bound).
       unsigned short* const yb = reinterpret_cast<unsigned short*>(a.y);
-#if TS_TCS_STORE_AUX
-      const __amdgpu_buffer_rsrc_t ry_out = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, 0x7fffffff, 0x00020000);
-#endif
       // ReLU as a packed signed-16-bit max against `floor`: 0 clamps negative bf16 to +0, 0x8000 is a no-op
       const unsigned floor2 = a.relu ? 0u : 0x80008000u;
       // frames >= the output length are stored as 0 when the caller asks for the tail-zero invariant
@@ -612,13 +598,7 @@ __global__ __launch_bounds__(512, 2) void tcs_kernel(const TcsArgs a) {
           const int co = cob + rl;
           const int t = t0 + csub * 8;
           const u32x4 v = *reinterpret_cast<const u32x4*>(et + (size_t)rl * EP + csub * 16);
-          if (co < a.c_out && t < a.pitch_out) {
-#if TS_TCS_STORE_AUX
-            __builtin_amdgcn_raw_buffer_store_b128(v, ry_out, (int)(((size_t)(b * a.c_out + co) * a.pitch_out + t) * 2), 0, TS_TCS_STORE_AUX);
-#else
-            *reinterpret_cast<u32x4*>(yb + (size_t)(b * a.c_out + co) * a.pitch_out + t) = v;
-#endif
-          }
+          if (co < a.c_out && t < a.pitch_out) *reinterpret_cast<u32x4*>(yb + (size_t)(b * a.c_out + co) * a.pitch_out + t) = v;
         }
       }
     }
@@ -646,209 +626,30 @@ static int launch(TcsArgs& a, hipStream_t stream) {
   return hip_status(hipGetLastError());
 }
 
-}  // namespace ts
-
-extern "C" int ts_time_pitch(int T) { return ts::round_up((T < 1 ? 1 : T) + 384, 128); }
-
-/* frames per tile of the masked pointwise-only launch (depthwise = 0, kernel 1, stride 1, no TS_TCS_IN_TAILZERO) for this shape: the tile grid of
-   ts_tcs_desc.stats is batch x ceil(t_out / this) */
-extern "C" int ts_tcs_pointwise_tile_frames(int32_t batch, int32_t c_out, int32_t t_out) {
-  using namespace ts;
-  if (batch <= 0 || c_out <= 0 || t_out <= 0) return TS_EINVAL;
-  if (round_up(c_out, 32) > 256) return 64;
-  const int n_tt = (t_out + 127) / 128;
-  return (long long)batch * n_tt * ((round_up(c_out, 32) + 255) / 256) < cu_count() ? 64 : 128;
-}
-
-static int g_pw_wide = 0;          // ts_tcs_pointwise_wide: 1 = wide-frame consumers for tail-zero pointwise-only layers with c_out > 256 (measured: no gain, profiles/round6_tcs_256.txt), 0 (default) = the 96 x 512 tiles
-
-// one layer through the split kernel (csrc/tcs_split.hip)
-static int split_single(const ts::TcsArgs& w, int npass, int xe, int wm, int dil, hipStream_t stream) {
-  using namespace ts;
-  // 32-bit byte offsets inside the split kernel's buffer descriptors
-  const int64_t cmax = w.c_in > w.c_out ? w.c_in : w.c_out;
-  if ((int64_t)w.batch * cmax * (w.pitch_in > w.pitch_out ? w.pitch_in : w.pitch_out) * 2 + TS_GUARD_BYTES >= (1ll << 31)) return TS_EUNSUPPORTED;
-  if (w.c_res > 0 && (int64_t)w.batch * w.c_res * w.pitch_res * 2 >= (1ll << 31)) return TS_EUNSUPPORTED;
-  SplitArgs a{};
-  SplitLayer& L = a.layer;
-  L.x = w.x; L.xres = w.xres; L.y = static_cast<unsigned short*>(w.y);
-  if (!w.pw_w16 || (w.c_res > 0 && !w.res_w16)) return TS_EUNSUPPORTED;
-  L.taps_raw = w.taps_raw; L.pw_w = w.pw_w16; L.res_w = w.res_w16; L.bias = w.bias;
-  L.c_in = w.c_in; L.c_res = w.c_res; L.pitch_res = w.c_res > 0 ? w.pitch_res : w.pitch_in; L.relu = w.relu;
-  L.kt_main = w.kt_main; L.kt_res = w.kt_res;
-  L.se_y = w.se_y; L.se_gate = w.se_gate;
-  a.len = w.len_in;
-  a.batch = w.batch; a.c_out = w.c_out; a.pitch_in = w.pitch_in; a.pitch_out = w.pitch_out; a.t_out = w.t_out;
-  a.kernel = w.kernel; a.padding = w.padding; a.dilation = w.dilation;
-  a.woff = w.woff; a.padl8 = w.padl8; a.zero_tail = w.zero_tail;
-  return launch_split_layer(a, npass, xe, wm, dil, stream);
-}
-
-extern "C" int ts_tcs_pointwise_wide(int32_t on) {
-  const int old = g_pw_wide;
-  g_pw_wide = on ? 1 : 0;
-  return old;
-}
-
-extern "C" int ts_tcs_subblock_fwd(const ts_tcs_desc* d, const void* x, const int32_t* len_in, const void* x_res,
-                                   const int32_t* len_res, void* y, void* stream_) {
-  using namespace ts;
-  if (!d || !x || !y || !len_in || !d->pw_w || !d->bias) return TS_EINVAL;
-  if (d->batch <= 0 || d->c_in <= 0 || d->c_out <= 0 || d->t_out <= 0) return TS_EINVAL;
-  if (d->pitch_in % 8 || d->pitch_out % 8 || d->pitch_out < d->t_out) return TS_EINVAL;
-  if (d->stride < 1 || d->dilation < 1 || d->kernel < 1) return TS_EINVAL;
-  if (d->stride > 1 && d->dilation > 1) return TS_EINVAL;          // blocks.py:192-193
-  if (d->c_res > 0 && (!x_res || !len_res || !d->res_w || d->pitch_res % 8)) return TS_EINVAL;
-  if (!d->depthwise && d->kernel != 1) return TS_EUNSUPPORTED;     // dense K>1 convs are not on the hot path
-  if (d->depthwise && (!d->dw_taps || d->dw_ksteps <= 0 || d->dw_ksteps % NKP)) return TS_EINVAL;
-  if (d->depthwise && d->stride > 2) return TS_EUNSUPPORTED;
-  if (d->out_fp32 && d->depthwise) return TS_EUNSUPPORTED;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-
-  TcsArgs a{};
-  a.x = static_cast<const unsigned short*>(x);
-  a.xres = static_cast<const unsigned short*>(x_res);
-  a.y = y;
-  a.len_in = len_in;
-  a.len_res = len_res;
-  a.taps = static_cast<const unsigned short*>(d->dw_taps);
-  a.taps_raw = static_cast<const unsigned short*>(d->dw_taps_raw);
-  a.pw_w = static_cast<const unsigned short*>(d->pw_w);
-  a.res_w = static_cast<const unsigned short*>(d->res_w);
-  a.pw_w16 = static_cast<const unsigned short*>(d->pw_w16);
-  a.res_w16 = static_cast<const unsigned short*>(d->res_w16);
-  a.bias = d->bias;
-  a.se_y = static_cast<const unsigned short*>(d->se_y);
-  a.se_gate = d->se_gate;
-  a.stats = d->stats;
-  // per-tile BatchNorm statistics come out of the generic pointwise-only kernel's epilogue only (what the training path launches)
-  if (a.stats && (d->depthwise || d->out_fp32 || d->stride != 1 || d->c_res > 0 || (d->flags & TS_TCS_IN_TAILZERO))) return TS_EUNSUPPORTED;
-  // the squeeze-excite tail lives in the split kernel's pointwise-only launch (tail-zero rows, stride 1, bf16 result, se_y at y's pitch);
-  // every other configuration answers TS_EUNSUPPORTED and the caller runs ts_se_apply_fwd as a separate pass
-  if (a.se_y && (!a.se_gate || d->depthwise || d->stride != 1 || d->out_fp32 || d->c_res > 0 || !(d->flags & TS_TCS_IN_TAILZERO) ||
-                 !(d->flags & TS_TCS_OUT_ZERO_TAIL) || d->c_in % KC || reinterpret_cast<uintptr_t>(a.se_y) % 16))
-    return TS_EUNSUPPORTED;
-  a.batch = d->batch;
-  a.c_in = d->c_in; a.c_out = d->c_out; a.c_res = d->c_res;
-  a.pitch_in = d->pitch_in; a.pitch_out = d->pitch_out; a.pitch_res = d->pitch_res;
-  a.t_out = d->t_out;
-  a.kernel = d->kernel; a.stride = d->stride; a.dilation = d->dilation; a.padding = d->padding;
-  a.relu = d->relu;
-  a.res_stride = d->res_stride < 1 ? 1 : d->res_stride;
-  a.kt_main = round_up(d->c_in, KC) / 16;
-  a.kt_res = round_up(d->c_res > 0 ? d->c_res : 1, KC) / 16;
-
-  a.zero_tail = (d->flags & TS_TCS_OUT_ZERO_TAIL) ? 1 : 0;
-  const bool wide = round_up(d->c_out, 32) > 256;   // 512-channel tiles for the wide layers
-  const int TT = wide ? 64 : 128;
-  const int n_tt = (d->t_out + TT - 1) / TT;
-  // tail-zero fast kernels: rows are 0 from their length to the pitch, the pitch has slack for the tile
-  // overreach and the buffer has zero guards, so the producers need no mask, predicate or bounds check
-  // (they also skip the re-masking of the depthwise output, which is only invisible when the output tail is zeroed)
-  bool tz = (d->flags & TS_TCS_IN_TAILZERO) && (d->flags & TS_TCS_OUT_ZERO_TAIL) && !d->out_fp32 && d->c_in % KC == 0 &&
-            (d->c_res == 0 || (d->c_res % KC == 0 && a.res_stride == 1 && d->pitch_res >= n_tt * TT));
-  if (d->depthwise) {
-    a.npass = d->dw_ksteps / NKP;
-    if (d->flags & TS_TCS_TAPS_PHASE) {
-      // dilation 2 as two interleaved dilation-1 sequences; dw_taps are packed for (K, stride 1, dilation 1, padding / 2)
-      const bool ok = (d->flags & TS_TCS_IN_TAILZERO) && (d->flags & TS_TCS_OUT_ZERO_TAIL) && d->stride == 1 && d->dilation == 2 &&
-                      d->padding % 2 == 0 && d->c_in % KC == 0 && d->c_res == 0 && round_up(d->c_out, 32) > 256;
-      if (!ok) return TS_EUNSUPPORTED;
-      TcsArgs w = a;
-      w.padl8 = 2 * round_up(d->padding / 2, 4);      // frames staged before the tile: even, so staged parity == frame parity
-      w.woff = 0;
-      const int n_ttp = (d->t_out + 95) / 96;
-      const bool fits = a.npass == 8 && 24 + 4 * (5 + d->dw_ksteps) <= 160 && (n_ttp - 1) * 96 - w.padl8 + 320 <= d->pitch_in &&
-                        d->pitch_in - d->t_in >= w.padl8 && d->pitch_out >= n_ttp * 96;
-      return (fits && d->dw_taps_raw) ? split_single(w, 8, 320, 1, 2, stream) : TS_EUNSUPPORTED;
-    }
-    a.taps_lds = d->dw_ksteps <= NKMAX;
-    const int padl4 = round_up(d->padding, 4);
-    a.padl8 = round_up(padl4, 8);
-    a.woff = a.padl8 - padl4;
-    const int M = TT / 16, RUN = TT / 4;
-    a.xuse = a.woff + 3 * RUN * d->stride + 4 * ((M - 1) * d->stride + d->dw_ksteps);
-    a.xe = round_up(a.xuse, 64);
-    if (a.xe > 64 * XMAX) return TS_EUNSUPPORTED;
-    a.xpitch = a.xe + 4;                              // row pitch == 8 (mod 16) bytes: conflict-free window reads
-    const int xj = a.xe / 64;
-    tz = tz && (n_tt - 1) * TT * d->stride - a.padl8 + a.xe <= d->pitch_in && d->pitch_in - d->t_in >= a.padl8;
-    if (tz && d->stride == 1 && d->dilation == 1 && a.npass <= 7 && d->dw_taps_raw) {
-      // split kernel: 96-frame granules, its own window geometry
-      const int WM = split_tile_wm(d->c_out);
-      const int TTp = 96 * WM;
-      const int n_ttp = (d->t_out + TTp - 1) / TTp;
-      const int xe = round_up(a.woff + TTp + 4 * d->dw_ksteps, 64);
-      const bool fits = (n_ttp - 1) * TTp - a.padl8 + xe <= d->pitch_in && d->pitch_out >= n_ttp * TTp &&
-                        (d->c_res == 0 || d->pitch_res >= (n_ttp - 1) * TTp + round_up(TTp, 64));
-      if (fits) {
-        const int st = split_single(a, a.npass, xe, WM, 1, stream);
-        if (st != TS_EUNSUPPORTED) return st;
-      }
-    }
-    if (tz) {
-      // straight-line instantiations (staged row groups XJ and depthwise passes NPASS are compile-time) for the
-      // geometries of the reference models; anything else takes the generic kernel below
-#define TS_TZ(TT_, NT_, S_, TL_, XJ_, NP_) \
-      if (TT == TT_ && d->stride == S_ && a.taps_lds == TL_ && xj == XJ_ && a.npass == NP_) \
-        return launch<TT_, NT_, S_, true, false, TL_, true, XJ_, NP_>(a, stream);
-      TS_TZ(128, 2, 1, true, 3, 3) TS_TZ(128, 2, 1, true, 3, 4) TS_TZ(128, 2, 1, true, 3, 2) TS_TZ(128, 2, 1, true, 3, 1)
-      TS_TZ(64, 4, 1, true, 2, 5) TS_TZ(64, 4, 1, true, 3, 6) TS_TZ(64, 4, 1, true, 3, 7) TS_TZ(64, 4, 1, true, 2, 3)
-      TS_TZ(64, 4, 1, false, 4, 15)
-      TS_TZ(128, 2, 2, true, 5, 4)
+// The instantiations.  Depthwise layers on tail-zero tensors (TZ) have straight-line kernels for the geometries of the reference models: staged
+// row groups XJ and depthwise passes NPASS are compile-time.  Every other kernel reads its geometry from TcsArgs (xj = npass = 0 here).
+int launch_tcs_generic(TcsArgs& a, int tt, int nt, int stride, bool dw, bool out_f32, bool taps_lds, bool tz, int xj, int npass, hipStream_t stream) {
+#define TS_GEN(TT_, NT_, S_, DW_, F32_, TL_, TZ_, XJ_, NP_)                                                                      \
+  if (tt == TT_ && nt == NT_ && stride == S_ && dw == DW_ && out_f32 == F32_ && taps_lds == TL_ && tz == TZ_ && xj == XJ_ && npass == NP_) \
+    return launch<TT_, NT_, S_, DW_, F32_, TL_, TZ_, XJ_, NP_>(a, stream);
+#define TS_TZ(TT_, NT_, S_, TL_, XJ_, NP_) TS_GEN(TT_, NT_, S_, true, false, TL_, true, XJ_, NP_)
+#define TS_ANY(TT_, NT_, S_, DW_, F32_, TL_) TS_GEN(TT_, NT_, S_, DW_, F32_, TL_, false, 0, 0)
+  TS_TZ(128, 2, 1, true, 3, 3) TS_TZ(128, 2, 1, true, 3, 4) TS_TZ(128, 2, 1, true, 3, 2) TS_TZ(128, 2, 1, true, 3, 1)
+  TS_TZ(64, 4, 1, true, 2, 5) TS_TZ(64, 4, 1, true, 3, 6) TS_TZ(64, 4, 1, true, 3, 7) TS_TZ(64, 4, 1, true, 2, 3)
+  TS_TZ(64, 4, 1, false, 4, 15)
+  TS_TZ(128, 2, 2, true, 5, 4)
+  /* depthwise, run-time geometry: taps through LDS (up to NKMAX k-steps) or from global memory */
+  TS_ANY(64, 4, 1, true, false, true) TS_ANY(128, 2, 1, true, false, true) TS_ANY(64, 4, 2, true, false, true) TS_ANY(128, 2, 2, true, false, true)
+  TS_ANY(64, 4, 1, true, false, false) TS_ANY(128, 2, 1, true, false, false) TS_ANY(64, 4, 2, true, false, false) TS_ANY(128, 2, 2, true, false, false)
+  /* pointwise only: tail-zero rows, masked rows (64 x 256 tiles for grids that would leave compute units idle), stride 2, f32 logits */
+  TS_GEN(64, 4, 1, false, false, false, true, 0, 0) TS_GEN(128, 2, 1, false, false, false, true, 0, 0)
+  TS_ANY(64, 4, 1, false, false, false) TS_ANY(128, 2, 1, false, false, false) TS_ANY(64, 2, 1, false, false, false)
+  TS_ANY(64, 4, 2, false, false, false) TS_ANY(128, 2, 2, false, false, false)
+  TS_ANY(128, 2, 1, false, true, false)
+#undef TS_ANY
 #undef TS_TZ
-    }
-    if (a.taps_lds) {
-      if (d->stride == 1)
-        return wide ? launch<64, 4, 1, true, false, true>(a, stream) : launch<128, 2, 1, true, false, true>(a, stream);
-      return wide ? launch<64, 4, 2, true, false, true>(a, stream) : launch<128, 2, 2, true, false, true>(a, stream);
-    }
-    if (d->stride == 1)
-      return wide ? launch<64, 4, 1, true, false, false>(a, stream) : launch<128, 2, 1, true, false, false>(a, stream);
-    return wide ? launch<64, 4, 2, true, false, false>(a, stream) : launch<128, 2, 2, true, false, false>(a, stream);
-  }
-  // pointwise only: `stride` is handled by the staging (generic gather when > 1)
-  if (d->out_fp32) {
-    if (d->stride != 1) return TS_EUNSUPPORTED;
-    const int st = launch_pw_logits(a, stream);          // the decoders: few output channels, a pure read stream (csrc/pw_logits.hip)
-    if (st != TS_EUNSUPPORTED) return st;
-    return launch<128, 2, 1, false, true>(a, stream);
-  }
-  if (d->stride == 1) {
-    // without a depthwise stage a tail-zero input needs no mask whether or not the output tail is zeroed: frames >= length
-    // come out as relu(shift), which is what the reference computes from its masked input (quirk A2)
-    const bool tz_in = (d->flags & TS_TCS_IN_TAILZERO) && d->c_in % KC == 0;
-    if (tz_in && d->c_res == 0) {
-      // pointwise only: the split kernel with identity stages only (the layer's input plays the residual input's role)
-      TcsArgs w = a;
-      const int WM = round_up(d->c_out, 32) <= 256 ? 2 : 1;
-      w.c_res = d->c_in; w.c_in = 0; w.xres = a.x; w.res_w = a.pw_w; w.res_w16 = a.pw_w16; w.kt_res = a.kt_main; w.pitch_res = d->pitch_in;
-      w.len_res = a.len_in; w.woff = 0; w.padl8 = 0;
-      if (g_pw_wide && WM == 1) {
-        // wide-frame consumers for the layers of more than 256 output channels (see launch_split_layer, wm code 4)
-        const int n_ttw = (d->t_out + 191) / 192;
-        if (d->pitch_in >= n_ttw * 192 && d->pitch_out >= n_ttw * 192) {
-          const int st = split_single(w, 2, 128, 4, 1, stream);
-          if (st != TS_EUNSUPPORTED) return st;
-        }
-      }
-      const int TTp = 96 * WM;
-      const int n_ttp = (d->t_out + TTp - 1) / TTp;
-      if (d->pitch_in >= (n_ttp - 1) * TTp + round_up(TTp, 64) && d->pitch_out >= n_ttp * TTp) {
-        const int st = WM == 2 ? split_single(w, 2, 256, 2, 1, stream) : split_single(w, 2, 128, 1, 1, stream);
-        if (st != TS_EUNSUPPORTED) return st;
-      }
-    }
-    if (a.se_y) return TS_EUNSUPPORTED;
-    if (tz && d->pitch_in >= n_tt * TT)
-      return wide ? launch<64, 4, 1, false, false, false, true, 0>(a, stream) : launch<128, 2, 1, false, false, false, true, 0>(a, stream);
-    // narrow layers whose 128-frame tiling leaves compute units idle (the training path's 32 clips x 501 frames: 128 tiles on 256 CUs) take
-    // 64-frame tiles: 9.2 -> 7.1 us at 256 -> 256 channels, 12.9 -> 9.5 at 512 -> 256 (tools/diag/pw_tile_bench.py); for the wide layers the
-    // same halving (64 x 256 tiles, two workgroups per CU) measured slower, 16.7 vs 15.4 us
-    if (!wide && (long long)d->batch * n_tt * ((round_up(d->c_out, 32) + 255) / 256) < cu_count()) return launch<64, 2, 1, false, false>(a, stream);
-    return wide ? launch<64, 4, 1, false, false>(a, stream) : launch<128, 2, 1, false, false>(a, stream);
-  }
-  if (d->stride == 2)
-    return wide ? launch<64, 4, 2, false, false>(a, stream) : launch<128, 2, 2, false, false>(a, stream);
+#undef TS_GEN
   return TS_EUNSUPPORTED;
 }
+
+}  // namespace ts

@@ -1,5 +1,6 @@
-// Shared between the fused TCS kernels (csrc/tcs_kernel.hip: first design / generic kernel and the C-ABI dispatch; csrc/tcs_split.hip:
-// split kernel).
+// Shared between the three files of the fused TCS sub-block: csrc/tcs_dispatch.hip (the C-ABI entry point: argument checks and the choice of
+// a kernel, host code only), csrc/tcs_split.hip (split kernel: the default for tail-zero tensors) and csrc/tcs_kernel.hip (generic kernel).
+// Each kernel file exports one non-template launcher, declared at the end of this header.
 #pragma once
 #include "ts_common.hpp"
 
@@ -9,6 +10,8 @@ namespace ts {
 
 constexpr int KC = 64;         // input channels per stage
 constexpr int NKP = 3;         // depthwise k-steps (of 4 samples) per pass
+constexpr int XMAX = 5;        // generic kernel: staged row length <= 64 * XMAX elements
+constexpr int NKMAX = 24;      // generic kernel: taps are cached in LDS up to this many k-steps
 
 struct TcsArgs {
   const unsigned short* x;     // [B][c_in][pitch_in]
@@ -151,6 +154,10 @@ struct SplitArgs {
 // TS_EUNSUPPORTED when no instantiation fits (npass = depthwise passes of 3 k-steps, xe = staged frames per row, a multiple of 64;
 // wm = 1: 96-frame x 512-channel tiles, 2: 192 x 256; dil = 1, or 2 for the phase-split form of a dilation-2 layer)
 int launch_split_layer(SplitArgs& a, int npass, int xe, int wm, int dil, hipStream_t stream);
+// generic kernel (csrc/tcs_kernel.hip), 64- or 128-frame tiles (tt) x 128 * nt output channels: TS_EUNSUPPORTED when the tuple is not instantiated.
+// tz: mask-free producers for tail-zero tensors, which for a depthwise layer (dw) exist only for given staged row groups xj = a.xe / 64 and
+// passes npass; all other kernels take the geometry from `a` and xj = npass = 0
+int launch_tcs_generic(TcsArgs& a, int tt, int nt, int stride, bool dw, bool out_f32, bool taps_lds, bool tz, int xj, int npass, hipStream_t stream);
 // pointwise layer with <= 32 output channels and f32 results (csrc/pw_logits.hip); TS_EUNSUPPORTED when the shape is not its
 int launch_pw_logits(const TcsArgs& w, hipStream_t stream);
 // time-tile choice of the split kernel for a layer: 1 = 96 frames, 2 = 192 frames (c_out <= 256 only)

@@ -24,39 +24,27 @@
 // of the product (git history: commit 4a86010 has the full kernel, ts_tcs_chain_fwd and its tests).
 #include "tcs_shared.hpp"
 
-#ifndef TS_SPLIT_SWITCH_OFF
-#define TS_SPLIT_SWITCH_OFF 0
-#endif
-#ifndef TS_SPLIT_DIRECT_STORE
-#define TS_SPLIT_DIRECT_STORE 0    // 1: result stores straight from the accumulators (8 bytes per lane), no LDS transpose (experiment)
-#endif
-#ifndef TS_SPLIT_RING
-#define TS_SPLIT_RING 2            // consumer weight fragments: k-steps in flight (see the consumer's `ring`; 1 = the round 4-5 loop, kept for A/B builds)
-#endif
-#ifndef TS_SPLIT_SWITCH_WM
-#define TS_SPLIT_SWITCH_WM 2         // which tiling the switch-off applies to: 2 = 192 x 256 (c_out <= 256), 1 = 96 x 512
-#endif
-#ifndef TS_SPLIT_STORE_AUX
+// The switch-off builds of round 6 (profiles/round6_tcs_256.txt) and the loops they were measured against are in git history:
+// profiles/tcs_cleanup.md lists them.
+
+namespace ts {
+
 // cache policy of the result stores (raw buffer aux: 1 = sc0, 2 = nt, 16 = sc1).  sc1 = write-through at system scope: the rows do not wait dirty in the
 // XCD's L2 for the end-of-kernel write-back; same-box A/B of the C2 encoder, 4 interleaved runs each: 2.812 2.792 2.801 2.801 ms (plain) vs 2.788 2.783
 // 2.791 2.789 (sc1); nt (streaming) costs +3 % -- it also evicts what the next launch would hit (profiles/round6_c4_pointwise.md section 3).
 // Layers of up to 512 output channels only: on Citrinet-1024 (C3) plain stores measured 0.6 % faster (8.64 vs 8.69 ms, twice).
-#define TS_SPLIT_STORE_AUX 16
-#endif
-
-namespace ts {
+constexpr int SPLIT_STORE_AUX = 16;
 
 // DIL == 2 (dilation-2 layers, K87 of QuartzNet): the even and the odd frames of a row are two independent dilation-1
 // sequences (y[2s+p] = sum_u w[u] x[2(s+u)+p - pad], pad even).  The producers stage each row as [even | odd] halves,
 // lane runs 0,1 filter the even half and 2,3 the odd half with dilation-1 tap fragments (no zero-stuffed Toeplitz rows:
 // 24 k-steps instead of 45), and lane pairs re-interleave their results on the way into the dw tile.
-// NT: 32-channel output tiles per consumer wave -- 2: a workgroup covers 512 (WM = 1) or 256 (WM = 2) output channels; 1 (WM = 1 only): 96 frames x
-// 256 channels, for layers of at most 256 output channels whose 192-frame tiling would leave a compute unit a single tile per layer (nothing
-// to overlap its prologue and epilogue with).
 // SE: the epilogue closes a CitrinetBlock -- y = relu(gate[b][co] * se_y[b][co][t] + result) with the main branch's output se_y read as 16-byte row
 // segments right where the result rows leave (what ts_se_apply_fwd did in a separate pass over three tensors).
-template <int NPASS, int XJ, int MT, int WM, int DIL = 1, int NT = 2, bool SE = false>
+// Every consumer wave owns 96 frames x 64 output channels: a workgroup covers 96 x 512 (WM = 1) or 192 x 256 (WM = 2).
+template <int NPASS, int XJ, int WM, int DIL = 1, bool SE = false>
 __global__ __launch_bounds__(768) void tcs_split_kernel(const SplitArgs a) {
+  constexpr int MT = 3, NT = 2;                   // 32-frame / 32-channel tiles per consumer wave
   constexpr int WN = 8 / WM;
   constexpr int FW = 32 * MT;
   constexpr int TT = FW * WM;
@@ -78,7 +66,7 @@ __global__ __launch_bounds__(768) void tcs_split_kernel(const SplitArgs a) {
   constexpr int NTD = (16 * CST + 1023) / 1024;   // KiB (= DMA instructions) per 16-channel group and stage
   constexpr int TAPB = NTD * 1024;
   constexpr int XSB = 16 * (64 * XJ + 4) * 2;     // bytes of a producer's staged rows
-  constexpr int ER = (WM == 2 || DIL == 2 || MT > 3) ? 16 : 32;   // output-channel rows of a consumer's epilogue tile
+  constexpr int ER = (WM == 2 || DIL == 2) ? 16 : 32;             // output-channel rows of a consumer's epilogue tile
   constexpr int PHW = 32 * XJ;                    // DIL == 2: frames of a staged half row
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -145,7 +133,7 @@ __global__ __launch_bounds__(768) void tcs_split_kernel(const SplitArgs a) {
     u32x4 X[ROWS2 ? 2 : 1][XP];
     // identity rows in flight: one stage ahead; TWO (a second register set, alternating statically) when the residual has an even number of
     // stages -- an identity stage is as short as the consumers' k-loop, shorter than a loaded HBM round trip.
-    constexpr bool ID2 = WM == 1 && MT <= 3;       // (the 192-frame identity rows are 6 registers per set: one set)
+    constexpr bool ID2 = WM == 1;                  // (the 192-frame identity rows are 6 registers per set: one set)
     u32x4 I[IDP], I2[ID2 ? IDP : 1];
     s16x4 P[NP];
     u32x2 T[NK];
@@ -180,24 +168,15 @@ __global__ __launch_bounds__(768) void tcs_split_kernel(const SplitArgs a) {
     auto dw_pass = [&](auto pc) {
       constexpr int p = decltype(pc)::value;
       if constexpr (p + WD < NPASS) {
-#if TS_SPLIT_SWITCH_OFF == 2
-        if (WM != TS_SPLIT_SWITCH_WM) {
-#endif
 #pragma unroll
         for (int u = 0; u < NKP; ++u) win_load((p + WD) * NKP + M - 1 + u);
 #pragma unroll
         for (int u = 0; u < NKP; ++u) tap_load((p + WD) * NKP + u);
-#if TS_SPLIT_SWITCH_OFF == 2
-        }
-#endif
       }
 #pragma unroll
       for (int kk = 0; kk < NKP; ++kk)
 #pragma unroll
         for (int m = 0; m < M; ++m) {    // the very first k-step starts from 0 (an inline constant: no register is zeroed)
-#if TS_SPLIT_SWITCH_OFF >= 1             // diagnostic builds only (tools/variants.py): the producers' matrix work switched off -- WRONG results, a lower bound
-          if (WM == TS_SPLIT_SWITCH_WM && !(p == 0 && kk == 0 && m < M)) continue;       // of what ANY faster depthwise producer could buy those launches
-#endif
           d[m] = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(__builtin_bit_cast(s16x4, T[p * NKP + kk]), P[p * NKP + kk + m],
                                                         (p == 0 && kk == 0) ? f32x4{0.f, 0.f, 0.f, 0.f} : d[m], 0, 0, 0);
         }
@@ -384,19 +363,18 @@ __global__ __launch_bounds__(768) void tcs_split_kernel(const SplitArgs a) {
   int abase[MT16];
 #pragma unroll
   for (int mt = 0; mt < MT16; ++mt) abase[mt] = taddr(8 * kg + q4, wm * FW + 16 * mt + 4 * p4);
-  constexpr int SEG = FW / 8 <= 16 ? 16 : 32;         // 16-byte segments of an epilogue row (FW frames), padded to a power of two
+  constexpr int SEG = 16;                             // 16-byte segments of an epilogue row (FW / 8 = 12), padded to a power of two
   constexpr int RPI = 64 / SEG;                       // rows per wave instruction in the epilogue
   const int rsub = lane / SEG, csub = lane % SEG;
   const int lane_w = lane * 16;
   const int lane_y = (rsub * a.pitch_out + csub * 8) * 2;
 
-  // B fragments: TS_SPLIT_RING sets of one k-step each; a slot is refilled right after its last use with the fragment of the k-step RING ahead
-  constexpr int RD = TS_SPLIT_RING;
-  s16x8 ring[RD][NT16];
+  // B fragments: two sets of one k-step each; a set is refilled right after its last use with the fragments of the k-step two ahead
+  s16x8 ring[2][NT16];
   f32x4 acc[MT16][NT16];
   float bnext[NT16];
-  s16x8 af[TS_SPLIT_RING == 1 ? MT16 : 3];
-  static_assert(TS_SPLIT_RING == 1 || MT16 % 3 == 0, "three rotating A-fragment registers");
+  s16x8 af[3];
+  static_assert(MT16 % 3 == 0, "three rotating A-fragment registers");
   auto read_a1 = [&](const char* src, int ks, int mt) {
     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((TS_LDS s16x4*)((TS_LDS char*)src + abase[mt] + ks * 32 * ROWB));
     const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((TS_LDS s16x4*)((TS_LDS char*)src + abase[mt] + ks * 32 * ROWB + 4 * ROWB));
@@ -431,9 +409,6 @@ __global__ __launch_bounds__(768) void tcs_split_kernel(const SplitArgs a) {
       }
     };
     auto w_next = [&]() {
-#if TS_SPLIT_SWITCH_OFF == 5            // diagnostic build 5: the weight loads are issued but never advance (always the same, cache-hot fragments; WRONG results)
-      return;
-#endif
       ++w_k;
       if (w_k == nk_all) {
         w_k = 0;
@@ -454,25 +429,7 @@ __global__ __launch_bounds__(768) void tcs_split_kernel(const SplitArgs a) {
         bnext[nt] = L.bias[col < a.c_out ? col : 0];
       }
     };
-    // one k-step: MT16 x NT16 products.
-#if TS_SPLIT_RING == 1
-    // `more_a`: the A fragments of the stage's second k-step replace the first one's as they retire
-    auto kstep = [&](const char* src, bool more_a) {
-#pragma unroll
-      for (int nt = 0; nt < NT16; ++nt) {
-#pragma unroll
-        for (int mt = 0; mt < MT16; ++mt) {
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mt], ring[0][nt], acc[mt][nt], 0, 0, 0);
-          if (more_a && nt == NT16 - 1) af[mt] = read_a1(src, 1, mt);
-        }
-#if TS_SPLIT_SWITCH_OFF != 4            // diagnostic build 4: the consumers' weight stream switched off (stale fragments, WRONG results): what the stream costs
-        load_w(0, nt);
-#endif
-      }
-      w_next();
-    };
-#else
-    // Frame-tile-major order: the four weight fragments of the k-step stay put while the A fragments stream through THREE registers (the one being
+    // one k-step: MT16 x NT16 products, in frame-tile-major order: the four weight fragments of the k-step stay put while the A fragments stream through THREE registers (the one being
     // multiplied, the next, and the one after that in flight from LDS) instead of six -- the 12 registers that frees, plus slack, hold a SECOND set of
     // weight fragments, so that a fragment is requested two k-steps (a whole stage) before its first use instead of one: the round-6 switch-off
     // runs priced the consumers' weight stream at 16 % of the encoder (10 % even with cache-hot fragments: latency, not bandwidth).
@@ -480,31 +437,22 @@ __global__ __launch_bounds__(768) void tcs_split_kernel(const SplitArgs a) {
       const int set = more_a ? 0 : 1;                      // a stage is two k-steps: the set follows the k-step's parity (static after inlining)
 #pragma unroll
       for (int mt = 0; mt < MT16; ++mt) {
-#if TS_SPLIT_SWITCH_OFF != 6            // diagnostic build 6: the consumers' A-fragment LDS reads inside the k-step switched off (stale fragments)
         if (mt + 2 < MT16) af[(mt + 2) % 3] = read_a1(src, more_a ? 0 : 1, mt + 2);
         else if (more_a) af[(mt + 2) % 3] = read_a1(src, 1, mt + 2 - MT16);
-#endif
 #pragma unroll
         for (int nt = 0; nt < NT16; ++nt) {
-#if TS_SPLIT_SWITCH_OFF == 7            // diagnostic build 7: the consumers' matrix instructions switched off (operands still fetched and kept alive)
-          asm volatile("" :: "v"(af[mt % 3]), "v"(ring[set][nt]));
-#else
           acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mt % 3], ring[set][nt], acc[mt][nt], 0, 0, 0);
-#endif
-#if TS_SPLIT_SWITCH_OFF != 4
           if (mt == MT16 - 1) load_w(set, nt);
-#endif
         }
       }
       w_next();
     };
-#endif
 
     TilePos pos;
     pos.init(tile0, tile_step, a.n_tt, a.n_z);
     w_seek(nk_main == 0);
 #pragma unroll
-    for (int set = 0; set < RD; ++set) {
+    for (int set = 0; set < 2; ++set) {
 #pragma unroll
       for (int nt = 0; nt < NT16; ++nt) load_w(set, nt);
       w_next();
@@ -522,7 +470,7 @@ __global__ __launch_bounds__(768) void tcs_split_kernel(const SplitArgs a) {
       for (int s = 0; s < n_stage; ++s, ++gs) {
         const char* const src = dwt + (gs & 1) * TILEB;
 #pragma unroll
-        for (int mt = 0; mt < (TS_SPLIT_RING == 1 ? MT16 : 2); ++mt) af[mt] = read_a1(src, 0, mt);
+        for (int mt = 0; mt < 2; ++mt) af[mt] = read_a1(src, 0, mt);
         __builtin_amdgcn_sched_barrier(0);
         kstep(src, true);
         __builtin_amdgcn_sched_barrier(0);
@@ -540,32 +488,6 @@ __global__ __launch_bounds__(768) void tcs_split_kernel(const SplitArgs a) {
       if (partial) keep = keep_first(keep, len_out - (tw + csub * 8));
       asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
       const s16x2 f2 = __builtin_bit_cast(s16x2, floor2);
-#if TS_SPLIT_DIRECT_STORE
-      // experiment: the accumulators leave as they are -- lane (channel n = lane & 15, frame group kg) stores its 4 frames (8 bytes) of every 16-frame
-      // tile; a store instruction covers 16 rows x 32 bytes, the six frame tiles of a row follow each other
-      if constexpr (!SE) {
-        const int lane_d = ((lane & 15) * a.pitch_out + 4 * kg) * 2;
-#pragma unroll
-        for (int nt = 0; nt < NT16; ++nt) {
-          const int ch0 = (c16_0 + nt) * 16;
-          const bool chan_ok = ch0 + (lane & 15) < a.c_out;
-          const int soff = ((b * a.c_out + ch0) * a.pitch_out + tw) * 2;
-#pragma unroll
-          for (int mt = 0; mt < MT16; ++mt) {
-            unsigned lo = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2,
-                pack_bf16_settled(acc[mt][nt][0], acc[mt][nt][1])), f2));
-            unsigned hi = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2,
-                pack_bf16_settled(acc[mt][nt][2], acc[mt][nt][3])), f2));
-            if (partial) {
-              const int n = len_out - (tw + 16 * mt + 4 * kg);
-              lo &= n >= 2 ? ~0u : (n == 1 ? 0xffffu : 0u);
-              hi &= n >= 4 ? ~0u : (n == 3 ? 0xffffu : 0u);
-            }
-            if (chan_ok) __builtin_amdgcn_raw_buffer_store_b64(u32x2{lo, hi}, ry, lane_d, soff + 32 * mt, 0);
-          }
-        }
-      } else
-#endif
       // 32 output channels (two accumulator columns) at a time through the wave-private LDS tile: lane (channel n = lane & 15, frame group
       // kg) writes its 4 frames (8 bytes) of every 16-frame tile into row n (+ 16 for the second column), the rows leave as 16-byte segments
 #pragma unroll
@@ -592,11 +514,7 @@ __global__ __launch_bounds__(768) void tcs_split_kernel(const SplitArgs a) {
           static_assert(NB * RB * RPI == ER, "row batches");
           if (csub < FW / 8) {
             const int row0 = cob + half * ER;
-#if TS_SPLIT_SWITCH_OFF == 10           // diagnostic build 10: every result store of a workgroup lands in the same 16 KB (WRONG results): stores issued and acknowledged, no write traffic
-            const int y_soff = ((((b * a.c_out + row0) * a.pitch_out + tw) * 2) & 0x3ff0) + (int)blockIdx.x * 32768;
-#else
             const int y_soff = ((b * a.c_out + row0) * a.pitch_out + tw) * 2;
-#endif
             const char* const prow = priv + (size_t)rsub * EP + csub * 16;
 #pragma unroll
             for (int bt = 0; bt < NB; ++bt) {
@@ -634,39 +552,33 @@ __global__ __launch_bounds__(768) void tcs_split_kernel(const SplitArgs a) {
 #pragma unroll
               for (int i = 0; i < RB; ++i) {
                 if (partial) v[i] &= keep;
-                if (row0 + RPI * (RB * bt + i) + rsub < a.c_out)
-#if TS_SPLIT_SWITCH_OFF == 8            // diagnostic build 8: the result stores switched off
-                  asm volatile("" :: "v"(v[i]));
-#else
-                  if (TS_SPLIT_STORE_AUX != 0 && a.c_out <= 512)      // (wave-uniform) -- see TS_SPLIT_STORE_AUX
-                    __builtin_amdgcn_raw_buffer_store_b128(v[i], ry, lane_y, y_soff + RPI * (RB * bt + i) * a.pitch_out * 2, TS_SPLIT_STORE_AUX);
+                if (row0 + RPI * (RB * bt + i) + rsub < a.c_out) {
+                  if (a.c_out <= 512)      // (wave-uniform) -- see SPLIT_STORE_AUX
+                    __builtin_amdgcn_raw_buffer_store_b128(v[i], ry, lane_y, y_soff + RPI * (RB * bt + i) * a.pitch_out * 2, SPLIT_STORE_AUX);
                   else
                     __builtin_amdgcn_raw_buffer_store_b128(v[i], ry, lane_y, y_soff + RPI * (RB * bt + i) * a.pitch_out * 2, 0);
-#endif
+                }
               }
             }
           }
         }
       }
-#if TS_SPLIT_SWITCH_OFF == 9            // diagnostic build 9: the consumers wait for their result stores' acknowledgements before the next tile (results unchanged)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     }
   }
 }
 
-template <int NPASS, int XJ, int MT, int WM, int DIL = 1, int NT = 2, bool SE = false>
+template <int NPASS, int XJ, int WM, int DIL = 1, bool SE = false>
 static int launch_split(SplitArgs& a, hipStream_t stream) {
-  constexpr int FW = 32 * MT, TT = FW * WM, CO_WG = 32 * NT * (8 / WM);
+  constexpr int FW = 96, TT = FW * WM, CO_WG = 64 * (8 / WM);
   constexpr int ROWB = TT <= 128 ? 256 : 512;
   constexpr int NK_ = NPASS * NKP, CST = (16 * NK_ + 16) % 32 == 16 ? 16 * NK_ + 16 : 16 * NK_ + 32, TAPB = (16 * CST + 1023) / 1024 * 1024;
   a.n_tt = (a.t_out + TT - 1) / TT;
   a.n_z = (round_up(a.c_out, 32) + CO_WG - 1) / CO_WG;
   a.n_tiles = a.batch * a.n_tt * a.n_z;
-  const size_t lds = (size_t)2 * KC * ROWB + (size_t)8 * ((WM == 2 || DIL == 2 || MT > 3) ? 16 : 32) * (FW * 2 + 24) +
+  const size_t lds = (size_t)2 * KC * ROWB + (size_t)8 * ((WM == 2 || DIL == 2) ? 16 : 32) * (FW * 2 + 24) +
                      (size_t)4 * (16 * (64 * XJ + 4) * 2 + 2 * TAPB);
   if (lds > 160 * 1024) return TS_EUNSUPPORTED;
-  auto kern = tcs_split_kernel<NPASS, XJ, MT, WM, DIL, NT, SE>;
+  auto kern = tcs_split_kernel<NPASS, XJ, WM, DIL, SE>;
   static bool attr_set[64] = {};                          // per device (one process may drive several GPUs)
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return TS_EINVAL;
@@ -684,23 +596,15 @@ static int launch_split(SplitArgs& a, hipStream_t stream) {
 }
 
 int launch_split_layer(SplitArgs& a, int npass, int xe, int wm, int dil, hipStream_t stream) {
-  if (wm == 4) {
-    // wide-frame consumers (round 6): every consumer wave owns 192 frames x 32 channels (workgroup tile 192 x 256) instead of 96 x 64 -- half the
-    // weight-fragment loads per matrix instruction (profiles/round6_tcs_256.txt prices that stream at 15 % of the encoder); pointwise-only layers only
-    // (with a depthwise stage the 192-frame producer rows and tap images do not fit the LDS beside the 64 KB tile pair)
-    if (dil != 1 || npass != 2 || a.layer.c_in != 0) return TS_EUNSUPPORTED;
-    if (a.layer.se_y) return a.layer.se_gate ? launch_split<2, 2, 6, 1, 1, 1, true>(a, stream) : TS_EUNSUPPORTED;
-    return launch_split<2, 2, 6, 1, 1, 1>(a, stream);
-  }
   if (a.layer.se_y) {
     // squeeze-excite tail: the pointwise-only launches of the Citrinet blocks (512 / 256 output channels per workgroup)
     if (!a.layer.se_gate || dil != 1 || npass != 2) return TS_EUNSUPPORTED;
-    if (xe == 128 && wm == 1) return launch_split<2, 2, 3, 1, 1, 2, true>(a, stream);
-    if (xe == 256 && wm == 2) return launch_split<2, 4, 3, 2, 1, 2, true>(a, stream);
+    if (xe == 128 && wm == 1) return launch_split<2, 2, 1, 1, true>(a, stream);
+    if (xe == 256 && wm == 2) return launch_split<2, 4, 2, 1, true>(a, stream);
     return TS_EUNSUPPORTED;
   }
   if (wm == 1 && round_up(a.c_out, 32) <= 256) return TS_EUNSUPPORTED;       // narrow layers run on the 192-frame tiles only (split_tile_wm)
-#define TS_PIPE(NP_, XJ_, WM_, DIL_) if (npass == NP_ && xe == 64 * XJ_ && wm == WM_ && dil == DIL_) return launch_split<NP_, XJ_, 3, WM_, DIL_>(a, stream);
+#define TS_PIPE(NP_, XJ_, WM_, DIL_) if (npass == NP_ && xe == 64 * XJ_ && wm == WM_ && dil == DIL_) return launch_split<NP_, XJ_, WM_, DIL_>(a, stream);
   TS_PIPE(3, 4, 2, 1) TS_PIPE(4, 4, 2, 1) TS_PIPE(5, 3, 1, 1) TS_PIPE(6, 3, 1, 1) TS_PIPE(7, 3, 1, 1)      /* QuartzNet: K 33..75 */
   TS_PIPE(2, 2, 1, 1) TS_PIPE(3, 3, 1, 1) TS_PIPE(4, 3, 1, 1) TS_PIPE(2, 4, 2, 1)                         /* Citrinet: K 11..41; pointwise only */
   TS_PIPE(8, 5, 1, 2)                                                                                      /* QuartzNet K87, dilation 2 */

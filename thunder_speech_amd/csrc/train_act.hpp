@@ -30,26 +30,10 @@ __device__ __forceinline__ void load8(const bf16_t* p, float (&v)[8]) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) { v[2 * j] = bf16_lo(a[j]); v[2 * j + 1] = bf16_hi(a[j]); }
 }
-// Activation rows leave with streaming (nontemporal) stores: a training launch writes 8-16 MB that the NEXT launch reads, possibly on another
-// XCD, so the lines have to reach memory anyway -- streaming them out while the kernel runs beats leaving them dirty in the XCD's L2 for the
-// end-of-kernel write-back the next launch waits for (measured on the 1x1 products: -10 % per launch, profiles/round6_pw_tile.txt).
-#ifndef TS_TRAIN_NT
-#define TS_TRAIN_NT 0
-#endif
-__device__ __forceinline__ void st16(u32x4* p, u32x4 v) {
-#if TS_TRAIN_NT
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
-__device__ __forceinline__ void st16(f32x4* p, f32x4 v) {
-#if TS_TRAIN_NT
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
+// Activation rows leave with plain stores.  Streaming (nontemporal) stores were built and measured on the training step: +4 % -- a launch writes
+// 8-16 MB that the NEXT launch reads, and streaming the lines out evicts what that launch would hit in L2.
+__device__ __forceinline__ void st16(u32x4* p, u32x4 v) { *p = v; }
+__device__ __forceinline__ void st16(f32x4* p, f32x4 v) { *p = v; }
 __device__ __forceinline__ void store8(float* p, const float (&v)[8]) {
   st16(reinterpret_cast<f32x4*>(p), f32x4{v[0], v[1], v[2], v[3]});
   st16(reinterpret_cast<f32x4*>(p + 4), f32x4{v[4], v[5], v[6], v[7]});

@@ -1,11 +1,9 @@
 #!/bin/bash
-# Same-box A/B of the C3 (Citrinet-1024) encoder step: wide-frame pointwise tiles on / off.
-for i in 1 2; do for w in 1 0; do python - <<PY
+# Same-box repeats of the C3 (Citrinet-1024) encoder step, each in a fresh process; TS_LIB_VARIANT selects a variant library (tools/variants.py).
+for i in 1 2 3 4; do python - <<PY
 import json, subprocess, sys, os
 sys.path.insert(0, ".")
 sys.argv = ["bench_extra.py", "c3", "--no-check"]
-from thunder_speech_amd import _lib
-_lib.lib().ts_tcs_pointwise_wide($w)
 import io, contextlib, runpy
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
@@ -16,6 +14,6 @@ with contextlib.redirect_stdout(buf):
 for line in buf.getvalue().splitlines():
     if line.startswith("{"):
         d = json.loads(line)
-        print("wide=$w", round(d["c3"]["ms_per_step"], 3))
+        print("run $i", round(d["c3"]["ms_per_step"], 3))
 PY
-done; done
+done
