@@ -426,7 +426,12 @@ def test_tile_statistics_out_of_the_pointwise_epilogue_equal_the_separate_pass()
     (ts_tcs_desc.stats) and summed by the next matrix-core depthwise launch (ts_train_dwconv_fwd_bn_tiles), instead of ts_train_bn_stats reading the
     tensor back (quartznet/blocks.py:317-338 in train mode: BatchNorm over all B x T frames, quirk A4).  The pairs are formed from the f32 accumulators,
     the pass from the bf16-stored values: outputs, every gradient and the running statistics of a 3-repeat block agree to bf16 accuracy, at 24 clips
-    (the matrix-core depthwise kernels need >= 17) with ragged lengths and a frame count that is no multiple of the tile."""
+    (the matrix-core depthwise kernels need >= 17) with ragged lengths and a frame count that is no multiple of the tile.
+    Each mode is also held on its own against the oracle's train-mode block evaluated in float64 on the same parameters: the output within the 3e-2 of
+    the scale that the two modes are allowed between themselves (some 18 roundings to bf16 lie on a path through the three repeats and the residual
+    branch -- stored rows, taps, 1x1 weights -- each 2^-9 of a value, carried 1:1 through the normalising layers: sqrt(18) x 2^-9 = 8e-3 of an
+    element's deviation, 4 to 5 deviations for the worst of 2 M elements, against a maximum of as many deviations), the running statistics within the
+    rtol 2e-3 / atol 2e-4 of the mode-against-mode check."""
     from thunder_speech_amd import train_ops
     from thunder_speech_amd.quartznet.blocks import QuartznetBlock
     g = torch.Generator().manual_seed(12)
@@ -444,6 +449,7 @@ def test_tile_statistics_out_of_the_pointwise_epilogue_equal_the_separate_pass()
             for p in blk.parameters():
                 if p.dim() == 1:
                     p.data.add_(0.1 * torch.randn_like(p))
+            sd64 = {k: v.detach().cpu().double().clone() if v.is_floating_point() else v.detach().cpu().clone() for k, v in blk.state_dict().items()}
             y, _ = blk(x, lengths)
             yf = train_ops.from_act(y) if train_ops.is_act(y) else y
             (yf * cot).sum().backward()
@@ -453,6 +459,18 @@ def test_tile_statistics_out_of_the_pointwise_epilogue_equal_the_separate_pass()
         train_ops.TILE_STATS = True
         train_ops.set_activation_dtype("fp32")
     (y1, g1, r1), (y0, g0, r0) = res[True], res[False]
+    # float64 reference: the oracle's block in train mode on the parameters both modes started from (same seed, same perturbation)
+    new64 = {}
+    y64, _ = otcs.block_forward(otcs.BlockSpec(in_ch=128, out_ch=256, repeat=3, kernel=33), sd64, "", x.cpu().double(), lengths.cpu(), training=True,
+                                new_stats=new64)
+    for mode, (ym, _, rm) in res.items():
+        err = float((ym.cpu().double() - y64).abs().max()) / float(y64.abs().max())
+        print(f"tile statistics {'on' if mode else 'off'}: block output max error / scale against float64 = {err:.3e}")
+        assert err <= 3e-2, (mode, err)
+        for n in rm:
+            d = (rm[n].cpu().double() - new64[n]).abs()
+            print(f"  {n}: max abs {float(d.max()):.3e}, max relative {float((d / new64[n].abs().clamp_min(1e-30)).max()):.3e}")
+            assert torch.allclose(rm[n].cpu().double(), new64[n], rtol=2e-3, atol=2e-4), (mode, n)
     assert float((y1 - y0).abs().max()) <= 3e-2 * float(y0.abs().max())
     for n in g0:            # three BatchNorm + ReLU layers deep, bf16 rounding boundaries and ReLU gates move with the last bits of the statistics
         assert float((g1[n] - g0[n]).norm()) <= 8e-2 * max(float(g0[n].norm()), 1e-6), n

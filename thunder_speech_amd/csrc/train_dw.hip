@@ -437,16 +437,18 @@ __device__ __forceinline__ void store_pair(T* ra, T* rb, const v2f (&acc)[8], in
   store8(ra + t, a); store8(rb + t, b);
 }
 
-// PH: entries te .. te + 7 of one row = frames 2 te .. 2 te + 15
+// PH: entries te .. te + 7 of one row = frames 2 te .. 2 te + 15.  The second 8 frames may start at the pitch (a multiple of 8, not of 16:
+// t = 200 on a pitch of 200 puts frames 200 .. 207 of the last 16 into the NEXT row, and behind the tensor for its last row): not written then
 template <class T>
-__device__ __forceinline__ void store_phase(T* row, const v2f (&acc)[8], int te, int lim) {
+__device__ __forceinline__ void store_phase(T* row, const v2f (&acc)[8], int te, int lim, int pitch) {
   float a[8], b[8];
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
     a[2 * m] = 2 * te + 2 * m < lim ? acc[m][0] : 0.f;             a[2 * m + 1] = 2 * te + 2 * m + 1 < lim ? acc[m][1] : 0.f;
     b[2 * m] = 2 * te + 8 + 2 * m < lim ? acc[4 + m][0] : 0.f;     b[2 * m + 1] = 2 * te + 9 + 2 * m < lim ? acc[4 + m][1] : 0.f;
   }
-  store8(row + 2 * te, a); store8(row + 2 * te + 8, b);
+  store8(row + 2 * te, a);
+  if (2 * te + 8 < pitch) store8(row + 2 * te + 8, b);
 }
 
 __host__ __device__ constexpr int pair_xl(int k8) { return PT + k8 + 16; }                       // staged x samples per tile
@@ -502,7 +504,7 @@ __global__ __launch_bounds__(256) void dw_fwd_pair_kernel(const T* __restrict__ 
 #pragma unroll
       for (int m = 0; m < 8; ++m) acc[m] = v2f{0.f, 0.f};
       fir_pair(xs + ((t8 >> 3) << 1), q, 0, k8, tp, acc);
-      if (PH) store_phase(ya, acc, t0 + t8, lo); else store_pair(ya, ya + pitch, acc, t0 + t8, lo);
+      if (PH) store_phase(ya, acc, t0 + t8, lo, pitch); else store_pair(ya, ya + pitch, acc, t0 + t8, lo);
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -748,7 +750,7 @@ __global__ __launch_bounds__(256) void dw_bwd_pair_kernel(const T* __restrict__ 
             s2 += v2f{ga != 0.f ? ga * (va[m] - mu_a) * rs_a : 0.f, gb != 0.f ? gb * (vb[m] - mu_b) * rs_b : 0.f};   // pitch padding may hold NaN bits
           }
         }
-        if (PH) store_phase(dx + r0, acc, t0 + i8, li); else store_pair(dx + r0, dx + r0 + pitch, acc, t0 + i8, li);
+        if (PH) store_phase(dx + r0, acc, t0 + i8, li, pitch); else store_pair(dx + r0, dx + r0 + pitch, acc, t0 + i8, li);
       }
       if (active) {
         const int per = round_up((nt + nq - 1) / nq, 8);
