@@ -26,7 +26,7 @@ extern "C" {
 #define TS_EINVAL (-1)       /* bad argument / unsupported shape */
 #define TS_EUNSUPPORTED (-2) /* valid reference configuration this build has no kernel for */
 
-#define TS_ABI_VERSION 12
+#define TS_ABI_VERSION 13
 
 /* Library identification: ABI version and the gfx target the code objects were built for. */
 int ts_abi_version(void);
@@ -105,6 +105,31 @@ typedef struct ts_tcs_desc {
  * y: bf16 or f32 [B][c_out][pitch_out]. */
 int ts_tcs_subblock_fwd(const ts_tcs_desc* desc, const void* x, const int32_t* len_in, const void* x_res,
                         const int32_t* len_res, void* y, void* stream);
+
+/* ABI v13.  Which kernel the calling thread's last ts_tcs_subblock_fwd launched: the entry point tries its kernels in a fixed order and a refusal
+ * of a faster one falls through to the next, so the return code alone does not say which one answered.  The record is thread-local host state:
+ * ts_tcs_subblock_fwd clears it on entry and the launcher that is reached fills it immediately before its launch, the template tuple from the
+ * kernel's own template parameters.  Fields a family does not have are 0. */
+#define TS_TCS_LAUNCH_NONE 0     /* nothing launched: no call on this thread yet, or the last one returned before reaching a launcher */
+#define TS_TCS_LAUNCH_GENERIC 1  /* csrc/tcs_kernel.hip: tt, nt, stride, dw, out_f32, tlds, tz, xj, npass */
+#define TS_TCS_LAUNCH_SPLIT 2    /* csrc/tcs_split.hip: npass, xj, wm, dil, se (and xcd) */
+#define TS_TCS_LAUNCH_LOGITS 3   /* csrc/pw_logits.hip: tt = frames per tile (96 or 128) */
+typedef struct ts_tcs_launch {
+  int32_t family;               /* TS_TCS_LAUNCH_* */
+  int32_t tt, nt;               /* generic: frames per tile, 128-channel groups per workgroup tile; logits: frames per tile */
+  int32_t stride, dw, out_f32;  /* generic: staging stride, depthwise stage, f32 result */
+  int32_t tlds, tz;             /* generic: taps cached in LDS, mask-free (tail-zero) producers */
+  int32_t xj, npass;            /* generic straight-line kernels and split: staged 64-frame groups per row, depthwise passes of 3 k-steps (0: run-time) */
+  int32_t wm, dil, se;          /* split: 1 = 96-frame x 512-channel tiles, 2 = 192 x 256; 2 = phase-split form of a dilation-2 layer; squeeze-excite tail */
+  int32_t grid;                 /* workgroups launched */
+  int32_t n_tt, n_z, n_tiles;   /* time tiles per clip, output-channel splits, tiles in all (logits: n_z = 1) */
+  int32_t lds_bytes;            /* dynamic LDS of the launch */
+  int32_t xcd;                  /* split: 1 = XCD-contiguous tile order */
+} ts_tcs_launch;
+/* Copies the calling thread's record to *out and returns TS_OK; "nothing launched" is TS_OK with family == TS_TCS_LAUNCH_NONE and every other
+ * field 0.  TS_EINVAL for a NULL `out`.  A filled record says that the launch was issued, not that it succeeded: that is ts_tcs_subblock_fwd's
+ * own return code. */
+int ts_tcs_last_launch(ts_tcs_launch* out);
 
 
 /* ------------------------------------------------------------------------------------------------

@@ -39,7 +39,7 @@ def test_library_builds_and_exports_every_declared_symbol():
 def test_library_loads_and_answers_version_queries():
     from thunder_speech_amd import _lib
     L = _lib.lib()
-    assert L.ts_abi_version() == _lib.ABI_VERSION == 12
+    assert L.ts_abi_version() == _lib.ABI_VERSION == 13
     assert L.ts_build_target() == b"gfx950"
     for t in (1, 127, 128, 129, 751, 1501, 2001):
         assert L.ts_time_pitch(t) == _lib.time_pitch(t) and _lib.time_pitch(t) % 128 == 0 and _lib.time_pitch(t) >= t
@@ -92,7 +92,7 @@ def test_ctypes_structs_match_the_c_compilers_layout(tmp_path):
     from thunder_speech_amd import _lib
     from thunder_speech_amd import build as b
     src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    structs = (("ts_tcs_desc", _lib.TcsDesc), ("ts_frontend_desc", _lib.FrontendDesc), ("ts_wgrad_item", _lib.WgradItem))
+    structs = (("ts_tcs_desc", _lib.TcsDesc), ("ts_tcs_launch", _lib.TcsLaunch), ("ts_frontend_desc", _lib.FrontendDesc), ("ts_wgrad_item", _lib.WgradItem))
     lines = []
     for struct, cls in structs:
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), src, flags=re.S).group(1)
@@ -120,7 +120,7 @@ def test_derived_signatures_pin_every_type_mapping():
     from thunder_speech_amd import _lib
     S, P = _lib.SIGNATURES, ctypes.POINTER
     i32, i64, u64, f32, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_void_p
-    assert len(S) == 118 and list(S) == _lib.EXPORTED_SYMBOLS
+    assert len(S) == 119 and list(S) == _lib.EXPORTED_SYMBOLS
     assert S["ts_abi_version"] == (ctypes.c_int, [])
     assert S["ts_build_target"][0] is ctypes.c_char_p
     assert S["ts_time_pitch"] == (ctypes.c_int, [i32])                                      # int
@@ -128,13 +128,14 @@ def test_derived_signatures_pin_every_type_mapping():
     assert S["ts_frontend_workspace_bytes"][0] is i64
     assert S["ts_train_pwconv_wgrad_multi_parts"] == (ctypes.c_int, [i32, i32, i32])         # int32_t return
     assert S["ts_tcs_subblock_fwd"] == (ctypes.c_int, [P(_lib.TcsDesc)] + [vp] * 6)
+    assert S["ts_tcs_last_launch"] == (ctypes.c_int, [P(_lib.TcsLaunch)])                    # struct* (an output)
     assert S["ts_train_pwconv_wgrad_multi"][1] == [P(_lib.WgradItem), i32, vp]
     args = S["ts_train_dropout"][1]
     assert args[5] is f32 and args[6] is u64 and args[2] is i64
     assert len(S["ts_gemm_f32"][1]) == 23 and S["ts_gemm_f32"][1][:2] == [vp, i64]
     assert S["ts_train_wgrad_reduce_multi"][1] == [vp, vp, vp, vp, i32, vp]                   # void* const*, const int64_t*
     assert S["ts_w2v_mask_embed"][1][1] is vp                                               # const uint8_t*
-    assert (_lib.ABI_VERSION, _lib.TS_EINVAL, _lib.TS_EUNSUPPORTED, _lib.GUARD_BYTES) == (12, -1, -2, 1024)
+    assert (_lib.ABI_VERSION, _lib.TS_EINVAL, _lib.TS_EUNSUPPORTED, _lib.GUARD_BYTES) == (13, -1, -2, 1024)
     assert (_lib.TCS_IN_TAILZERO, _lib.TCS_OUT_ZERO_TAIL, _lib.TCS_TAPS_PHASE) == (1, 2, 4)
 
 
@@ -405,6 +406,9 @@ def _tcs_host_cases():
         (dict(phase, dilation=1), {}, U), (dict(phase, **res), with_res, U), (dict(phase, c_out=256), {}, U),
         # ... a depthwise layer whose staged row exceeds 320 elements
         (dict(dw, c_out=256, kernel=229, padding=114, dw_ksteps=60), {}, U),
+        # ... among them every stride-2 layer of at most 256 output channels with more than 24 k-steps: the generic kernel's instantiation for
+        # 128-frame tiles, stride 2 and taps from global memory is never launched (tests/test_gpu_tcs_kernels.py: UNREACHABLE)
+        (dict(dw, c_out=256, kernel=95, stride=2, padding=47, dw_ksteps=27, t_out=50), {}, U),
     ]
     return [pytest.param(fields, args, want, id=f"{i}-{'einval' if want == E else 'eunsupported'}") for i, (fields, args, want) in enumerate(cases)]
 
@@ -419,13 +423,39 @@ def test_tcs_subblock_refuses_bad_descriptors_before_any_launch(fields, args, wa
     d = _lib.TcsDesc(**fields)
     got = _lib.lib().ts_tcs_subblock_fwd(ctypes.byref(d), A, A, args.get("x_res"), args.get("len_res"), A, None)
     assert got == want
+    # none of these calls reaches a launcher: the thread's launch record says "nothing launched"
+    rec = _lib.TcsLaunch(family=7, grid=7)
+    assert _lib.lib().ts_tcs_last_launch(ctypes.byref(rec)) == 0
+    assert rec.family == _lib.TCS_LAUNCH_NONE == 0 and bytes(rec) == bytes(_lib.TcsLaunch())
+
+
+def test_tcs_last_launch_refuses_null_and_starts_as_nothing_launched():
+    """ts_tcs_last_launch: TS_EINVAL for a null pointer; on a thread that never called ts_tcs_subblock_fwd the record is TS_TCS_LAUNCH_NONE with
+    every field 0 (the record is thread-local), and the families keep their values."""
+    import threading
+    from thunder_speech_amd import _lib
+    L = _lib.lib()
+    assert L.ts_tcs_last_launch(None) == _lib.TS_EINVAL
+    assert (_lib.TCS_LAUNCH_NONE, _lib.TCS_LAUNCH_GENERIC, _lib.TCS_LAUNCH_SPLIT, _lib.TCS_LAUNCH_LOGITS) == (0, 1, 2, 3)
+    assert [n for n, _ in _lib.TcsLaunch._fields_] == ["family", "tt", "nt", "stride", "dw", "out_f32", "tlds", "tz", "xj", "npass", "wm", "dil", "se",
+                                                       "grid", "n_tt", "n_z", "n_tiles", "lds_bytes", "xcd"]
+    seen = []
+
+    def fresh_thread():
+        rec = _lib.TcsLaunch(family=7, xcd=7)
+        seen.append((L.ts_tcs_last_launch(ctypes.byref(rec)), bytes(rec)))
+
+    th = threading.Thread(target=fresh_thread)
+    th.start()
+    th.join()
+    assert seen == [(0, bytes(_lib.TcsLaunch()))]
 
 
 _ASAN_DRIVER = r'''
 import ctypes as C, sys
 L = C.CDLL(sys.argv[1])
 i32, i64, vp = C.c_int32, C.c_int64, C.c_void_p
-assert L.ts_abi_version() == 12
+assert L.ts_abi_version() == 13
 L.ts_build_target.restype = C.c_char_p
 assert L.ts_build_target() == b"gfx950"
 assert [L.ts_time_pitch(t) for t in (1, 128, 751, 1501)] == [512, 512, 1152, 1920]

@@ -78,8 +78,19 @@ def test_pointwise_only_block_matches_oracle(cin, cout, t, lens):
     _run_case(cin, cout, 1, 1, 1, t, lens, False, separable=False)
 
 
-def _run_case_tail_zero(cin, cout, k, stride, dil, t, lens, residual, seed=0):
-    """Same comparison through the mask-free kernels: tail-zero inputs (arena, guards) and zeroed output tails."""
+def _last_launch():
+    """(split kernel's template tuple (NPASS, XJ, WM, DIL, SE) or None, record) of this thread's last ts_tcs_subblock_fwd (ts_tcs_last_launch)"""
+    import ctypes
+    from thunder_speech_amd import _lib
+    rec = _lib.TcsLaunch()
+    assert _lib.lib().ts_tcs_last_launch(ctypes.byref(rec)) == 0
+    split = (rec.npass, rec.xj, rec.wm, rec.dil, rec.se) if rec.family == _lib.TCS_LAUNCH_SPLIT else None
+    return split, rec
+
+
+def _run_case_tail_zero(cin, cout, k, stride, dil, t, lens, residual, seed=0, split=None, check=None):
+    """Same comparison through the mask-free kernels: tail-zero inputs (arena, guards) and zeroed output tails.
+    split: the split kernel the row's comment names, as its template tuple; check: a predicate on the launch record."""
     from thunder_speech_amd import plan, tensors as TS
     spec = otcs.BlockSpec(cin, cout, repeat=1, kernel=k, stride=stride, dilation=dil, residual=residual)
     sd = {key[2:]: v for key, v in otcs.synth_encoder_state([spec], seed=seed).items()}
@@ -104,13 +115,34 @@ def _run_case_tail_zero(cin, cout, k, stride, dil, t, lens, residual, seed=0):
     out.fill_(3.0)                                     # stale data from an earlier use must be overwritten
     y, _ = layer.run(xb, t, li, x_res=xb if residual else None, t_res=t, len_res=li if residual else None, out=out,
                      in_tail_zero=True, zero_tail=True)
+    launched, rec = _last_launch()
     torch.cuda.synchronize()
+    if split is not None:
+        assert launched == split, f"launched {launched} (family {rec.family}), the row names the split kernel {split}"
+    if check is not None:
+        assert check(rec), {n: getattr(rec, n) for n, _ in rec._fields_}
     got = y[:, :, :t_out].float().cpu()
     scale = max(1.0, float(ref.abs().max()))
     for b, n in enumerate(ref_len.tolist()):
         n = int(n)
         assert float((got[b, :, :n] - ref[b, :, :n]).abs().max()) <= 0.012 * scale
         assert float(got[b, :, n:].abs().max()) == 0.0 if n < t_out else True      # tail-zero invariant on the output
+
+
+# The rows of the table below whose comment names a kernel, by (cin, cout, k, t, clips): the split kernel's template tuple (NPASS, XJ, WM, DIL, SE)
+# that must have been launched, and what else the launch record must say.
+_WRAPS = lambda r: r.n_tiles > r.grid                       # more tiles than workgroups: the persistent loop wraps
+_NAMED = {
+    (512, 512, 87, 260, 2): ((8, 5, 1, 2, 0), None), (512, 512, 87, 751, 4): ((8, 5, 1, 2, 0), None), (64, 512, 87, 97, 3): ((8, 5, 1, 2, 0), None),
+    (320, 384, 11, 251, 2): ((2, 2, 1, 1, 0), None), (384, 640, 25, 200, 2): ((3, 3, 1, 1, 0), None),
+    (128, 1024, 39, 150, 2): ((4, 3, 1, 1, 0), lambda r: r.n_z == 2),
+    (128, 128, 17, 400, 2): ((2, 4, 2, 1, 0), lambda r: r.n_tt == 3),
+    (256, 256, 39, 401, 3): ((4, 4, 2, 1, 0), None),
+    (256, 256, 33, 1400, 160): ((3, 4, 2, 1, 0), _WRAPS),
+    (512, 512, 51, 570, 43): ((5, 3, 1, 1, 0), lambda r: r.n_tiles == 258 and _WRAPS(r) and r.xcd == 1),
+    (320, 512, 25, 300, 3): ((3, 3, 1, 1, 0), None), (320, 512, 25, 300, 130): ((3, 3, 1, 1, 0), _WRAPS),
+    (512, 512, 63, 751, 80): ((6, 3, 1, 1, 0), lambda r: r.n_tiles == 640 and _WRAPS(r)),
+}
 
 
 @pytest.mark.parametrize("cin,cout,k,stride,dil,t,lens,res", [
@@ -136,7 +168,8 @@ def _run_case_tail_zero(cin, cout, k, stride, dil, t, lens, residual, seed=0):
     (512, 512, 63, 1, 1, 751, [751, 700] * 40, False),             # the headline shape with 640 tiles: rows fetched by the consumer waves across tiles
 ])
 def test_tail_zero_fast_kernels_match_oracle(cin, cout, k, stride, dil, t, lens, res):
-    _run_case_tail_zero(cin, cout, k, stride, dil, t, lens, res)
+    split, check = _NAMED.get((cin, cout, k, t, len(lens)), (None, None))
+    _run_case_tail_zero(cin, cout, k, stride, dil, t, lens, res, split=split, check=check)
 
 
 # (the poison test lives in tests/test_gpu_configs.py::test_padding_region_never_leaks: different garbage per run)
@@ -166,6 +199,8 @@ def test_back_to_back_launches_never_use_the_next_stages_taps(k):
         y, _ = layer.run(xb, t, li, out=out, in_tail_zero=True, zero_tail=True)
         err = float((y[:, :, :t].float().cpu() - ref).abs().max())
         assert err <= 0.012 * scale, f"launch {it}: max err {err} (scale {scale})"
+    if k == 87:
+        assert _last_launch()[0] == (8, 5, 1, 2, 0)
 
 
 @pytest.mark.parametrize("cin,cout,t,lens", [(512, 1024, 751, [751, 400, 9]), (128, 256, 300, [300, 150])])
@@ -212,7 +247,9 @@ def test_pointwise_only_tail_zero_layer_with_a_clamped_channel_split_zeroes_its_
     out = TS.arena(("pwtz0o", cout), b, cout, t, "cuda")
     out.fill_(7.0)                                     # stale data must be overwritten, zeros included
     y, t_out = layer.run(xb, t, li, out=out, in_tail_zero=True, zero_tail=True)
+    launched, rec = _last_launch()
     torch.cuda.synchronize()
+    assert launched == (2, 2, 1, 1, 0) and rec.n_z == 2          # the split kernel's pointwise-only form, two channel splits
     assert t_out == t
     got = y[:, :, :t].float().cpu()
     scale = max(1.0, float(ref.abs().max()))

@@ -22,7 +22,7 @@ WAVLM_HEADER = os.path.join(ROOT, "include", "thunder_speech_amd_wavlm.h")    # 
 WAVLM_TRAIN_HEADER = os.path.join(ROOT, "include", "thunder_speech_amd_wavlm_train.h")    # second companion (WavLM fine-tuning), versioned on its own
 CONFORMER_HEADER = os.path.join(ROOT, "include", "thunder_speech_amd_conformer.h")        # third companion (wav2vec2-conformer), versioned on its own
 
-# Parameters and struct fields: these scalars, `const <struct>*` as POINTER(struct), every other pointer to one of
+# Parameters and struct fields: these scalars, `[const] <struct>*` as POINTER(struct), every other pointer to one of
 # _POINTEES (const or not, any depth) as c_void_p.  Return types: _RETURNS only.
 _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float}
 _POINTEES = {"void", "float", "int32_t", "int64_t", "uint64_t", "uint8_t"}
@@ -37,7 +37,7 @@ def _ctype(decl: str, where: str, structs: dict, ret: bool = False):
         return table[key]
     base = [w for w in words if w != "const"]
     if not ret and stars and len(base) == 1:
-        if key == f"const {base[0]}*" and base[0] in structs:
+        if stars == 1 and base[0] in structs:                           # `const struct*` in, `struct*` out
             return C.POINTER(structs[base[0]])
         if base[0] in _POINTEES:
             return C.c_void_p
@@ -87,11 +87,13 @@ WAVLM_TRAIN_ABI_VERSION = WAVLM_TRAIN_DEFINES["TS_WAVLM_TRAIN_ABI_VERSION"]
 CONFORMER_SIGNATURES, _, CONFORMER_DEFINES = _read_installed_header(CONFORMER_HEADER)
 CONFORMER_ABI_VERSION = CONFORMER_DEFINES["TS_CONFORMER_ABI_VERSION"]
 TcsDesc, FrontendDesc, WgradItem = STRUCTS["ts_tcs_desc"], STRUCTS["ts_frontend_desc"], STRUCTS["ts_wgrad_item"]
+TcsLaunch = STRUCTS["ts_tcs_launch"]
 EXPORTED_SYMBOLS = list(SIGNATURES)
 ABI_VERSION = DEFINES["TS_ABI_VERSION"]
 TS_EINVAL, TS_EUNSUPPORTED = DEFINES["TS_EINVAL"], DEFINES["TS_EUNSUPPORTED"]
 TCS_IN_TAILZERO, TCS_OUT_ZERO_TAIL = DEFINES["TS_TCS_IN_TAILZERO"], DEFINES["TS_TCS_OUT_ZERO_TAIL"]
 TCS_TAPS_PHASE = DEFINES["TS_TCS_TAPS_PHASE"]
+TCS_LAUNCH_NONE, TCS_LAUNCH_GENERIC, TCS_LAUNCH_SPLIT, TCS_LAUNCH_LOGITS = (DEFINES["TS_TCS_LAUNCH_" + n] for n in ("NONE", "GENERIC", "SPLIT", "LOGITS"))
 GUARD_BYTES = DEFINES["TS_GUARD_BYTES"]
 
 _lib: Optional[C.CDLL] = None

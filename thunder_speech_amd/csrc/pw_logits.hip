@@ -153,6 +153,11 @@ int launch_pw_logits(const TcsArgs& w, hipStream_t stream) {
   if (w.pitch_in < n_tt * lt || w.pitch_out % 4 || reinterpret_cast<uintptr_t>(w.y) % 16 || reinterpret_cast<uintptr_t>(w.x) % 16) return TS_EUNSUPPORTED;
   LogitArgs a{w.x, w.pw_w16, w.bias, static_cast<float*>(w.y), w.len_in, w.batch, w.c_in, w.c_out, w.pitch_in, w.pitch_out, w.t_out, w.relu, w.zero_tail, n_tt};
   const size_t lds = 4 * LK * LROWB;
+  ts_tcs_launch rec{};
+  rec.family = TS_TCS_LAUNCH_LOGITS;
+  rec.tt = lt;
+  rec.grid = w.batch * n_tt; rec.n_tt = n_tt; rec.n_z = 1; rec.n_tiles = w.batch * n_tt; rec.lds_bytes = (int32_t)lds;
+  tcs_launch_record() = rec;
   (void)hipGetLastError();
   if (t96) hipLaunchKernelGGL(pw_logits_kernel<6>, dim3((unsigned)(w.batch * n_tt)), dim3(256), lds, stream, a);
   else hipLaunchKernelGGL(pw_logits_kernel<8>, dim3((unsigned)(w.batch * n_tt)), dim3(256), lds, stream, a);

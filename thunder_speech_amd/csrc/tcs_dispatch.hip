@@ -3,7 +3,7 @@
 //   the split kernel (csrc/tcs_split.hip, launch_split_layer)     depthwise and pointwise-only layers on tail-zero tensors, stride 1
 //   the read-stream kernel (csrc/pw_logits.hip, launch_pw_logits) f32 decoder logits, few output channels
 //   the generic kernel (csrc/tcs_kernel.hip, launch_tcs_generic)  everything else: masked caller tensors, stride 2, odd geometries, per-tile statistics
-// A refusal (TS_EUNSUPPORTED) of a faster kernel falls through to the next one in that order.  DESIGN.md section 3.1 has the measurements
+// A refusal (TS_EUNSUPPORTED) of a faster kernel falls through to the next one in that order; ts_tcs_last_launch tells which one was launched.  DESIGN.md section 3.1 has the measurements
 // behind the thresholds.
 #include "tcs_shared.hpp"
 
@@ -17,6 +17,19 @@ extern "C" int ts_tcs_pointwise_tile_frames(int32_t batch, int32_t c_out, int32_
   if (round_up(c_out, 32) > 256) return 64;
   const int n_tt = (t_out + 127) / 128;
   return (long long)batch * n_tt * ((round_up(c_out, 32) + 255) / 256) < cu_count() ? 64 : 128;
+}
+
+namespace ts {
+ts_tcs_launch& tcs_launch_record() {
+  static thread_local ts_tcs_launch rec{};
+  return rec;
+}
+}  // namespace ts
+
+extern "C" int ts_tcs_last_launch(ts_tcs_launch* out) {
+  if (!out) return TS_EINVAL;
+  *out = ts::tcs_launch_record();
+  return TS_OK;
 }
 
 namespace {
@@ -161,6 +174,7 @@ int pointwise_plan(const ts_tcs_desc* d, TcsArgs& a, const GenericTile& g, bool 
 extern "C" int ts_tcs_subblock_fwd(const ts_tcs_desc* d, const void* x, const int32_t* len_in, const void* x_res,
                                    const int32_t* len_res, void* y, void* stream_) {
   using namespace ts;
+  tcs_launch_record() = ts_tcs_launch{};
   const int bad = check_args(d, x, len_in, x_res, len_res, y);
   if (bad != TS_OK) return bad;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);

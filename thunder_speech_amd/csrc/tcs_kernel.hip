@@ -497,6 +497,9 @@ __global__ __launch_bounds__(512, 2) void tcs_kernel(const TcsArgs a) {
 
     // ---- epilogue (overlaps the producers' first stage of the next tile) -------------------------------
     if constexpr (OUT_F32) {
+      // frames >= the length are stored as 0 when the caller asks for it (pointwise only, stride 1: the output length is the input's), as
+      // csrc/pw_logits.hip stores them for the shapes it takes
+      const int len_out = a.zero_tail ? a.len_in[b] : 0x7fffffff;
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
         const int co = (cot0 + nt) * 32 + (lane & 31);
@@ -509,6 +512,7 @@ __global__ __launch_bounds__(512, 2) void tcs_kernel(const TcsArgs a) {
               float v0 = acc[mt][nt][4 * rg + 0], v1 = acc[mt][nt][4 * rg + 1];
               float v2 = acc[mt][nt][4 * rg + 2], v3 = acc[mt][nt][4 * rg + 3];
               if (a.relu) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
+              if (t + 4 > len_out) { v0 = t + 0 < len_out ? v0 : 0.f; v1 = t + 1 < len_out ? v1 : 0.f; v2 = t + 2 < len_out ? v2 : 0.f; v3 = t + 3 < len_out ? v3 : 0.f; }
               if (t < a.pitch_out)
                 *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.y) + (size_t)(b * a.c_out + co) * a.pitch_out + t) =
                     f32x4{v0, v1, v2, v3};
@@ -621,6 +625,11 @@ static int launch(TcsArgs& a, hipStream_t stream) {
   }
   const int n_cu = cu_count();
   const int grid = a.n_tiles < n_cu ? a.n_tiles : n_cu;      // persistent: one workgroup per CU
+  ts_tcs_launch rec{};
+  rec.family = TS_TCS_LAUNCH_GENERIC;
+  rec.tt = TT; rec.nt = NT; rec.stride = STRIDE; rec.dw = DW; rec.out_f32 = OUT_F32; rec.tlds = TLDS; rec.tz = TZ; rec.xj = XJ; rec.npass = NPASS;
+  rec.grid = grid; rec.n_tt = a.n_tt; rec.n_z = a.n_z; rec.n_tiles = a.n_tiles; rec.lds_bytes = (int32_t)lds;
+  tcs_launch_record() = rec;
   (void)hipGetLastError();
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, a);
   return hip_status(hipGetLastError());

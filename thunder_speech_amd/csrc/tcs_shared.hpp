@@ -160,6 +160,8 @@ int launch_split_layer(SplitArgs& a, int npass, int xe, int wm, int dil, hipStre
 int launch_tcs_generic(TcsArgs& a, int tt, int nt, int stride, bool dw, bool out_f32, bool taps_lds, bool tz, int xj, int npass, hipStream_t stream);
 // pointwise layer with <= 32 output channels and f32 results (csrc/pw_logits.hip); TS_EUNSUPPORTED when the shape is not its
 int launch_pw_logits(const TcsArgs& w, hipStream_t stream);
+// the calling thread's launch record (ts_tcs_last_launch; defined in csrc/tcs_dispatch.hip): each launcher fills it immediately before its launch
+ts_tcs_launch& tcs_launch_record();
 // time-tile choice of the split kernel for a layer: 1 = 96 frames, 2 = 192 frames (c_out <= 256 only)
 int split_tile_wm(int c_out);
 

@@ -590,6 +590,11 @@ static int launch_split(SplitArgs& a, hipStream_t stream) {
   const int n_cu = cu_count();
   const int grid = a.n_tiles < n_cu ? a.n_tiles : n_cu;
   a.xcd = grid % 8 == 0 ? 1 : 0;
+  ts_tcs_launch rec{};
+  rec.family = TS_TCS_LAUNCH_SPLIT;
+  rec.npass = NPASS; rec.xj = XJ; rec.wm = WM; rec.dil = DIL; rec.se = SE;
+  rec.grid = grid; rec.n_tt = a.n_tt; rec.n_z = a.n_z; rec.n_tiles = a.n_tiles; rec.lds_bytes = (int32_t)lds; rec.xcd = a.xcd;
+  tcs_launch_record() = rec;
   (void)hipGetLastError();
   hipLaunchKernelGGL(kern, dim3(grid), dim3(768), lds, stream, a);
   return hip_status(hipGetLastError());
