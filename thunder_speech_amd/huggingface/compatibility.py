@@ -64,15 +64,24 @@ def module_from_huggingface(model, feature_extractor, tokenizer=None) -> BaseCTC
     return module.eval()
 
 
-def load_huggingface_checkpoint(model_name: str, **model_kwargs: Dict[str, Any]) -> BaseCTCModule:
+def load_huggingface_checkpoint(model_name: str, target_lang: Optional[str] = None, **model_kwargs: Dict[str, Any]) -> BaseCTCModule:
     """`model_name`: hub identifier ("facebook/wav2vec2-large-960h") or a local directory written by `save_pretrained`;
     `model_kwargs` go to `AutoModelForCTC.from_pretrained`.  A checkpoint without a tokenizer yields a module whose
-    decoder and text_transform are None, with the reference's warning."""
+    decoder and text_transform are None, with the reference's warning.
+
+    `target_lang` (MMS: "facebook/mms-1b-all" and its kin) selects one language of a multilingual checkpoint: transformers loads that
+    language's `adapter.<lang>.safetensors` (attention adapters and lm_head, which it resizes: `ignore_mismatched_sizes=True` unless the caller
+    set it) and the tokenizer takes that language's entry of the nested vocab.json, so the decoder and text_transform are that language's.
+    Another language needs another module: load the checkpoint again."""
     from transformers import AutoFeatureExtractor, AutoModelForCTC, AutoTokenizer
+    tokenizer_kwargs = {}
+    if target_lang is not None:
+        model_kwargs = {"ignore_mismatched_sizes": True, **model_kwargs, "target_lang": target_lang}
+        tokenizer_kwargs["target_lang"] = target_lang
     model = AutoModelForCTC.from_pretrained(model_name, **model_kwargs)
     feature_extractor = AutoFeatureExtractor.from_pretrained(model_name)
     try:
-        tokenizer = AutoTokenizer.from_pretrained(model_name)
+        tokenizer = AutoTokenizer.from_pretrained(model_name, **tokenizer_kwargs)
         if not hasattr(model, "lm_head"):
             raise KeyError("lm_head")
     except (OSError, KeyError):

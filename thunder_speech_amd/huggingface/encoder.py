@@ -8,7 +8,8 @@ difference); the arithmetic runs in `Wav2Vec2Plan`, which keeps packed fp32 devi
 call per stage.  Both published families (group-norm / post-LN: wav2vec2-base-960h, -large-960h; layer-norm / pre-LN: -large-lv60, xlsr);
 WavLM runs the same sequence with its gated relative-position attention (csrc/wavlm.hip, include/thunder_speech_amd_wavlm.h) in place of
 the wav2vec2 one (fine-tuning in mixed precision only: csrc/wavlm_train.hip); wav2vec2-conformer (rotary) runs conformer blocks behind the same
-front end (huggingface/conformer.py, inference only); training mode (fine-tuning with the conv feature extractor frozen) runs
+front end (huggingface/conformer.py, inference only); MMS (config.adapter_attn_dim: an attention adapter behind every pre-LN layer) and the head_dim 80
+of MMS-1B / XLS-R 1B run on csrc/mms.hip (include/thunder_speech_amd_mms.h, inference only); training mode (fine-tuning with the conv feature extractor frozen) runs
 through huggingface/train.py; no CPU fallback."""
 from __future__ import annotations
 
@@ -98,6 +99,16 @@ def _check_conformer_config(cfg, bad: list) -> None:
         bad.append("feat_extract_activation != gelu")
 
 
+ATTN_ADAPTER_MAX_DIM = 64          # ts_mms_attn_adapter_fwd: adapter_attn_dim a multiple of 16 up to 64, hidden a multiple of 8 up to 4096
+
+
+def has_attn_adapters(cfg) -> bool:
+    """config.adapter_attn_dim puts a Wav2Vec2AttnAdapterLayer behind every Wav2Vec2EncoderLayerStableLayerNorm (MMS); transformers' post-LN layer
+    class has none, whatever the config says."""
+    return (getattr(cfg, "adapter_attn_dim", None) is not None and bool(getattr(cfg, "do_stable_layer_norm", False))
+            and getattr(cfg, "model_type", "wav2vec2") == "wav2vec2")
+
+
 def _check_config(cfg) -> None:
     bad = []
     if getattr(cfg, "model_type", "wav2vec2") not in SUPPORTED_MODEL_TYPES:
@@ -118,6 +129,12 @@ def _check_config(cfg) -> None:
     if getattr(cfg, "model_type", "wav2vec2") == "wavlm" and int(cfg.hidden_size) != 64 * int(cfg.num_attention_heads):
         bad.append(f"model_type='wavlm' with head_dim={int(cfg.hidden_size) // int(cfg.num_attention_heads)} (the gated relative-position attention "
                    "kernels take head_dim 64, as every published WavLM)")
+    if has_attn_adapters(cfg):
+        a, c = int(cfg.adapter_attn_dim), int(cfg.hidden_size)
+        if a < 16 or a % 16 or a > ATTN_ADAPTER_MAX_DIM:
+            bad.append(f"adapter_attn_dim={a} (the attention-adapter kernel takes multiples of 16 up to {ATTN_ADAPTER_MAX_DIM}; MMS has 16)")
+        elif c % 8 or c > 4096:
+            bad.append(f"adapter_attn_dim={a} with hidden_size={c} (the attention-adapter kernel takes a hidden size that is a multiple of 8, up to 4096)")
     if bad:
         raise NotImplementedError("wav2vec2 HIP path: unsupported configuration: " + ", ".join(bad))
 
@@ -152,6 +169,8 @@ class Wav2Vec2Plan:
         # lv60 / xlsr family; Data2VecAudioConvLayer is always conv -> LayerNorm -> GELU and its config carries no feat_extract_norm
         self.layer_norm_convs = self.d2v or getattr(cfg, "feat_extract_norm", "group") == "layer"
         self.stable_ln = bool(getattr(cfg, "do_stable_layer_norm", False))
+        # head_dim 80 (MMS-1B, XLS-R 1B) in bf16 mode: ts_mms_attention_fwd; fp32 mode and every other head_dim keep ts_w2v_attention_fwd
+        self.mms_attention = bool(self.prec) and self.model_type != "wavlm" and self.hidden == 80 * self.heads
         self.fp_has_ln = bool(getattr(cfg, "feat_proj_layer_norm", True))                  # HubertFeatureProjection
         opt = lambda k: f(k) if k in sd else None
         self.conv_b = [opt(f"feature_extractor.conv_layers.{i}.conv.bias") if getattr(cfg, "conv_bias", False) else None
@@ -166,6 +185,7 @@ class Wav2Vec2Plan:
                        for i in range(1, len(self.kernels))]
         self.feature_extractor_only = bool(feature_extractor_only)
         self.layers = []
+        self.attn_adapter_keys = []                      # state-dict keys of the attention adapters this plan packed (MMS), in layer order
         if self.feature_extractor_only:
             return
         self._pack_projection(f, gw)
@@ -201,6 +221,13 @@ class Wav2Vec2Plan:
                 w1=gw(f(q + "feed_forward.intermediate_dense.weight")), b1=f(q + "feed_forward.intermediate_dense.bias"),
                 w2=gw(f(q + "feed_forward.output_dense.weight")), b2=f(q + "feed_forward.output_dense.bias"),
                 ln2=(f(q + "final_layer_norm.weight"), f(q + "final_layer_norm.bias"))))
+            if q + "adapter_layer.linear_1.weight" in sd:
+                # Wav2Vec2AttnAdapterLayer (MMS): LayerNorm (eps 1e-5) -> linear_1 [a][c] -> ReLU -> linear_2 [c][a], added to the residual stream
+                self.attn_adapter_keys += [q + "adapter_layer." + k for k in ("norm.weight", "norm.bias", "linear_1.weight", "linear_1.bias",
+                                                                              "linear_2.weight", "linear_2.bias")]
+                self.layers[-1]["ad"] = dict(norm=(f(q + "adapter_layer.norm.weight"), f(q + "adapter_layer.norm.bias")),
+                                             w1=gw(f(q + "adapter_layer.linear_1.weight")), b1=f(q + "adapter_layer.linear_1.bias"),
+                                             w2=gw(f(q + "adapter_layer.linear_2.weight")), b2=f(q + "adapter_layer.linear_2.bias"))
             if self.wavlm:
                 # WavLMAttention's gate: gru_rel_pos_linear [8][64] + bias, gru_rel_pos_const [1][H][1][1] -> [H]
                 self.layers[-1].update(gate_w=f(q + "attention.gru_rel_pos_linear.weight"), gate_b=f(q + "attention.gru_rel_pos_linear.bias"),
@@ -283,6 +310,18 @@ class Wav2Vec2Plan:
                                     self.eps if eps is None else eps, x.shape[0] * x.shape[1], x.shape[2], act, self._ptr(y),
                                     self._ptr(y_op), stream)
         _lib.check(st, "ts_w2v_layernorm_fwd")
+        return y, (y_op if self.prec else y)
+
+    def _attn_adapter(self, L, stream, h, ad, next_ln, last: bool):
+        """h += adapter(h) in place, and LN(h; next_ln) in the same launch: the next layer's layer_norm as the GEMM operand of its QKV product, or
+        (`last`) encoder.layer_norm as the f32 result of the encoder.  -> (f32 result or None, GEMM operand or None)."""
+        y = torch.empty_like(h) if (last or not self.prec) else None
+        y_op = self._op(*h.shape) if (self.prec and not last) else None
+        a = ad["w1"].shape[0]
+        st = L.ts_mms_attn_adapter_fwd(h.data_ptr(), h.shape[0] * h.shape[1], h.shape[2], a, ad["norm"][0].data_ptr(), ad["norm"][1].data_ptr(),
+                                       ad["w1"].data_ptr(), ad["b1"].data_ptr(), ad["w2"].data_ptr(), ad["b2"].data_ptr(), next_ln[0].data_ptr(),
+                                       next_ln[1].data_ptr(), self.eps, self._ptr(y), self._ptr(y_op), self.prec, stream)
+        _lib.check(st, "ts_mms_attn_adapter_fwd")
         return y, (y_op if self.prec else y)
 
     def feature_extractor(self, audio: torch.Tensor) -> torch.Tensor:
@@ -374,6 +413,8 @@ class Wav2Vec2Plan:
             rel_bias = self._buf(self.heads, 2 * t - 1)
             _lib.check(L.ts_wavlm_rel_bias(self.rel_embed.data_ptr(), self.abs_bucket.data_ptr(), self.nb, self.md, self.heads, t,
                                            rel_bias.data_ptr(), stream), "ts_wavlm_rel_bias")
+        elif self.mms_attention:
+            att_ws = None                              # head_dim 80 in bf16 mode: the fused kernel of csrc/mms.hip, no [t][t] scores
         else:
             att_ws = self._buf(L.ts_w2v_attention_workspace_bytes(b, t, self.heads, self.prec), dtype=torch.uint8)
 
@@ -387,6 +428,10 @@ class Wav2Vec2Plan:
                                                     rel_bias.data_ptr(), ctx_op.data_ptr(), att_ws.data_ptr() if att_ws.numel() else None,
                                                     stream), "ts_wavlm_attention_fwd")
                 return ctx_op
+            if self.mms_attention:
+                _lib.check(L.ts_mms_attention_fwd(qkv_op.data_ptr(), b, t, c, self.heads, self._ptr(key_len), ctx_op.data_ptr(), stream),
+                           "ts_mms_attention_fwd")
+                return ctx_op
             _lib.check(L.ts_w2v_attention_fwd(qkv_op.data_ptr(), b, t, c, self.heads, self._ptr(key_len), self.prec, ctx_op.data_ptr(),
                                               att_ws.data_ptr(), stream), "ts_w2v_attention_fwd")
             return ctx_op
@@ -395,13 +440,23 @@ class Wav2Vec2Plan:
             # pre-LN family: h += attn(LN(h)); h += ffn(LN(h)); one LayerNorm after the last layer
             assert pos_res is None
             h = hp
-            for lw in self.layers:
-                _, x_op = self._ln(L, stream, h, lw["ln1"], want_f32=False)
+            y, x_op = None, None                        # LN(h) for what comes next, when the previous layer's adapter launch computed it
+            for i, lw in enumerate(self.layers):
+                if x_op is None:
+                    _, x_op = self._ln(L, stream, h, lw["ln1"], want_f32=False)
                 self._linear(L, stream, attention(x_op), lw["wo"], lw["bo"], into=h)        # h += attn W^T (+ bias in the epilogue)
                 _, x_op = self._ln(L, stream, h, lw["ln2"], want_f32=False)
                 _, f1_op = self._linear(L, stream, x_op, lw["w1"], lw["b1"], act=1, want_op=True)
                 self._linear(L, stream, f1_op, lw["w2"], lw["b2"], into=h)
-            h, _ = self._ln(L, stream, h, self.enc_ln, want_op=False)
+                x_op = None
+                if "ad" in lw:
+                    # MMS: h += adapter(h); the launch also computes the LayerNorm that reads h next -- layer i + 1's, or the encoder's
+                    last = i + 1 == len(self.layers)
+                    y, x_op = self._attn_adapter(L, stream, h, lw["ad"], self.enc_ln if last else self.layers[i + 1]["ln1"], last)
+            if self.layers and "ad" in self.layers[-1]:
+                h = y
+            else:
+                h, _ = self._ln(L, stream, h, self.enc_ln, want_op=False)
             return self._adapter(L, stream, h) if self.adapter else h
         # post-LN family: LayerNorm before the layers, after each residual add inside them
         h, h_op = self._ln(L, stream, hp, self.enc_ln, res=pos_res)
@@ -491,6 +546,9 @@ class HuggingFaceEncoderAdapt(nn.Module):
         if self.training and getattr(self.original_encoder.config, "model_type", "wav2vec2") == "wavlm":
             from .train import refuse_untrainable
             refuse_untrainable(self, True)              # adapter, mask_feature_prob, unfrozen feature extractor: by name, before any device work
+        if self.training and has_attn_adapters(self.original_encoder.config):
+            from .train import refuse_untrainable
+            refuse_untrainable(self, self.train_precision == "bf16")       # adapter_attn_dim: by name, before any device work
         _t.require_gpu(audio, "wav2vec2 encoder")
         x = audio.to(torch.float32).contiguous()
         if self.training:

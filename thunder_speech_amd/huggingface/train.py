@@ -723,6 +723,7 @@ def train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
 def refuse_untrainable(adapt, mixed: bool) -> None:
     """Raise NotImplementedError, by name, for a configuration this training path has no backward for (no device work: the WavLM adapter calls it
     before its GPU check).  `mixed`: train_precision == "bf16"."""
+    from .encoder import has_attn_adapters
     enc = adapt.original_encoder
     cfg = enc.config
     model_type = getattr(cfg, "model_type", "wav2vec2")
@@ -737,6 +738,10 @@ def refuse_untrainable(adapt, mixed: bool) -> None:
         raise NotImplementedError(f"HIP fine-tuning path: model_type={cfg.model_type!r} is inference-only (wav2vec2 and wavlm checkpoints fine-tune)")
     if getattr(cfg, "add_adapter", False):
         raise NotImplementedError("HIP fine-tuning path: add_adapter=True is inference-only (the adapter layers have no backward here)")
+    if has_attn_adapters(cfg):
+        # MMS: the attention adapters (csrc/mms.hip) have no backward; a step without them would train a different network
+        raise NotImplementedError(f"HIP fine-tuning path: adapter_attn_dim={cfg.adapter_attn_dim} is inference-only (the attention adapters have no "
+                                  "backward here)")
     if float(getattr(cfg, "mask_feature_prob", 0.0)) > 0.0 and getattr(cfg, "apply_spec_augment", True):
         raise NotImplementedError("wav2vec2 HIP training path: mask_feature_prob > 0 is not supported")
     unfrozen = [n for n, p in enc.feature_extractor.named_parameters() if p.requires_grad]
