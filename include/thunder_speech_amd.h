@@ -26,7 +26,7 @@ extern "C" {
 #define TS_EINVAL (-1)       /* bad argument / unsupported shape */
 #define TS_EUNSUPPORTED (-2) /* valid reference configuration this build has no kernel for */
 
-#define TS_ABI_VERSION 13
+#define TS_ABI_VERSION 14
 
 /* Library identification: ABI version and the gfx target the code objects were built for. */
 int ts_abi_version(void);
@@ -272,6 +272,16 @@ int ts_fe_mel(const float* x, const float* fb, float* out, int32_t batch, int32_
 int ts_fe_normalize(const float* x, const int32_t* len, float* out, int32_t batch, int32_t features, int32_t t, float guard, void* stream);
 /* Debug/parity hook: copy of the un-normalised log-mel [B][n_frames][n_mels] f32 left in workspace. */
 const float* ts_frontend_logmel_ptr(const ts_frontend_desc* desc, const void* workspace);
+/* ABI v14.  What ts_mel_frontend_fwd would launch its first kernel with for this descriptor, computed by the function the entry point itself
+ * launches from: grid = persistent workgroups (at most CUs x resident workgroups per CU: 3 in eval mode, 2 for the dither instantiation on an
+ * MI355X), n_groups = batch x ceil(n_frames / 16) frame groups they walk (workgroup w takes groups w, w + grid, ...), lds_bytes = its dynamic LDS,
+ * dither_instantiation = 1 when desc->dither > 0.  Host code only: nothing is launched and no stream is touched (the device's properties and the
+ * occupancy query are read; without a device 256 CUs and the LDS limit alone are assumed).  Returns what ts_mel_frontend_fwd returns for the
+ * descriptor (TS_EINVAL / TS_EUNSUPPORTED as there: TS_EUNSUPPORTED for n_fft != 512, n_mels > 256 and a first kernel whose LDS -- the staged span
+ * 15 hop + 512, the tables and the CSR bank -- exceeds 160 KiB; TS_EINVAL also when batch x ceil(n_frames / 16) does not fit an int32;
+ * ABI v14 also makes n_mels 248 .. 256 run as documented: the normaliser's LDS exceeds 64 KiB there and is now opted in to), TS_EINVAL for a
+ * NULL argument.  The query changes no state: the LDS opt-in of the kernels is ts_mel_frontend_fwd's. */
+int ts_frontend_launch_config(const ts_frontend_desc* desc, int32_t* grid, int32_t* n_groups, int32_t* lds_bytes, int32_t* dither_instantiation);
 
 /* ------------------------------------------------------------------------------------------------
  * Training-time augmentation.  SpecAugment / SpecCutout (quartznet/spec_augment.py:23-102): a mask is a row
@@ -310,6 +320,15 @@ int64_t ts_ctc_workspace_bytes(int32_t batch, int32_t n_classes, int32_t n_frame
 int ts_ctc_loss(const float* logits, int32_t batch, int32_t n_classes, int32_t n_frames, int32_t pitch,
                 const int32_t* targets, int32_t s_max, const int32_t* input_len, const int32_t* target_len,
                 int32_t blank, float* nll, float* loss, float* grad, void* workspace, void* stream);
+/* ABI v14.  Which recursion kernel ts_ctc_loss launches for a tensor of n_frames frames and a label capacity of s_max, computed by the function
+ * the entry point itself launches from: states_per_thread = 1 (2 s_max + 1 <= 1024 states), 2 (<= 2048) or 4; threads = the workgroup size,
+ * round_up(ceil((2 s_max + 1) / states_per_thread), 64); lse_in_lds = 1 when the per-frame log-sum-exp row sits in LDS next to the state rows
+ * (160 KiB: about 38 000 frames), 0 when it is read back from global memory; lds_bytes = the dynamic LDS (above 64 KiB the kernel is opted in).
+ * The time dimension of the TENSOR selects the configuration, not input_len.  Host code only: no launch, no stream, no device call.
+ * TS_EINVAL for n_frames <= 0, s_max < 0 or a NULL argument; TS_EUNSUPPORTED for s_max > 2047, exactly as ts_ctc_loss.
+ * Length rule (ABI v14 fixes the loss for s_max == 0): every kernel reads clamp(target_len[b], 0, s_max) labels; the mean loss and the gradient
+ * both divide by that count clamped to at least 1, i.e. by clamp(target_len[b], 1, max(s_max, 1)). */
+int ts_ctc_launch_config(int32_t n_frames, int32_t s_max, int32_t* states_per_thread, int32_t* threads, int32_t* lse_in_lds, int32_t* lds_bytes);
 /* Targets and lengths in the forms F.ctc_loss takes them (ctc_loss.py:36-47: padded [B][s_in] labels, int32 (kind 0) or int64 (1), row
  * stride targets_stride; lengths int32 / int64 / float32 / float64 (kind 0..3), truncated toward zero like the reference's `.long()`)
  * -> the int32 arrays ts_ctc_loss reads: targets_out [B][s_max] (s_max >= max(s_in, 1)) with positions >= length and ids outside

@@ -295,7 +295,8 @@ __global__ void ctc_mean_kernel(const float* nll, const int* target_len, int bat
   float s = 0.f;
   for (int b = threadIdx.x; b < batch; b += 64) {
     int S = target_len[b];
-    S = S < 1 ? 1 : (S > s_max ? s_max : S);
+    S = S > s_max ? s_max : S;                     // the labels ctc_kernel reads, then clamp(., 1): [1, max(s_max, 1)], as ctc_grad_kernel's scale
+    S = S < 1 ? 1 : S;
     s += nll[b] / (float)S;
   }
   for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
@@ -306,6 +307,38 @@ __global__ void ctc_mean_kernel(const float* nll, const int* target_len, int bat
 
 static int ctc_states_per_thread(int lmax) { return lmax <= 1024 ? 1 : (lmax <= 2048 ? 2 : 4); }
 static int ctc_threads(int lmax) { const int spt = ctc_states_per_thread(lmax); return ((lmax + spt - 1) / spt + 63) / 64 * 64; }
+
+// What ts_ctc_loss launches ctc_kernel with, as a function of the tensor's time dimension and the label capacity alone: the instantiation
+// (states per thread, log-sum-exp row in LDS or read back from global memory), the workgroup size and the dynamic LDS.  ts_ctc_loss launches from
+// this and ts_ctc_launch_config reports it.
+struct CtcLaunch {
+  int spt, threads;
+  bool lse_lds;
+  size_t lds;
+};
+static int ctc_launch_config(int n_frames, int s_max, CtcLaunch* c) {
+  if (n_frames <= 0 || s_max < 0) return TS_EINVAL;
+  if (s_max > 2047) return TS_EUNSUPPORTED;                                                        // more than 2 047 labels in a transcript
+  const int lmax = 2 * s_max + 1;
+  c->spt = ctc_states_per_thread(lmax);
+  c->threads = ctc_threads(lmax);
+  c->lds = ((size_t)2 * (lmax + 4) + lmax + (size_t)n_frames) * sizeof(float);
+  // the per-frame log-sum-exp row lives in LDS next to the two state rows: 160 KiB hold about 38 000 frames (a 12-minute clip after the stem);
+  // longer clips take the instantiation that reads the row back from its global copy
+  c->lse_lds = c->lds <= 160 * 1024;
+  if (!c->lse_lds) c->lds = ((size_t)2 * (lmax + 4) + lmax) * sizeof(float);
+  return c->lds > 160 * 1024 ? TS_EUNSUPPORTED : TS_OK;
+}
+
+extern "C" int ts_ctc_launch_config(int32_t n_frames, int32_t s_max, int32_t* states_per_thread, int32_t* threads, int32_t* lse_in_lds,
+                                    int32_t* lds_bytes) {
+  if (!states_per_thread || !threads || !lse_in_lds || !lds_bytes) return TS_EINVAL;
+  CtcLaunch c{};
+  const int st = ctc_launch_config(n_frames, s_max, &c);
+  if (st != TS_OK) return st;
+  *states_per_thread = c.spt; *threads = c.threads; *lse_in_lds = c.lse_lds ? 1 : 0; *lds_bytes = (int32_t)c.lds;
+  return TS_OK;
+}
 
 extern "C" int64_t ts_ctc_workspace_bytes(int32_t batch, int32_t n_classes, int32_t n_frames, int32_t s_max) {
   (void)n_classes;
@@ -329,22 +362,22 @@ extern "C" int ts_ctc_loss(const float* logits, int32_t batch, int32_t n_classes
   a.lse = static_cast<float*>(workspace);
   a.batch = batch; a.n_classes = n_classes; a.n_frames = n_frames; a.pitch = pitch; a.s_max = s_max;
   a.lmax = 2 * s_max + 1; a.blank = blank;
-  const int spt = ctc_states_per_thread(a.lmax);
-  a.rowp = spt * ctc_threads(a.lmax);
+  CtcLaunch cfg{};
+  const int cst = ctc_launch_config(n_frames, s_max, &cfg);
+  if (cst != TS_OK) return cst;
+  const int spt = cfg.spt;
+  a.rowp = spt * cfg.threads;
   a.alpha = a.lse + (size_t)batch * n_frames;
   a.lse2 = a.alpha + (size_t)batch * (n_frames + 1) * a.rowp;
   a.beta = a.lse2 + (size_t)batch * n_frames;
   a.feasible = reinterpret_cast<int*>(a.beta + (size_t)batch * (n_frames + 1) * a.rowp);
-  size_t lds = ((size_t)2 * (a.lmax + 4) + a.lmax + (size_t)n_frames) * sizeof(float);
+  const size_t lds = cfg.lds;
   const size_t lds_g = ((size_t)a.lmax + 4 * (size_t)n_classes) * sizeof(float);
-  // the per-frame log-sum-exp row lives in LDS next to the two state rows: 160 KiB hold about 38 000 frames (a 12-minute clip after the stem);
-  // longer clips take the instantiation that reads the row back from its global copy
-  const bool lse_lds = lds <= 160 * 1024;
-  if (!lse_lds) lds = ((size_t)2 * (a.lmax + 4) + a.lmax) * sizeof(float);
-  if (lds > 160 * 1024 || lds_g > 64 * 1024 || a.lmax > 4096) return TS_EUNSUPPORTED;            // more than 2 047 labels in a transcript
+  const bool lse_lds = cfg.lse_lds;
+  if (lds_g > 64 * 1024) return TS_EUNSUPPORTED;
   (void)hipGetLastError();
   const dim3 grid(batch, grad ? 2 : 1);                                                          // alpha || beta
-  const dim3 block((unsigned)ctc_threads(a.lmax));
+  const dim3 block((unsigned)cfg.threads);
   static bool big_all[64][3] = {};                                                               // more than the default 64 KiB allowed: per (device, instantiation)
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return TS_EINVAL;

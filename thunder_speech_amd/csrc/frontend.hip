@@ -399,52 +399,40 @@ extern "C" const float* ts_frontend_logmel_ptr(const ts_frontend_desc* d, const 
   return static_cast<const float*>(workspace);
 }
 
-extern "C" int ts_mel_frontend_fwd(const ts_frontend_desc* d, const float* wave, const int32_t* wave_len, void* features,
-                                   int32_t* feat_len, void* workspace, void* stream_) {
+// What ts_mel_frontend_fwd launches stft_mel_kernel with: every check of the descriptor, the dynamic LDS, the instantiation and the persistent grid
+// (as many workgroups as are resident at once -- LDS allows three per CU; the dither instantiation's registers only two, a third would start when
+// the first two have finished their share -- each walking frame groups g, g + grid, ...).  ts_mel_frontend_fwd launches from this and
+// ts_frontend_launch_config reports it.  Reads the device's properties and the occupancy query; changes nothing, launches nothing, touches no stream.
+namespace ts {
+struct FeLaunch {
+  int nwg, n_groups, grid, dither;
+  size_t lds1;
+};
+}  // namespace ts
+static int fe_launch_config(const ts_frontend_desc* d, ts::FeLaunch* c) {
   using namespace ts;
-  if (!d || !wave || !wave_len || !features || !feat_len || !workspace) return TS_EINVAL;
   if (!d->window || !d->mel_weights || !d->mel_offsets) return TS_EINVAL;
   if (d->batch <= 0 || d->n_samples <= NFFT / 2 || d->hop <= 0 || d->n_mels <= 0) return TS_EINVAL;
   if (d->n_fft != NFFT) return TS_EUNSUPPORTED;                    // both model families use n_fft = 512
   if (d->win_length > NFFT || d->win_length <= 0) return TS_EINVAL;  // transform.py:166-170
   if (d->n_frames != d->n_samples / d->hop + 1) return TS_EINVAL;
   if (d->pitch_out % 8 || d->pitch_out < d->n_frames) return TS_EINVAL;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const int nwg = fe_nwg(d);
-
-  FeArgs a{};
-  a.wave = wave; a.wave_len = wave_len; a.window = d->window; a.mel_w = d->mel_weights; a.mel_off = d->mel_offsets;
-  a.logmel = static_cast<float*>(workspace);
-  a.partial = reinterpret_cast<float*>(static_cast<char*>(workspace) + fe_logmel_bytes(d));
-  a.feat_len = feat_len;
-  a.feat_len64 = reinterpret_cast<long long*>(d->feat_len64);
-  a.n_samples = d->n_samples; a.hop = d->hop; a.n_mels = d->n_mels; a.n_frames = d->n_frames; a.nwg = nwg;
-  a.preemph = d->preemph;
-  a.dither = d->dither;
-  a.seed = d->dither_seed;
   if (d->n_masks < 0 || (d->n_masks > 0 && !d->masks)) return TS_EINVAL;
-  a.mel_nnz = d->mel_nnz;
-  a.batch = d->batch;
-  const int span = (FPW - 1) * d->hop + NFFT;
   if (d->mel_nnz < 0) return TS_EINVAL;
   if (d->n_mels > 256) return TS_EUNSUPPORTED;                     // the log-mel staging sits in the upper half of a frame tile
-  const size_t lds1 = ((size_t)round_up(span, 4) + NC * 2 + NFFT + (size_t)FPW * (16 * 17 * 2) +
+  const long long span = (long long)(FPW - 1) * d->hop + NFFT;
+  if (span > 160 * 1024 / 4) return TS_EUNSUPPORTED;
+  const size_t lds1 = ((size_t)round_up((int)span, 4) + NC * 2 + NFFT + (size_t)FPW * (16 * 17 * 2) +
                        (size_t)d->mel_nnz + (size_t)(d->n_mels + 1) * 2) * sizeof(float);
   if (lds1 > 160 * 1024) return TS_EUNSUPPORTED;
-  if (lds1 > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(stft_mel_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(stft_mel_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-    if (e != hipSuccess) return (int)e;
-  }
-  (void)hipGetLastError();
-  // persistent workgroups: as many as are resident at once, each walks frame groups g, g + grid, ...  (LDS allows three per CU; the dither instantiation's
-  // registers only two -- a third would start when the first two have finished their share)
+  // (above 64 KiB the LDS alone allows at most two workgroups per CU, which is also what the dither instantiation's registers allow: the occupancy
+  // query below cannot lower that, whether or not the kernels have been opted in to the larger LDS yet -- ts_mel_frontend_fwd does that)
   int per_cu = (int)((160 * 1024) / lds1) < 1 ? 1 : (int)((160 * 1024) / lds1);
+  const int di = d->dither > 0.f ? 1 : 0;
   {
     static int occ_cache[64][2] = {};          // per (device, instantiation); the query depends on lds1 too, which the two model families share
     static size_t occ_lds[64][2] = {};
     int dev = 0;
-    const int di = a.dither > 0.f ? 1 : 0;
     if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
       if (occ_lds[dev][di] != lds1) {
         int occ = 0;
@@ -456,11 +444,64 @@ extern "C" int ts_mel_frontend_fwd(const ts_frontend_desc* d, const float* wave,
       }
       if (occ_cache[dev][di] < per_cu) per_cu = occ_cache[dev][di];
     }
+    (void)hipGetLastError();
   }
-  const int n_groups = nwg * d->batch;
-  const int grid = n_groups < cu_count() * per_cu ? n_groups : cu_count() * per_cu;
-  if (a.dither > 0.f) hipLaunchKernelGGL(stft_mel_kernel<true>, dim3(grid), dim3(256), lds1, stream, a);
-  else hipLaunchKernelGGL(stft_mel_kernel<false>, dim3(grid), dim3(256), lds1, stream, a);
+  c->nwg = fe_nwg(d);
+  const long long n_groups = (long long)c->nwg * d->batch;
+  if (n_groups > 2147483647LL) return TS_EINVAL;
+  c->n_groups = (int)n_groups;
+  c->grid = c->n_groups < cu_count() * per_cu ? c->n_groups : cu_count() * per_cu;
+  c->dither = di;
+  c->lds1 = lds1;
+  return TS_OK;
+}
+
+extern "C" int ts_frontend_launch_config(const ts_frontend_desc* desc, int32_t* grid, int32_t* n_groups, int32_t* lds_bytes,
+                                         int32_t* dither_instantiation) {
+  if (!desc || !grid || !n_groups || !lds_bytes || !dither_instantiation) return TS_EINVAL;
+  ts::FeLaunch c{};
+  const int st = fe_launch_config(desc, &c);
+  if (st != TS_OK) return st;
+  *grid = c.grid; *n_groups = c.n_groups; *lds_bytes = (int32_t)c.lds1; *dither_instantiation = c.dither;
+  return TS_OK;
+}
+
+extern "C" int ts_mel_frontend_fwd(const ts_frontend_desc* d, const float* wave, const int32_t* wave_len, void* features,
+                                   int32_t* feat_len, void* workspace, void* stream_) {
+  using namespace ts;
+  if (!d || !wave || !wave_len || !features || !feat_len || !workspace) return TS_EINVAL;
+  FeLaunch cfg{};
+  const int cst = fe_launch_config(d, &cfg);
+  if (cst != TS_OK) return cst;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const int nwg = cfg.nwg;
+  const size_t lds1 = cfg.lds1;
+
+  FeArgs a{};
+  a.wave = wave; a.wave_len = wave_len; a.window = d->window; a.mel_w = d->mel_weights; a.mel_off = d->mel_offsets;
+  a.logmel = static_cast<float*>(workspace);
+  a.partial = reinterpret_cast<float*>(static_cast<char*>(workspace) + fe_logmel_bytes(d));
+  a.feat_len = feat_len;
+  a.feat_len64 = reinterpret_cast<long long*>(d->feat_len64);
+  a.n_samples = d->n_samples; a.hop = d->hop; a.n_mels = d->n_mels; a.n_frames = d->n_frames; a.nwg = nwg;
+  a.preemph = d->preemph;
+  a.dither = d->dither;
+  a.seed = d->dither_seed;
+  a.mel_nnz = d->mel_nnz;
+  a.batch = d->batch;
+  if (lds1 > 64 * 1024) {
+    hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(stft_mel_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
+    if (e1 == hipSuccess) e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(stft_mel_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
+    if (e1 != hipSuccess) return (int)e1;
+  }
+  const size_t lds2 = ((size_t)2 * d->n_mels + (size_t)NTF * (d->n_mels + 1)) * sizeof(float);
+  if (lds2 > 64 * 1024) {                                          // n_mels 248 .. 256 (67 840 bytes at 256): beyond the default limit, like lds1 above
+    const hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(normalize_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+    if (e2 != hipSuccess) return (int)e2;
+  }
+  (void)hipGetLastError();
+  if (cfg.dither) hipLaunchKernelGGL(stft_mel_kernel<true>, dim3(cfg.grid), dim3(256), lds1, stream, a);
+  else hipLaunchKernelGGL(stft_mel_kernel<false>, dim3(cfg.grid), dim3(256), lds1, stream, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
 
@@ -468,7 +509,6 @@ extern "C" int ts_mel_frontend_fwd(const ts_frontend_desc* d, const float* wave,
   n.logmel = a.logmel; n.partial = a.partial; n.feat_len = feat_len; n.out = static_cast<unsigned short*>(features);
   n.n_mels = d->n_mels; n.n_frames = d->n_frames; n.nwg = nwg; n.pitch = d->pitch_out;
   n.masks = d->masks; n.n_masks = d->n_masks;
-  const size_t lds2 = ((size_t)2 * d->n_mels + (size_t)NTF * (d->n_mels + 1)) * sizeof(float);
   (void)hipGetLastError();
   hipLaunchKernelGGL(normalize_kernel, dim3((d->pitch_out + NTF - 1) / NTF, d->batch), dim3(256), lds2, stream, n);
   return hip_status(hipGetLastError());
