@@ -1,7 +1,8 @@
 """wav2vec2 fine-tuning on the HIP kernels: the training-mode forward of `transformers.Wav2Vec2Model` as a chain of autograd nodes whose
 forward and backward are C-ABI launches (csrc/gemm_f32.hip for every product, csrc/w2v_train.hip for the rest).  `transformers.WavLMModel`
 trains on the same chain in mixed precision, with its gated relative-position attention on csrc/wavlm_train.hip (WavLMGate, WavLMRelBias,
-WavLMAttentionFused).
+WavLMAttentionFused).  In mixed precision the attention core is fused at head_dim 64 (AttentionFused, csrc/w2v_attn_train.hip) and at head_dim 80
+(AttentionFused80, csrc/mms_train.hip: the XLS-R 1B geometry); every other head dimension, and f32 training, take the materialised Attention node.
 
 The reference fine-tunes HuggingFace CTC checkpoints through `BaseCTCModule.training_step` (src/thunder/module.py:102-127) with the conv feature
 extractor frozen (`_HuggingFaceEncoderAdapt.__init__`, src/thunder/huggingface/compatibility.py:27-28 -> `freeze_feature_encoder()`); autograd
@@ -435,10 +436,42 @@ class Attention(torch.autograd.Function):
         return dqkv, None, None, None, None
 
 
+def _fused_attention_forward(ctx, entry: str, qkv, key_len, heads, p_drop, seed):
+    """Forward of the fused attention nodes on the C-ABI family `entry` (`<entry>_fwd_workspace`, `<entry>_fwd`; the backward: `<entry>_bwd*`)."""
+    qkv = _f32c(qkv)
+    b, t, c3 = qkv.shape
+    c = c3 // 3
+    q16, _ = _cast(qkv.view(b * t, c3), b * t, c3, True, False)
+    out = torch.empty(b, t, c, dtype=torch.float32, device=qkv.device)
+    lse2 = torch.empty(b, heads, t, dtype=torch.float32, device=qkv.device)
+    L = _lib.lib()
+    ws = torch.empty(getattr(L, entry + "_fwd_workspace")(b, t, c, heads), dtype=torch.uint8, device=qkv.device) if p_drop > 0 else None
+    st = getattr(L, entry + "_fwd")(q16.data_ptr(), b, t, c, heads, key_len.data_ptr() if key_len is not None else None, float(p_drop), int(seed),
+                                    out.data_ptr(), lse2.data_ptr(), ws.data_ptr() if ws is not None else None, _s(qkv))
+    _lib.check(st, entry + "_fwd")
+    ctx.save_for_backward(q16, out, lse2, key_len, ws)                       # ws: the mask bits (the backward would re-draw them otherwise)
+    ctx.geom = (b, t, c, heads, float(p_drop), int(seed))
+    return out
+
+
+def _fused_attention_backward(ctx, entry: str, dout):
+    q16, out, lse2, key_len, mask = ctx.saved_tensors
+    b, t, c, heads, p_drop, seed = ctx.geom
+    dout = _f32c(dout)
+    L = _lib.lib()
+    ws = torch.empty(getattr(L, entry + "_bwd_workspace")(b, t, c, heads), dtype=torch.uint8, device=dout.device)
+    dqkv = torch.empty(b, t, 3 * c, dtype=torch.float32, device=dout.device)
+    st = getattr(L, entry + "_bwd")(q16.data_ptr(), b, t, c, heads, key_len.data_ptr() if key_len is not None else None, p_drop, seed, dout.data_ptr(),
+                                    out.data_ptr(), lse2.data_ptr(), mask.data_ptr() if mask is not None else None, dqkv.data_ptr(), ws.data_ptr(), _s(dout))
+    _lib.check(st, entry + "_bwd")
+    return dqkv, None, None, None, None
+
+
 class AttentionFused(torch.autograd.Function):
     """The same attention in mixed precision WITHOUT the [T][T] matrices (csrc/w2v_attn_train.hip; head_dim 64): bf16 q / k / v / dO / probabilities, f32
     softmax arithmetic, accumulation and results; the dropout mask is ts_train_dropout's (same seed -> same mask as `Attention`), re-drawn in the two backward
     kernels; saved for the backward: the bf16 qkv, the f32 output and one f32 per (head, query)."""
+    ENTRY = "ts_w2v_attention_train"
 
     @staticmethod
     def supported(c: int, heads: int) -> bool:
@@ -446,33 +479,29 @@ class AttentionFused(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, key_len, heads, p_drop, seed):
-        qkv = _f32c(qkv)
-        b, t, c3 = qkv.shape
-        c = c3 // 3
-        q16, _ = _cast(qkv.view(b * t, c3), b * t, c3, True, False)
-        out = torch.empty(b, t, c, dtype=torch.float32, device=qkv.device)
-        lse2 = torch.empty(b, heads, t, dtype=torch.float32, device=qkv.device)
-        L = _lib.lib()
-        ws = torch.empty(L.ts_w2v_attention_train_fwd_workspace(b, t, c, heads), dtype=torch.uint8, device=qkv.device) if p_drop > 0 else None
-        st = L.ts_w2v_attention_train_fwd(q16.data_ptr(), b, t, c, heads, key_len.data_ptr() if key_len is not None else None, float(p_drop), int(seed),
-                                          out.data_ptr(), lse2.data_ptr(), ws.data_ptr() if ws is not None else None, _s(qkv))
-        _lib.check(st, "ts_w2v_attention_train_fwd")
-        ctx.save_for_backward(q16, out, lse2, key_len, ws)                       # ws: the mask bits (the backward would re-draw them otherwise)
-        ctx.geom = (b, t, c, heads, float(p_drop), int(seed))
-        return out
+        return _fused_attention_forward(ctx, AttentionFused.ENTRY, qkv, key_len, heads, p_drop, seed)
 
     @staticmethod
     def backward(ctx, dout):
-        q16, out, lse2, key_len, mask = ctx.saved_tensors
-        b, t, c, heads, p_drop, seed = ctx.geom
-        dout = _f32c(dout)
-        L = _lib.lib()
-        ws = torch.empty(L.ts_w2v_attention_train_bwd_workspace(b, t, c, heads), dtype=torch.uint8, device=dout.device)
-        dqkv = torch.empty(b, t, 3 * c, dtype=torch.float32, device=dout.device)
-        st = L.ts_w2v_attention_train_bwd(q16.data_ptr(), b, t, c, heads, key_len.data_ptr() if key_len is not None else None, p_drop, seed, dout.data_ptr(),
-                                          out.data_ptr(), lse2.data_ptr(), mask.data_ptr() if mask is not None else None, dqkv.data_ptr(), ws.data_ptr(), _s(dout))
-        _lib.check(st, "ts_w2v_attention_train_bwd")
-        return dqkv, None, None, None, None
+        return _fused_attention_backward(ctx, AttentionFused.ENTRY, dout)
+
+
+class AttentionFused80(torch.autograd.Function):
+    """AttentionFused at head_dim 80 (XLS-R 1B / MMS geometry: hidden 1280, 16 heads; csrc/mms_train.hip, include/thunder_speech_amd_mms_train.h):
+    the same contract, node shape and saved tensors on the ts_mms_attention_train_* entry points."""
+    ENTRY = "ts_mms_attention_train"
+
+    @staticmethod
+    def supported(c: int, heads: int) -> bool:
+        return c % heads == 0 and c // heads == 80
+
+    @staticmethod
+    def forward(ctx, qkv, key_len, heads, p_drop, seed):
+        return _fused_attention_forward(ctx, AttentionFused80.ENTRY, qkv, key_len, heads, p_drop, seed)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return _fused_attention_backward(ctx, AttentionFused80.ENTRY, dout)
 
 
 class WavLMGate(torch.autograd.Function):
@@ -570,13 +599,15 @@ class WavLMAttentionFused(torch.autograd.Function):
 
 
 MIXED_POSCONV = True        # mixed mode: the positional conv's forward and data gradient on the bf16 matrix-core kernel (False: f32 products, for A/B)
-FUSED_ATTENTION = True      # mixed mode: AttentionFused where it applies (False: the materialised-probabilities path, for A/B)
+FUSED_ATTENTION = True      # mixed mode: AttentionFused / AttentionFused80 where they apply (False: the materialised-probabilities path, for A/B)
 
 
 def attention(qkv: Tensor, key_len, heads: int, p_drop: float, seed: int) -> Tensor:
     """Self-attention of the training path in the current precision mode."""
-    if _MIXED and FUSED_ATTENTION and AttentionFused.supported(qkv.shape[-1] // 3, heads):
-        return AttentionFused.apply(qkv, key_len, heads, p_drop, seed)
+    if _MIXED and FUSED_ATTENTION:
+        for node in (AttentionFused, AttentionFused80):
+            if node.supported(qkv.shape[-1] // 3, heads):
+                return node.apply(qkv, key_len, heads, p_drop, seed)
     return Attention.apply(qkv, key_len, heads, p_drop, seed)
 
 

@@ -3,7 +3,16 @@ adapter_attn_dim 16; 16 x 20 s, bf16 -- eager and graphed, next to the same geom
 the two kernels of csrc/mms.hip at that step's geometry (t = 999 frames):
   ts_mms_attention_fwd     against ts_w2v_attention_fwd on the same head_dim-80 input (which materialises the [t][t] scores)
   ts_mms_attn_adapter_fwd  (adapter + the LayerNorm behind it) against a plain ts_w2v_layernorm_fwd over the same rows, next to its HBM floor
-python tools/bench_mms.py [--batch 16] [--seconds 20] [--layers 48] [--steps 5] [--out FILE.md]"""
+python tools/bench_mms.py [--batch 16] [--seconds 20] [--layers 48] [--steps 5] [--out FILE.md]
+
+--train: mixed-precision fine-tuning steps (train_precision="bf16": training forward, backward of a probe loss, AdamW) at the XLS-R 1B geometry
+without adapters, 8 x 10 s, attention dropout 0.1, with the fused head_dim 80 attention node (huggingface/train.py AttentionFused80,
+csrc/mms_train.hip) and with train.FUSED_ATTENTION = False (the materialised `Attention` node) -- same process, alternating blocks, device events,
+rotated inputs, peak allocated memory of both -- and the per-call times of ts_mms_attention_train_fwd / _bwd at that step's t next to the
+head_dim 64 calls at the same batch, t and heads (c = 1024).
+python tools/bench_mms.py --train [--batch 8] [--seconds 10] [--layers 48] [--steps 10] [--out FILE.md]
+--train-kernels: only issues those launches, for a kernel trace (rocprofv3 --kernel-trace --stats -- python tools/bench_mms.py --train-kernels):
+the four launches of the new path are mt_fwd_kernel, mt_rowdot_kernel, mt_bwd_dq_kernel and mt_bwd_dkv_kernel."""
 import argparse
 import os
 import sys
@@ -92,16 +101,176 @@ def time_adapter(a, t=999, c=1280, ad=16, reps=50):
     return _best_of_blocks(calls, reps), floors, rows
 
 
+def train_model(layers, seed=0):
+    """transformers' Wav2Vec2Model at the XLS-R 1B geometry (pre-LN, layer-norm convs, no adapters), random weights, attention dropout 0.1 and the
+    other dropouts / time masking of tools/bench_wavlm.py's fine-tuning recipe."""
+    import transformers
+    torch.manual_seed(seed)
+    return transformers.Wav2Vec2Model(transformers.Wav2Vec2Config(
+        hidden_size=1280, num_hidden_layers=layers, num_attention_heads=16, intermediate_size=5120, feat_extract_norm="layer",
+        do_stable_layer_norm=True, conv_bias=True, hidden_dropout=0.1, attention_dropout=0.1, activation_dropout=0.1, feat_proj_dropout=0.1,
+        layerdrop=0.0, mask_time_prob=0.05, mask_feature_prob=0.0, vocab_size=32))
+
+
+def graph_nodes(fn):
+    """{autograd node name: count} of the graph behind grad_fn `fn`."""
+    seen, todo, names = set(), [fn], {}
+    while todo:
+        f = todo.pop()
+        if f is None or f in seen:
+            continue
+        seen.add(f)
+        names[type(f).__name__] = names.get(type(f).__name__, 0) + 1
+        todo += [g for g, _ in f.next_functions]
+    return names
+
+
+def time_train_ab(a, rounds=2, n_inputs=3):
+    """ms / step and peak allocated bytes of the fine-tuning step with train.FUSED_ATTENTION on and off: one model, one optimizer, one process;
+    2 warm-up steps per mode, then `rounds` alternating blocks of steps / rounds timed steps per mode between device events; the inputs rotate
+    over `n_inputs` seeded batches.  -> ({mode: [ms / step of each block]}, {mode: bytes}, {mode: node names}, t, timed steps per mode)"""
+    from thunder_speech_amd.huggingface import train as T
+    from thunder_speech_amd.huggingface.encoder import HuggingFaceEncoderAdapt
+    adapt = HuggingFaceEncoderAdapt(train_model(a.layers), mask_input=True, train_precision="bf16").cuda().train()
+    opt = torch.optim.AdamW([p for p in adapt.parameters() if p.requires_grad], lr=1e-5)
+    g = torch.Generator().manual_seed(0)
+    xs = [(0.1 * torch.randn(a.batch, 16000 * a.seconds, generator=g)).cuda() for _ in range(n_inputs)]
+    lengths = torch.full((a.batch,), 16000 * a.seconds, dtype=torch.int64, device="cuda")
+    lengths[-1] = 16000 * a.seconds * 3 // 4                                  # one ragged clip
+    state = dict(probe=None, i=0, nodes=None, t=None)
+
+    def step(walk=False):
+        opt.zero_grad(set_to_none=True)
+        feats, _ = adapt(xs[state["i"] % n_inputs], lengths)
+        state["i"] += 1
+        if state["probe"] is None:
+            state["probe"], state["t"] = torch.randn(feats.shape, generator=g).cuda(), feats.shape[-1]
+        if walk:
+            state["nodes"] = graph_nodes(feats.grad_fn)
+        (feats * state["probe"]).mean().backward()
+        opt.step()
+
+    modes = {"fused (AttentionFused80)": True, "FUSED_ATTENTION = False (Attention)": False}
+    per = max(1, (a.steps + rounds - 1) // rounds)
+    blocks, peak, nodes = {k: [] for k in modes}, {k: 0 for k in modes}, {}
+    old = T.FUSED_ATTENTION
+    try:
+        for k, on in modes.items():
+            T.FUSED_ATTENTION = on
+            for i in range(2):
+                step(walk=i == 0)
+            nodes[k] = state["nodes"]
+        torch.cuda.synchronize()
+        for _ in range(rounds):
+            for k, on in modes.items():
+                T.FUSED_ATTENTION = on
+                # the caching allocator keeps its blocks: emptying it here would put the re-allocations of the block's first step into the timed window
+                torch.cuda.reset_peak_memory_stats()
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(per + 1)]
+                ev[0].record()
+                for i in range(per):
+                    step()
+                    ev[i + 1].record()
+                torch.cuda.synchronize()
+                steps_ms = [ev[i].elapsed_time(ev[i + 1]) for i in range(per)]
+                print(f"  block of {k}: " + " ".join(f"{x:.1f}" for x in steps_ms) + " ms", flush=True)
+                blocks[k].append(sum(steps_ms) / per)
+                peak[k] = max(peak[k], torch.cuda.max_memory_allocated())
+    finally:
+        T.FUSED_ATTENTION = old
+    t = state["t"]
+    del adapt, opt, xs
+    torch.cuda.empty_cache()
+    return blocks, peak, nodes, t, per * rounds
+
+
+def train_attention_calls(a, t, heads=16, p=0.1):
+    """{name: call} of the fused training attention at head_dim 80 and 64, same batch, t and heads; the backward is given the forward's mask, so a
+    forward call is the mask draw + the forward kernel and a backward call is the row-dot, dQ and dKV launches."""
+    from thunder_speech_amd import _lib
+    L = _lib.lib()
+    s = torch.cuda.current_stream().cuda_stream
+    g = torch.Generator().manual_seed(3)
+    calls = {}
+    keep = []
+    for hd, entry in ((80, "ts_mms_attention_train"), (64, "ts_w2v_attention_train")):
+        b, c = a.batch, hd * heads
+        q16 = torch.randn(b, t, 3 * c, generator=g).to(torch.bfloat16).cuda()
+        dout = torch.randn(b, t, c, generator=g).cuda()
+        ctx, lse2, dq = torch.empty(b, t, c, device="cuda"), torch.empty(b, heads, t, device="cuda"), torch.empty(b, t, 3 * c, device="cuda")
+        wf = torch.empty(getattr(L, entry + "_fwd_workspace")(b, t, c, heads), dtype=torch.uint8, device="cuda")
+        wb = torch.empty(getattr(L, entry + "_bwd_workspace")(b, t, c, heads), dtype=torch.uint8, device="cuda")
+        keep.append((q16, dout, ctx, lse2, dq, wf, wb))
+        fwd, bwd = getattr(L, entry + "_fwd"), getattr(L, entry + "_bwd")
+        calls[f"{entry}_fwd (head_dim {hd})"] = (lambda fwd=fwd, q16=q16, b=b, c=c, ctx=ctx, lse2=lse2, wf=wf:
+                                                 fwd(q16.data_ptr(), b, t, c, heads, None, p, 7, ctx.data_ptr(), lse2.data_ptr(), wf.data_ptr(), s))
+        calls[f"{entry}_bwd (head_dim {hd})"] = (lambda bwd=bwd, q16=q16, b=b, c=c, ctx=ctx, lse2=lse2, wf=wf, dout=dout, dq=dq, wb=wb:
+                                                 bwd(q16.data_ptr(), b, t, c, heads, None, p, 7, dout.data_ptr(), ctx.data_ptr(), lse2.data_ptr(),
+                                                     wf.data_ptr(), dq.data_ptr(), wb.data_ptr(), s))
+    return calls, keep
+
+
+def main_train(a):
+    blocks, peak, nodes, t, n = time_train_ab(a)
+    ms = {k: sum(v) / len(v) for k, v in blocks.items()}
+    plain = list(ms)[1]
+    lines = [f"fine-tuning step, train_precision=\"bf16\": {a.batch} x {a.seconds} s (one clip 3/4 long), {a.layers} layers, 1280 hidden / 16 heads (head_dim 80) / "
+             f"5120 FFN, pre-LN, layer-norm convs, no adapters, random weights, t = {t} frames, dropouts 0.1 (attention included), mask_time_prob 0.05; "
+             f"forward + backward + AdamW; one process, 2 warm-up steps per mode, then {n} timed steps per mode in alternating blocks between device "
+             "events, inputs rotated over 3 batches", "",
+             "| attention node | ms/step | blocks | vs FUSED_ATTENTION = False | peak allocated GiB |", "|---|---:|---|---:|---:|"]
+    for k in ms:
+        lines.append(f"| {k} | {ms[k]:.1f} | {' / '.join(f'{x:.1f}' for x in blocks[k])} | {ms[k] / ms[plain]:.3f} | {peak[k] / 2 ** 30:.2f} |")
+    lines += ["", "autograd nodes of one step's graph (name x count):", ""]
+    for k in ms:
+        lines.append(f"- {k}: " + ", ".join(f"{nm} x {cnt}" for nm, cnt in sorted(nodes[k].items())))
+    calls, keep = train_attention_calls(a, t)
+    best = _best_of_blocks(calls, 20)
+    lines += ["", f"fused training attention calls, {a.batch} clips x 16 heads x t = {t}, p = 0.1, the backward given the forward's mask (device events, best of 3 "
+              "blocks of 20); a forward call = mask draw + forward kernel, a backward call = row-dot + dQ + dKV launches:", "",
+              "| entry point | us per call | vs head_dim 64 |", "|---|---:|---:|"]
+    for k, us in best.items():
+        ref = best[k.replace("ts_mms_attention_train", "ts_w2v_attention_train").replace("head_dim 80", "head_dim 64")]
+        lines.append(f"| {k} | {us:.1f} | {us / ref:.3f} |")
+    return lines
+
+
+def main_train_kernels(a, t=499, reps=10):
+    from thunder_speech_amd import _lib
+    calls, keep = train_attention_calls(a, t)
+    for _ in range(reps):
+        for k, f in calls.items():
+            _lib.check(f(), k)
+    torch.cuda.synchronize()
+    print(f"issued {reps} x {list(calls)} at batch {a.batch}, t = {t}")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--batch", type=int, default=16)
-    ap.add_argument("--seconds", type=int, default=20)
+    ap.add_argument("--batch", type=int, default=None, help="default 16 (inference), 8 (--train)")
+    ap.add_argument("--seconds", type=int, default=None, help="default 20 (inference), 10 (--train)")
     ap.add_argument("--layers", type=int, default=48)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps per mode: default 5 (inference), 10 (--train)")
+    ap.add_argument("--train", action="store_true", help="mixed-precision fine-tuning steps, fused attention on and off, instead of inference")
+    ap.add_argument("--train-kernels", action="store_true", help="only issue the training attention launches at t = 499 (for a kernel trace)")
     ap.add_argument("--out", default=None, help="also write the tables (markdown) to this file")
     a = ap.parse_args()
+    training = a.train or a.train_kernels
+    a.batch = a.batch or (8 if training else 16)
+    a.seconds = a.seconds or (10 if training else 20)
+    a.steps = a.steps or (10 if training else 5)
     if not torch.cuda.is_available():
         raise SystemExit("bench_mms: needs an MI355X")
+    if a.train_kernels:
+        return main_train_kernels(a)
+    if a.train:
+        text = "\n".join(main_train(a))
+        print(text)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(text + "\n")
+        return
     rows, t = [], None
     for name, adapters in (("XLS-R 1B geometry (no adapters)", False), ("MMS-1B (adapter_attn_dim 16)", True)):
         r, t = time_model(name, *mms_variant(a.layers, adapters), a)
