@@ -1,6 +1,6 @@
 """ctypes binding of the C ABI declared in include/thunder_speech_amd.h and its companions include/thunder_speech_amd_wavlm.h,
-include/thunder_speech_amd_wavlm_train.h, include/thunder_speech_amd_conformer.h, include/thunder_speech_amd_mms.h and
-include/thunder_speech_amd_mms_train.h.
+include/thunder_speech_amd_wavlm_train.h, include/thunder_speech_amd_conformer.h, include/thunder_speech_amd_mms.h,
+include/thunder_speech_amd_mms_train.h and include/thunder_speech_amd_mms_adapter_train.h.
 
 The header is the only copy of the ABI: `read_header` derives every prototype, struct and TS_* constant from it and
 `lib()` applies the result, so a new entry point needs the header and its .hip definition and nothing here.  A C type
@@ -25,6 +25,7 @@ CONFORMER_HEADER = os.path.join(ROOT, "include", "thunder_speech_amd_conformer.h
 
 MMS_HEADER = os.path.join(ROOT, "include", "thunder_speech_amd_mms.h")                    # fourth companion (MMS / XLS-R 1B), versioned on its own
 MMS_TRAIN_HEADER = os.path.join(ROOT, "include", "thunder_speech_amd_mms_train.h")        # fifth companion (head_dim 80 fine-tuning), versioned on its own
+MMS_ADAPTER_TRAIN_HEADER = os.path.join(ROOT, "include", "thunder_speech_amd_mms_adapter_train.h")    # sixth companion (adapter fine-tuning), versioned on its own
 
 # Parameters and struct fields: these scalars, `[const] <struct>*` as POINTER(struct), every other pointer to one of
 # _POINTEES (const or not, any depth) as c_void_p.  Return types: _RETURNS only.
@@ -94,6 +95,8 @@ MMS_SIGNATURES, _, MMS_DEFINES = _read_installed_header(MMS_HEADER)
 MMS_ABI_VERSION = MMS_DEFINES["TS_MMS_ABI_VERSION"]
 MMS_TRAIN_SIGNATURES, _, MMS_TRAIN_DEFINES = _read_installed_header(MMS_TRAIN_HEADER)
 MMS_TRAIN_ABI_VERSION = MMS_TRAIN_DEFINES["TS_MMS_TRAIN_ABI_VERSION"]
+MMS_ADAPTER_TRAIN_SIGNATURES, _, MMS_ADAPTER_TRAIN_DEFINES = _read_installed_header(MMS_ADAPTER_TRAIN_HEADER)
+MMS_ADAPTER_TRAIN_ABI_VERSION = MMS_ADAPTER_TRAIN_DEFINES["TS_MMS_ADAPTER_TRAIN_ABI_VERSION"]
 TcsDesc, FrontendDesc, WgradItem = STRUCTS["ts_tcs_desc"], STRUCTS["ts_frontend_desc"], STRUCTS["ts_wgrad_item"]
 TcsLaunch = STRUCTS["ts_tcs_launch"]
 EXPORTED_SYMBOLS = list(SIGNATURES)
@@ -123,11 +126,11 @@ def lib() -> C.CDLL:
     import torch  # noqa: F401  -- must initialise its bundled HIP runtime BEFORE our code object is loaded
     L = C.CDLL(path)
     missing = [s for s in EXPORTED_SYMBOLS + list(WAVLM_SIGNATURES) + list(WAVLM_TRAIN_SIGNATURES) + list(CONFORMER_SIGNATURES) + list(MMS_SIGNATURES) +
-               list(MMS_TRAIN_SIGNATURES) if not hasattr(L, s)]
+               list(MMS_TRAIN_SIGNATURES) + list(MMS_ADAPTER_TRAIN_SIGNATURES) if not hasattr(L, s)]
     if missing:
         raise RuntimeError(f"thunder_speech_amd: {path} does not export {missing}; rebuild it")
     for name, (restype, argtypes) in {**SIGNATURES, **WAVLM_SIGNATURES, **WAVLM_TRAIN_SIGNATURES, **CONFORMER_SIGNATURES, **MMS_SIGNATURES,
-                                      **MMS_TRAIN_SIGNATURES}.items():
+                                      **MMS_TRAIN_SIGNATURES, **MMS_ADAPTER_TRAIN_SIGNATURES}.items():
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     if L.ts_abi_version() != ABI_VERSION:
@@ -148,6 +151,9 @@ def lib() -> C.CDLL:
     if L.ts_mms_train_abi_version() != MMS_TRAIN_ABI_VERSION:
         raise RuntimeError(f"thunder_speech_amd: {path} reports MMS training ABI {L.ts_mms_train_abi_version()}, the header {MMS_TRAIN_HEADER} "
                            f"declares {MMS_TRAIN_ABI_VERSION}; rebuild it")
+    if L.ts_mms_adapter_train_abi_version() != MMS_ADAPTER_TRAIN_ABI_VERSION:
+        raise RuntimeError(f"thunder_speech_amd: {path} reports MMS adapter training ABI {L.ts_mms_adapter_train_abi_version()}, the header "
+                           f"{MMS_ADAPTER_TRAIN_HEADER} declares {MMS_ADAPTER_TRAIN_ABI_VERSION}; rebuild it")
     _lib = L
     return L
 

@@ -1,7 +1,9 @@
 // What MMS (facebook/mms-1b-*) and XLS-R 1B need beyond the wav2vec2 launches (include/thunder_speech_amd_mms.h):
 //   ts_mms_attention_fwd     the fused attention core at head_dim 80 (hidden 1280, 16 heads): mms_flash_attn_kernel
 //   ts_mms_attn_adapter_fwd  h += W2 relu(W1 LN(h) + b1) + b2 in place on the residual stream, with the LayerNorm that follows it: mms_adapter_kernel
+// adapter_launch (declared in mms_adapter_rows.hpp) is that kernel's launcher, also used by ts_mms_attn_adapter_train_fwd (csrc/mms_adapter_train.hip).
 #include "attn_tile.hpp"
+#include "mms_adapter_rows.hpp"
 #include "thunder_speech_amd_mms.h"
 
 namespace ts {
@@ -143,55 +145,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The attention adapter with the LayerNorm behind it.  Workgroup = 16 rows, NW waves; the row tile lives in registers, split by columns: the
-// columns come in chunks of 16, wave w owns chunks w NQ .. w NQ + NQ - 1, and lane (row = lane & 15, g = lane >> 4) holds columns
-// 16 q + 4 g .. + 3 of its row for each of them (one f32x4 per chunk).  That is the accumulator layout of a 16 x 16 MFMA whose N index is the row
-// and whose M index is the column, so both products run on the matrix cores without moving the tile:
-//   z[row][j]   = sum_col LN(h)[row][col] W1[j][col]   A = LN(h) (M = row), B = W1 (N = j), contraction over the lane's own columns -- the
-//                                                      order of a contraction is free, so a k-step is simply the next 32 (bf16) / 4 (f32)
-//                                                      columns the lanes hold; every wave sums its own columns, the NW partial sums meet in LDS
-//   h^T[col][row] += sum_j W2[col][j] relu(z + b1)[row][j]   A = W2 (M = col), B = relu(z)^T (N = row), C = the tile itself
-// precision 1: v_mfma_f32_16x16x32_bf16 (a = 16 fills half a k-step: the other half is zeros); precision 0: v_mfma_f32_16x16x4_f32.
+// The attention adapter with the LayerNorm behind it.  The tile layout, the two matrix-core products and the LayerNorm statistics are
+// csrc/mms_adapter_rows.hpp's (shared with the adapter's backward, csrc/mms_adapter_train.hip).
 // Every weight is read once per workgroup (from L2) for its 16 rows: 2 a c / 16 values per row next to the row's own 2 c.
-// The LayerNorm statistics (mean, then the centred sum of squares, as w2v_layernorm_kernel) go lane -> row's 4 lanes -> the NW waves through LDS.
+// p.in: the rows are read from there and written to p.h (the training forward, which keeps its input); NULL: in place on p.h.
 // ---------------------------------------------------------------------------------------------------------------------
-struct AdArgs {
-  float* h;
-  long long rows;
-  int c, a;
-  const float *norm_w, *norm_b, *b1, *b2, *next_w, *next_b;
-  const void *w1, *w2;
-  float next_eps;
-  float* y_next;
-  unsigned short* y_next16;
-};
-
-constexpr int AD_WAVES = 4;    // waves per SIMD the register budget is set for: the launch is bound by memory, the resident workgroups overlap their phases
-// The chunk loops are fully unrolled (the tile is a register array) and the scheduler would hoist every chunk's weight loads to the top: twice the
-// tile in registers.  A scheduling fence every 4 chunks keeps 4 chunks' loads in flight and the rest of the budget for the tile.
-#define AD_FENCE __builtin_amdgcn_sched_barrier(0)
-// 16 wait states: more than the 11 an 8-pass MFMA's result needs before a vector / LDS / memory instruction may read it
-#define AD_MFMA_DRAIN                               \
-  do {                                              \
-    __builtin_amdgcn_sched_barrier(0);              \
-    asm volatile("s_nop 15" ::: "memory");          \
-    __builtin_amdgcn_sched_barrier(0);              \
-  } while (0)
-constexpr int AD_ZP = 68;      // floats per row of a wave's partial z tile (64 + 4)
-
-// sum of `v` over the whole row (all columns, all waves), in every lane of the row; red = [NW][16] floats of its own per call
-template <int NW>
-__device__ __forceinline__ float ad_row_sum(float v, float* red, int wave, int rl, int g) {
-  v += __shfl_xor(v, 16);
-  v += __shfl_xor(v, 32);
-  if (g == 0) red[wave * 16 + rl] = v;
-  __syncthreads();
-  float s = 0.f;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) s += red[w * 16 + rl];
-  return s;
-}
-
 template <int NQ, int NW, bool BF>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(AD_WAVES, AD_WAVES))) void mms_adapter_kernel(const AdArgs p) {
   __shared__ float red[4][NW * 16];
@@ -201,123 +159,44 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(AD_WAVE
   const int rl = lane & 15, g = lane >> 4;
   const long long row = (long long)blockIdx.x * 16 + rl;
   const bool row_ok = row < p.rows;
-  float* hr = p.h + (row_ok ? row : p.rows - 1) * p.c;          // rows past the end: the last row again, never stored
+  const long long row_off = (row_ok ? row : p.rows - 1) * p.c;  // rows past the end: the last row again, never stored
+  float* hr = p.h + row_off;
   const int c = p.c, a = p.a;
   const int col0 = 16 * wave * NQ + 4 * g;                      // the lane's columns of chunk i: col0 + 16 i + 0..3
   f32x4 v[NQ];
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < NQ; ++i) {
-    const int col = col0 + 16 * i;
-    v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (col < c) v[i] = *reinterpret_cast<const f32x4*>(hr + col);
-    s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-  }
-  const float mu = ad_row_sum<NW>(s, red[0], wave, rl, g) / c;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < NQ; ++i)
-    if (col0 + 16 * i < c) {
-      const f32x4 d = v[i] - mu;
-      q += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
-    }
-  const float rs = rsqrtf(ad_row_sum<NW>(q, red[1], wave, rl, g) / c + 1e-5f);
+  float mu, rs;
+  ad_load_stats<NQ, NW>(p.in ? p.in + row_off : hr, c, col0, v, red[0], red[1], wave, rl, g, mu, rs);
 
-  // LN(h) of chunk i, 0 outside the row
-  auto xhat = [&](int i) -> f32x4 {
-    const int col = col0 + 16 * i;
-    if (col >= c) return f32x4{0.f, 0.f, 0.f, 0.f};
-    const f32x4 w4 = *reinterpret_cast<const f32x4*>(p.norm_w + col), b4 = *reinterpret_cast<const f32x4*>(p.norm_b + col);
-    return (v[i] - mu) * rs * w4 + b4;
-  };
-
-  // ---- z = LN(h) W1^T: this wave's columns, 16 outputs j at a time; the partial tile goes to zp[wave][row][j]
-  for (int na = 0; na < a / 16; ++na) {
-    const int j = 16 * na + rl;                                  // B operand: this lane's W1 row
-    f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
-    if constexpr (BF) {
-      const unsigned short* w1r = static_cast<const unsigned short*>(p.w1) + (size_t)j * c;
-#pragma unroll
-      for (int i = 0; i < NQ; i += 2) {
-        if (16 * (wave * NQ + i) >= c) break;                    // uniform: the wave's columns end here
-        const f32x4 x0 = xhat(i), x1 = xhat(i + 1);
-        const s16x8 af = __builtin_bit_cast(s16x8, uint4{pack_bf16(x0[0], x0[1]), pack_bf16(x0[2], x0[3]), pack_bf16(x1[0], x1[1]), pack_bf16(x1[2], x1[3])});
-        const int ca = col0 + 16 * i, cb = ca + 16;
-        const uint2 wa = ca < c ? *reinterpret_cast<const uint2*>(w1r + ca) : uint2{0u, 0u};
-        const uint2 wb = cb < c ? *reinterpret_cast<const uint2*>(w1r + cb) : uint2{0u, 0u};
-        z = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, __builtin_bit_cast(s16x8, uint4{wa.x, wa.y, wb.x, wb.y}), z, 0, 0, 0);
-        if (i % 4 == 2 && i + 2 < NQ) AD_FENCE;
-      }
-    } else {
-      const float* w1r = static_cast<const float*>(p.w1) + (size_t)j * c;
-#pragma unroll
-      for (int i = 0; i < NQ; ++i) {
-        if (16 * (wave * NQ + i) >= c) break;
-        const f32x4 x0 = xhat(i);
-        const int ca = col0 + 16 * i;
-        const f32x4 w4 = ca < c ? *reinterpret_cast<const f32x4*>(w1r + ca) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int r = 0; r < 4; ++r) z = __builtin_amdgcn_mfma_f32_16x16x4f32(x0[r], w4[r], z, 0, 0, 0);
-        if (i % 4 == 3 && i + 1 < NQ) AD_FENCE;
-      }
-    }
-    // The last MFMA of the chain must have retired before the LDS store reads its result.  Measured without this wait: exactly the last
-    // k-step's contribution was missing from z (one-hot weights, c = 160) -- the compiler had put no wait states between that MFMA and the store.
-    // Seen with hipcc of ROCm 7.2.0 (HIP 7.2.26015, AMD clang 22.0.0git roc-7.2.0): the MFMA ends one basic block, the store opens the next.
-    AD_MFMA_DRAIN;
-    // accumulator register r of lane (n = rl, g): row 4 g + r, output j = 16 na + rl
-#pragma unroll
-    for (int r = 0; r < 4; ++r) zp[wave][4 * g + r][16 * na + rl] = z[r];
-  }
+  // ---- z = LN(h) W1^T: this wave's columns; the partial tile goes to zp[wave][row][j]
+  ad_prod_in<NQ, NW, BF, false>([&](int i) { return ad_xhat(v[i], col0 + 16 * i, c, mu, rs, p.norm_w, p.norm_b); }, p.w1, c, a, wave, rl, g, col0, zp);
   __syncthreads();
   // relu(z + b1)[row][j], summed over the waves in a fixed order
   auto zval = [&](int j) -> float {
     if (j >= a) return 0.f;
-    float t = p.b1[j];
-#pragma unroll
-    for (int w = 0; w < NW; ++w) t += zp[w][rl][j];
-    return fmaxf(t, 0.f);
+    return fmaxf(ad_zsum<NW>(zp, p.b1[j], rl, j), 0.f);
   };
 
   // ---- h^T += W2 relu(z)^T, chunk by chunk; then + b2
   if constexpr (BF) {
-    s16x8 zb[2];                                                 // B operand of k-step ks: j = 32 ks + 8 g + 0..7 of this lane's row
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      float e[8];
-#pragma unroll
-      for (int x = 0; x < 8; ++x) e[x] = zval(32 * ks + 8 * g + x);
-      zb[ks] = __builtin_bit_cast(s16x8, uint4{pack_bf16(e[0], e[1]), pack_bf16(e[2], e[3]), pack_bf16(e[4], e[5]), pack_bf16(e[6], e[7])});
-    }
+    s16x8 zb[2];
+    ad_out_b(zval, g, zb);
     const unsigned short* w2 = static_cast<const unsigned short*>(p.w2);
 #pragma unroll
     for (int i = 0; i < NQ; ++i) {
       const int cm = 16 * (wave * NQ + i) + rl;                  // A operand: this lane's W2 row (= output column)
       if (cm - rl >= c) break;                                   // uniform
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        if (32 * ks >= a) break;
-        const int j = 32 * ks + 8 * g;
-        const uint4 wf = (cm < c && j < a) ? *reinterpret_cast<const uint4*>(w2 + (size_t)cm * a + j) : uint4{0u, 0u, 0u, 0u};
-        v[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(s16x8, wf), zb[ks], v[i], 0, 0, 0);
-      }
+      v[i] = ad_out_chunk<false>(v[i], w2, cm, c, a, g, zb);
       if (i % 4 == 3 && i + 1 < NQ) AD_FENCE;
     }
   } else {
-    float zf[16];                                                // B operand of k-step sidx: j = 4 sidx + g
-#pragma unroll
-    for (int sidx = 0; sidx < 16; ++sidx) zf[sidx] = zval(4 * sidx + g);
+    float zf[16];
+    ad_out_b(zval, g, zf);
     const float* w2 = static_cast<const float*>(p.w2);
 #pragma unroll
     for (int i = 0; i < NQ; ++i) {
       const int cm = 16 * (wave * NQ + i) + rl;
       if (cm - rl >= c) break;
-      const float* w2r = w2 + (size_t)(cm < c ? cm : c - 1) * a + g;
-#pragma unroll
-      for (int sidx = 0; sidx < 16; ++sidx) {
-        if (4 * sidx >= a) break;
-        v[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(cm < c ? w2r[4 * sidx] : 0.f, zf[sidx], v[i], 0, 0, 0);
-      }
+      v[i] = ad_out_chunk<false>(v[i], w2, cm, c, a, g, zf);
       if (i % 4 == 3 && i + 1 < NQ) AD_FENCE;
     }
   }
@@ -377,22 +256,9 @@ extern "C" int ts_mms_attention_fwd(const void* qkv, int32_t batch, int32_t t, i
   return hip_status(hipGetLastError());
 }
 
-extern "C" int ts_mms_attn_adapter_fwd(float* h, int64_t rows, int32_t c, int32_t a, const float* norm_w, const float* norm_b, const void* w1,
-                                       const float* b1, const void* w2, const float* b2, const float* next_w, const float* next_b, float next_eps,
-                                       float* y_next, void* y_next_op, int32_t precision, void* stream_) {
-  if (!h || !norm_w || !norm_b || !w1 || !b1 || !w2 || !b2 || rows <= 0 || c <= 0 || a <= 0) return TS_EINVAL;
-  if (next_w && (!next_b || (!y_next && !y_next_op))) return TS_EINVAL;
-  if (a % 16 || a > 64 || c % 8 || c > 4096 || precision < 0 || precision > 1 || (y_next_op && !precision)) return TS_EUNSUPPORTED;
-  if (misaligned(h) || misaligned(norm_w) || misaligned(norm_b) || misaligned(w1) || misaligned(b1) || misaligned(w2) || misaligned(b2) ||
-      misaligned(next_w) || misaligned(next_b) || misaligned(y_next) || misaligned(y_next_op, 7))
-    return TS_EUNSUPPORTED;
-  if ((rows + 15) / 16 > 0x7fffffffLL) return TS_EUNSUPPORTED;
-  TS_STREAM;
-  AdArgs p{};
-  p.h = h; p.rows = rows; p.c = c; p.a = a; p.norm_w = norm_w; p.norm_b = norm_b; p.b1 = b1; p.b2 = b2; p.w1 = w1; p.w2 = w2;
-  p.next_w = next_w; p.next_b = next_b; p.next_eps = next_eps;
-  p.y_next = next_w ? y_next : nullptr; p.y_next16 = next_w ? static_cast<unsigned short*>(y_next_op) : nullptr;
-  const dim3 grid((unsigned)((rows + 15) / 16));
+int ts::adapter_launch(const AdArgs& p, int precision, hipStream_t stream) {
+  const int c = p.c;
+  const dim3 grid((unsigned)((p.rows + 15) / 16));
 #define TS_AD(NQ_, NW_)                                                                                              \
   do {                                                                                                               \
     if (precision) hipLaunchKernelGGL((mms_adapter_kernel<NQ_, NW_, true>), grid, dim3(NW_ * 64), 0, stream, p);     \
@@ -409,4 +275,22 @@ extern "C" int ts_mms_attn_adapter_fwd(float* h, int64_t rows, int32_t c, int32_
   else TS_AD(16, 16);
 #undef TS_AD
   return hip_status(hipGetLastError());
+}
+
+extern "C" int ts_mms_attn_adapter_fwd(float* h, int64_t rows, int32_t c, int32_t a, const float* norm_w, const float* norm_b, const void* w1,
+                                       const float* b1, const void* w2, const float* b2, const float* next_w, const float* next_b, float next_eps,
+                                       float* y_next, void* y_next_op, int32_t precision, void* stream_) {
+  if (!h || !norm_w || !norm_b || !w1 || !b1 || !w2 || !b2 || rows <= 0 || c <= 0 || a <= 0) return TS_EINVAL;
+  if (next_w && (!next_b || (!y_next && !y_next_op))) return TS_EINVAL;
+  if (a % 16 || a > 64 || c % 8 || c > 4096 || precision < 0 || precision > 1 || (y_next_op && !precision)) return TS_EUNSUPPORTED;
+  if (misaligned(h) || misaligned(norm_w) || misaligned(norm_b) || misaligned(w1) || misaligned(b1) || misaligned(w2) || misaligned(b2) ||
+      misaligned(next_w) || misaligned(next_b) || misaligned(y_next) || misaligned(y_next_op, 7))
+    return TS_EUNSUPPORTED;
+  if ((rows + 15) / 16 > 0x7fffffffLL) return TS_EUNSUPPORTED;
+  TS_STREAM;
+  AdArgs p{};
+  p.h = h; p.rows = rows; p.c = c; p.a = a; p.norm_w = norm_w; p.norm_b = norm_b; p.b1 = b1; p.b2 = b2; p.w1 = w1; p.w2 = w2;
+  p.next_w = next_w; p.next_b = next_b; p.next_eps = next_eps;
+  p.y_next = next_w ? y_next : nullptr; p.y_next16 = next_w ? static_cast<unsigned short*>(y_next_op) : nullptr;
+  return adapter_launch(p, precision, stream);
 }

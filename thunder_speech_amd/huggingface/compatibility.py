@@ -72,7 +72,11 @@ def load_huggingface_checkpoint(model_name: str, target_lang: Optional[str] = No
     `target_lang` (MMS: "facebook/mms-1b-all" and its kin) selects one language of a multilingual checkpoint: transformers loads that
     language's `adapter.<lang>.safetensors` (attention adapters and lm_head, which it resizes: `ignore_mismatched_sizes=True` unless the caller
     set it) and the tokenizer takes that language's entry of the nested vocab.json, so the decoder and text_transform are that language's.
-    Another language needs another module: load the checkpoint again."""
+    Another language needs another module: load the checkpoint again.
+
+    Teaching such a checkpoint a new language trains the attention adapters and the CTC head on the frozen base:
+        module = load_huggingface_checkpoint(dir, target_lang=...)
+        adapters = module.encoder.adapter_finetuning(init=True)     # {name: parameter}; optimise these and module.decoder.parameters()"""
     from transformers import AutoFeatureExtractor, AutoModelForCTC, AutoTokenizer
     tokenizer_kwargs = {}
     if target_lang is not None:

@@ -534,6 +534,37 @@ class HuggingFaceEncoderAdapt(nn.Module):
         sd = {"feature_extractor." + k: v for k, v in fe.state_dict().items()}
         return self._fe_cache.get(params, lambda: Wav2Vec2Plan(self.original_encoder.config, sd, device, self.precision, feature_extractor_only=True))
 
+    def adapter_finetuning(self, init: bool = False) -> Dict[str, nn.Parameter]:
+        """Put an MMS checkpoint (config.adapter_attn_dim) into the adapter-only fine-tuning regime, transformers' recipe for a new language:
+        `init=True` re-initialises the attention adapters (the encoder's own `init_adapter_layers()`, and its Linear / LayerNorm initialisation
+        for the adapters' children, which that call does not reach), every encoder parameter is frozen and the
+        adapter layers' parameters are made trainable.  Returns those, {name: parameter}, named as in `state_dict()` (under `original_encoder.`);
+        hand them and the CTC head (the module's `decoder`) to the optimizer.  Train mode then runs huggingface/train.py with the fused adapter
+        node; with any base parameter trainable it refuses by name."""
+        enc = self.original_encoder
+        if not has_attn_adapters(enc.config):
+            raise ValueError("adapter_finetuning: the checkpoint has no attention adapters (config.adapter_attn_dim is None, or the layers are post-LN)")
+        if init:
+            enc.init_adapter_layers()
+            # transformers hands each Wav2Vec2AttnAdapterLayer itself to _init_weights, which knows Linear and LayerNorm but not that container: its
+            # children keep their values.  Give them what _init_weights gives those two types, so that a new language starts from fresh adapters
+            with torch.no_grad():
+                for layer in enc.encoder.layers:
+                    ad = layer.adapter_layer
+                    for lin in (ad.linear_1, ad.linear_2):
+                        lin.weight.normal_(mean=0.0, std=float(enc.config.initializer_range))
+                        lin.bias.zero_()
+                    ad.norm.weight.fill_(1.0)
+                    ad.norm.bias.zero_()
+        for p in enc.parameters():
+            p.requires_grad_(False)
+        out = {}
+        for name, p in enc.named_parameters():
+            if ".adapter_layer." in name:
+                p.requires_grad_(True)
+                out["original_encoder." + name] = p
+        return out
+
     def forward(self, audio: torch.Tensor, audio_lengths: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         if self.training and getattr(self.original_encoder.config, "model_type", "wav2vec2") == "wav2vec2-conformer":
             # no conformer backward exists (BatchNorm in train mode, the depthwise conv, the rotary products): refused before any device work

@@ -3,6 +3,8 @@ forward and backward are C-ABI launches (csrc/gemm_f32.hip for every product, cs
 trains on the same chain in mixed precision, with its gated relative-position attention on csrc/wavlm_train.hip (WavLMGate, WavLMRelBias,
 WavLMAttentionFused).  In mixed precision the attention core is fused at head_dim 64 (AttentionFused, csrc/w2v_attn_train.hip) and at head_dim 80
 (AttentionFused80, csrc/mms_train.hip: the XLS-R 1B geometry); every other head dimension, and f32 training, take the materialised Attention node.
+MMS checkpoints (config.adapter_attn_dim) train adapter-only: the base frozen (HuggingFaceEncoderAdapt.adapter_finetuning), the attention adapter
+behind every layer one fused node (AttnAdapter, csrc/mms_adapter_train.hip).
 
 The reference fine-tunes HuggingFace CTC checkpoints through `BaseCTCModule.training_step` (src/thunder/module.py:102-127) with the conv feature
 extractor frozen (`_HuggingFaceEncoderAdapt.__init__`, src/thunder/huggingface/compatibility.py:27-28 -> `freeze_feature_encoder()`); autograd
@@ -275,6 +277,47 @@ class LayerNorm(torch.autograd.Function):
                                         dx.data_ptr(), dg.data_ptr(), db.data_ptr(), ws.data_ptr(), _s(x))        # dgamma / dbeta written: no fill launches, one reduce
         _lib.check(st, "ts_w2v_layernorm_bwd_set")
         return dx, (dx if res is not None else None), dg, db, None
+
+
+class AttnAdapter(torch.autograd.Function):
+    """MMS attention adapter with its residual: y = h + W2 relu(W1 LN(h; norm_w, norm_b, eps 1e-5) + b1) + b2 (transformers'
+    Wav2Vec2AttnAdapterLayer at the end of a pre-LN layer), one launch forward and a fused backward (csrc/mms_adapter_train.hip,
+    include/thunder_speech_amd_mms_adapter_train.h).  Only h and the weights are saved: the backward recomputes LN(h), z and the ReLU mask.
+    Mixed mode: the two small weights are cast to bf16 here and multiply bf16 operands (f32 accumulation); LayerNorm and every gradient are f32."""
+
+    @staticmethod
+    def forward(ctx, h, norm_w, norm_b, w1, b1, w2, b2):
+        h = _f32c(h)
+        mixed = _MIXED
+        a, c = w1.shape
+        rows = h.numel() // c
+        wdt = torch.bfloat16 if mixed else torch.float32
+        norm_w, norm_b, b1, b2 = (_f32c(t.detach()) for t in (norm_w, norm_b, b1, b2))
+        w1o, w2o = w1.detach().to(wdt).contiguous(), w2.detach().to(wdt).contiguous()
+        y = torch.empty_like(h)
+        st = _lib.lib().ts_mms_attn_adapter_train_fwd(h.data_ptr(), rows, c, a, norm_w.data_ptr(), norm_b.data_ptr(), w1o.data_ptr(), b1.data_ptr(),
+                                                      w2o.data_ptr(), b2.data_ptr(), y.data_ptr(), int(mixed), _s(h))
+        _lib.check(st, "ts_mms_attn_adapter_train_fwd")
+        ctx.save_for_backward(h, norm_w, norm_b, w1o, b1, w2o)
+        ctx.mixed = mixed
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        h, norm_w, norm_b, w1o, b1, w2o = ctx.saved_tensors
+        dy = _f32c(dy)
+        a, c = w1o.shape
+        rows = h.numel() // c
+        L = _lib.lib()
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=h.device)
+        dh = torch.empty_like(h) if ctx.needs_input_grad[0] else None          # the first adapter of a frozen base: no upstream gradient
+        grads = [new(c), new(c), new(a, c), new(a), new(c, a), new(c)]         # d_norm_w, d_norm_b, d_w1, d_b1, d_w2, d_b2
+        ws = torch.empty(L.ts_mms_attn_adapter_train_bwd_workspace(rows, c, a), dtype=torch.uint8, device=h.device)
+        st = L.ts_mms_attn_adapter_train_bwd(h.data_ptr(), dy.data_ptr(), rows, c, a, norm_w.data_ptr(), norm_b.data_ptr(), w1o.data_ptr(),
+                                             b1.data_ptr(), w2o.data_ptr(), dh.data_ptr() if dh is not None else None, *(g.data_ptr() for g in grads),
+                                             ws.data_ptr(), int(ctx.mixed), _s(h))
+        _lib.check(st, "ts_mms_attn_adapter_train_bwd")
+        return (dh,) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[1:]))
 
 
 class BiasGelu(torch.autograd.Function):
@@ -770,9 +813,13 @@ def refuse_untrainable(adapt, mixed: bool) -> None:
     if getattr(cfg, "add_adapter", False):
         raise NotImplementedError("HIP fine-tuning path: add_adapter=True is inference-only (the adapter layers have no backward here)")
     if has_attn_adapters(cfg):
-        # MMS: the attention adapters (csrc/mms.hip) have no backward; a step without them would train a different network
-        raise NotImplementedError(f"HIP fine-tuning path: adapter_attn_dim={cfg.adapter_attn_dim} is inference-only (the attention adapters have no "
-                                  "backward here)")
+        # MMS: the adapters train on a frozen base (AttnAdapter); with anything else trainable the step would need every base gradient next to the
+        # adapters', a regime nothing here has been checked in
+        base = [n for n, p in enc.named_parameters() if p.requires_grad and ".adapter_layer." not in n]
+        if base:
+            raise NotImplementedError(f"HIP fine-tuning path: adapter_attn_dim={cfg.adapter_attn_dim} trains adapter-only (the attention adapters and "
+                                      f"the CTC head on a frozen base); {len(base)} base parameters have requires_grad=True (first: {base[0]}). "
+                                      "Call HuggingFaceEncoderAdapt.adapter_finetuning() first")
     if float(getattr(cfg, "mask_feature_prob", 0.0)) > 0.0 and getattr(cfg, "apply_spec_augment", True):
         raise NotImplementedError("wav2vec2 HIP training path: mask_feature_prob > 0 is not supported")
     unfrozen = [n for n, p in enc.feature_extractor.named_parameters() if p.requires_grad]
@@ -862,6 +909,9 @@ def _train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
         if stable:                                                  # pre-LN: h += attn(LN(h)); h += ffn(LN(h))
             h = Add.apply(h, attend(LayerNorm.apply(h, None, layer.layer_norm.weight, layer.layer_norm.bias, eps)))
             h = Add.apply(h, ffn(LayerNorm.apply(h, None, layer.final_layer_norm.weight, layer.final_layer_norm.bias, eps)))
+            ad = getattr(layer, "adapter_layer", None)
+            if ad is not None:                                      # MMS: h += adapter_layer(h), skipped by LayerDrop with the rest of the layer
+                h = AttnAdapter.apply(h, ad.norm.weight, ad.norm.bias, ad.linear_1.weight, ad.linear_1.bias, ad.linear_2.weight, ad.linear_2.bias)
         else:                                                       # post-LN: h = LN(h + attn(h)); h = LN(h + ffn(h))
             h = LayerNorm.apply(attend(h), h, layer.layer_norm.weight, layer.layer_norm.bias, eps)
             h = LayerNorm.apply(ffn(h), h, layer.final_layer_norm.weight, layer.final_layer_norm.bias, eps)

@@ -12,7 +12,14 @@ rotated inputs, peak allocated memory of both -- and the per-call times of ts_mm
 head_dim 64 calls at the same batch, t and heads (c = 1024).
 python tools/bench_mms.py --train [--batch 8] [--seconds 10] [--layers 48] [--steps 10] [--out FILE.md]
 --train-kernels: only issues those launches, for a kernel trace (rocprofv3 --kernel-trace --stats -- python tools/bench_mms.py --train-kernels):
-the four launches of the new path are mt_fwd_kernel, mt_rowdot_kernel, mt_bwd_dq_kernel and mt_bwd_dkv_kernel."""
+the four launches of the new path are mt_fwd_kernel, mt_rowdot_kernel, mt_bwd_dq_kernel and mt_bwd_dkv_kernel.
+
+--train-adapters: adapter-only fine-tuning of the MMS-1B geometry (adapter_attn_dim 16, HuggingFaceEncoderAdapt.adapter_finetuning(): the base frozen,
+the 48 attention adapters trained; huggingface/train.py AttnAdapter, csrc/mms_adapter_train.hip), 8 x 10 s, train_precision="bf16" -- ms per step
+and peak allocated memory next to the full fine-tuning step of the same geometry without adapters, same process -- and the per-call times of
+ts_mms_attn_adapter_train_fwd / _bwd at that step's rows next to their HBM floor and to transformers' own Wav2Vec2AttnAdapterLayer + residual,
+forward + backward under torch on the same GPU.  The fused pair taking longer than torch's is an error (exit status 1).
+python tools/bench_mms.py --train-adapters [--batch 8] [--seconds 10] [--layers 48] [--steps 10] [--out FILE.md]"""
 import argparse
 import os
 import sys
@@ -101,15 +108,15 @@ def time_adapter(a, t=999, c=1280, ad=16, reps=50):
     return _best_of_blocks(calls, reps), floors, rows
 
 
-def train_model(layers, seed=0):
-    """transformers' Wav2Vec2Model at the XLS-R 1B geometry (pre-LN, layer-norm convs, no adapters), random weights, attention dropout 0.1 and the
-    other dropouts / time masking of tools/bench_wavlm.py's fine-tuning recipe."""
+def train_model(layers, seed=0, adapter_attn_dim=None):
+    """transformers' Wav2Vec2Model at the XLS-R 1B geometry (pre-LN, layer-norm convs; adapter_attn_dim: MMS-1B's attention adapters), random weights,
+    attention dropout 0.1 and the other dropouts / time masking of tools/bench_wavlm.py's fine-tuning recipe."""
     import transformers
     torch.manual_seed(seed)
     return transformers.Wav2Vec2Model(transformers.Wav2Vec2Config(
         hidden_size=1280, num_hidden_layers=layers, num_attention_heads=16, intermediate_size=5120, feat_extract_norm="layer",
         do_stable_layer_norm=True, conv_bias=True, hidden_dropout=0.1, attention_dropout=0.1, activation_dropout=0.1, feat_proj_dropout=0.1,
-        layerdrop=0.0, mask_time_prob=0.05, mask_feature_prob=0.0, vocab_size=32))
+        layerdrop=0.0, mask_time_prob=0.05, mask_feature_prob=0.0, vocab_size=32, adapter_attn_dim=adapter_attn_dim))
 
 
 def graph_nodes(fn):
@@ -235,6 +242,142 @@ def main_train(a):
     return lines
 
 
+def time_train_step(a, adapters: bool, rounds=2, n_inputs=3):
+    """ms / step (per block), peak allocated bytes, node names, t and the number of trained parameters of one fine-tuning regime: adapters = True --
+    MMS-1B geometry, adapter_finetuning() (base frozen); False -- the same geometry without adapters, everything behind the conv front end trained.
+    2 warm-up steps, then `rounds` blocks of steps / rounds timed steps between device events; the inputs rotate over `n_inputs` seeded batches."""
+    from thunder_speech_amd.huggingface.encoder import HuggingFaceEncoderAdapt
+    adapt = HuggingFaceEncoderAdapt(train_model(a.layers, adapter_attn_dim=16 if adapters else None), mask_input=True, train_precision="bf16").cuda().train()
+    if adapters:
+        adapt.adapter_finetuning(init=True)
+    params = [p for p in adapt.parameters() if p.requires_grad]
+    opt = torch.optim.AdamW(params, lr=1e-5)
+    g = torch.Generator().manual_seed(0)
+    xs = [(0.1 * torch.randn(a.batch, 16000 * a.seconds, generator=g)).cuda() for _ in range(n_inputs)]
+    lengths = torch.full((a.batch,), 16000 * a.seconds, dtype=torch.int64, device="cuda")
+    lengths[-1] = 16000 * a.seconds * 3 // 4                                  # one ragged clip
+    state = dict(probe=None, i=0, nodes=None, t=None)
+
+    def step(walk=False):
+        opt.zero_grad(set_to_none=True)
+        feats, _ = adapt(xs[state["i"] % n_inputs], lengths)
+        state["i"] += 1
+        if state["probe"] is None:
+            state["probe"], state["t"] = torch.randn(feats.shape, generator=g).cuda(), feats.shape[-1]
+        if walk:
+            state["nodes"] = graph_nodes(feats.grad_fn)
+        (feats * state["probe"]).mean().backward()
+        opt.step()
+
+    for i in range(2):
+        step(walk=i == 0)
+    torch.cuda.synchronize()
+    per = max(1, (a.steps + rounds - 1) // rounds)
+    blocks, peak = [], 0
+    for _ in range(rounds):
+        torch.cuda.reset_peak_memory_stats()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(per + 1)]
+        ev[0].record()
+        for i in range(per):
+            step()
+            ev[i + 1].record()
+        torch.cuda.synchronize()
+        steps_ms = [ev[i].elapsed_time(ev[i + 1]) for i in range(per)]
+        print(f"  block ({'adapter-only' if adapters else 'full'}): " + " ".join(f"{x:.1f}" for x in steps_ms) + " ms", flush=True)
+        blocks.append(sum(steps_ms) / per)
+        peak = max(peak, torch.cuda.max_memory_allocated())
+    out = dict(blocks=blocks, peak=peak, nodes=state["nodes"], t=state["t"], trained=sum(p.numel() for p in params), steps=per * rounds)
+    del adapt, opt, xs, params
+    torch.cuda.empty_cache()
+    return out
+
+
+def adapter_train_calls(rows, c=1280, ad=16):
+    """-> ({name: call}, torch's forward + backward as a callable, buffers to keep alive) at precision 1, dh asked for."""
+    import transformers
+    from transformers.models.wav2vec2.modeling_wav2vec2 import Wav2Vec2AttnAdapterLayer
+    from thunder_speech_amd import _lib
+    L = _lib.lib()
+    s = torch.cuda.current_stream().cuda_stream
+    g = torch.Generator().manual_seed(4)
+    h, dy = torch.randn(rows, c, generator=g).cuda(), torch.randn(rows, c, generator=g).cuda()
+    layer = Wav2Vec2AttnAdapterLayer(transformers.Wav2Vec2Config(hidden_size=c, adapter_attn_dim=ad)).cuda()
+    with torch.no_grad():
+        layer.linear_2.weight.copy_(0.02 * torch.randn(c, ad, generator=g))
+    nw, nb, b1, b2 = (t.detach() for t in (layer.norm.weight, layer.norm.bias, layer.linear_1.bias, layer.linear_2.bias))
+    w1, w2 = layer.linear_1.weight.detach().to(torch.bfloat16), layer.linear_2.weight.detach().to(torch.bfloat16)
+    y, dh = torch.empty_like(h), torch.empty_like(h)
+    grads = [torch.empty_like(t, dtype=torch.float32) for t in (nw, nb, w1, b1, w2, b2)]
+    ws = torch.empty(L.ts_mms_attn_adapter_train_bwd_workspace(rows, c, ad), dtype=torch.uint8, device="cuda")
+    calls = {
+        "ts_mms_attn_adapter_train_fwd": lambda: L.ts_mms_attn_adapter_train_fwd(h.data_ptr(), rows, c, ad, nw.data_ptr(), nb.data_ptr(), w1.data_ptr(),
+                                                                                 b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), y.data_ptr(), 1, s),
+        "ts_mms_attn_adapter_train_bwd": lambda: L.ts_mms_attn_adapter_train_bwd(h.data_ptr(), dy.data_ptr(), rows, c, ad, nw.data_ptr(), nb.data_ptr(),
+                                                                                 w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), dh.data_ptr(),
+                                                                                 *(t.data_ptr() for t in grads), ws.data_ptr(), 1, s),
+    }
+    hg = h.clone().requires_grad_(True)
+    inputs = [hg] + list(layer.parameters())
+
+    def torch_pair(autocast):
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+            out = hg + layer(hg)
+        torch.autograd.grad(out, inputs, dy)
+    return calls, torch_pair, (h, dy, y, dh, grads, ws, layer, hg)
+
+
+def time_adapter_train(a, t, reps=20):
+    rows = a.batch * t
+    calls, torch_pair, keep = adapter_train_calls(rows)
+    best = _best_of_blocks(calls, reps)
+    ref = {}
+    for name, autocast in (("torch, f32", False), ("torch, autocast bf16", True)):
+        ref[name] = float("inf")
+        for _ in range(3):
+            torch_pair(autocast)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                torch_pair(autocast)
+            e1.record(); torch.cuda.synchronize()
+            ref[name] = min(ref[name], e0.elapsed_time(e1) / reps * 1e3)
+    return best, ref, rows
+
+
+def main_train_adapters(a):
+    """-> (markdown lines, whether the fused pair is no slower than torch's)"""
+    full = time_train_step(a, adapters=False)
+    ad = time_train_step(a, adapters=True)
+    t = ad["t"]
+    lines = [f"fine-tuning step, train_precision=\"bf16\": {a.batch} x {a.seconds} s (one clip 3/4 long), {a.layers} layers, 1280 hidden / 16 heads (head_dim 80) / "
+             f"5120 FFN, pre-LN, layer-norm convs, random weights, t = {t} frames, dropouts 0.1 (attention included), mask_time_prob 0.05; forward + backward of "
+             f"a probe loss + AdamW over the trained parameters; one process, 2 warm-up steps, then {ad['steps']} timed steps in 2 blocks between device "
+             "events, inputs rotated over 3 batches", "",
+             "| regime | trained parameters | ms/step | blocks | peak allocated GiB |", "|---|---:|---:|---|---:|"]
+    for name, r in (("full fine-tuning, no adapters (XLS-R 1B geometry)", full), ("adapter-only, adapter_attn_dim 16 (MMS-1B geometry)", ad)):
+        ms = sum(r["blocks"]) / len(r["blocks"])
+        lines.append(f"| {name} | {r['trained']:,} | {ms:.1f} | {' / '.join(f'{x:.1f}' for x in r['blocks'])} | {r['peak'] / 2 ** 30:.2f} |")
+    lines += ["", "autograd nodes of one adapter-only step's graph (name x count): " +
+              ", ".join(f"{nm} x {cnt}" for nm, cnt in sorted(ad["nodes"].items()))]
+    best, ref, rows = time_adapter_train(a, t)
+    floor = {"ts_mms_attn_adapter_train_fwd": 2 * rows * 1280 * 4 / HBM_PEAK * 1e6, "ts_mms_attn_adapter_train_bwd": 3 * rows * 1280 * 4 / HBM_PEAK * 1e6}
+    lines += ["", f"adapter node calls, rows = {a.batch} x {t} = {rows}, c = 1280, a = 16, precision 1, dh asked for (device events, best of 3 blocks of 20); HBM "
+              f"floor at {HBM_PEAK / 1e12:.0f} TB/s: forward 2 rows c 4 bytes (read h, write y), backward 3 rows c 4 (read h, read dy, write dh):", "",
+              "| entry point | us per call | HBM floor us |", "|---|---:|---:|"]
+    for k, us in best.items():
+        lines.append(f"| {k} | {us:.1f} | {floor[k]:.1f} |")
+    pair = sum(best.values())
+    lines += ["", "forward + backward of the adapter with its residual, same rows, same GPU, same run; torch = transformers' Wav2Vec2AttnAdapterLayer under "
+              "autograd (LayerNorm, Linear, ReLU, Linear, add: u, z, r and the term stored and read back):", "",
+              "| path | us per forward + backward | vs the fused pair |", "|---|---:|---:|",
+              f"| fused pair (ts_mms_attn_adapter_train_fwd + _bwd) | {pair:.1f} | 1.000 |"]
+    for k, us in ref.items():
+        lines.append(f"| {k} | {us:.1f} | {us / pair:.3f} |")
+    ok = pair <= min(ref.values())
+    lines += ["", f"the fused pair takes {'no longer' if ok else 'LONGER'} than torch's faster path ({pair:.1f} us against {min(ref.values()):.1f} us)"]
+    return lines, ok
+
+
 def main_train_kernels(a, t=499, reps=10):
     from thunder_speech_amd import _lib
     calls, keep = train_attention_calls(a, t)
@@ -253,9 +396,11 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="timed steps per mode: default 5 (inference), 10 (--train)")
     ap.add_argument("--train", action="store_true", help="mixed-precision fine-tuning steps, fused attention on and off, instead of inference")
     ap.add_argument("--train-kernels", action="store_true", help="only issue the training attention launches at t = 499 (for a kernel trace)")
+    ap.add_argument("--train-adapters", action="store_true", help="adapter-only fine-tuning steps of the MMS-1B geometry next to full fine-tuning, and the "
+                    "adapter node's calls against torch")
     ap.add_argument("--out", default=None, help="also write the tables (markdown) to this file")
     a = ap.parse_args()
-    training = a.train or a.train_kernels
+    training = a.train or a.train_kernels or a.train_adapters
     a.batch = a.batch or (8 if training else 16)
     a.seconds = a.seconds or (10 if training else 20)
     a.steps = a.steps or (10 if training else 5)
@@ -263,13 +408,16 @@ def main():
         raise SystemExit("bench_mms: needs an MI355X")
     if a.train_kernels:
         return main_train_kernels(a)
-    if a.train:
-        text = "\n".join(main_train(a))
+    if a.train or a.train_adapters:
+        lines, ok = main_train_adapters(a) if a.train_adapters else (main_train(a), True)
+        text = "\n".join(lines)
         print(text)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:
                 f.write(text + "\n")
+        if not ok:
+            raise SystemExit(1)
         return
     rows, t = [], None
     for name, adapters in (("XLS-R 1B geometry (no adapters)", False), ("MMS-1B (adapter_attn_dim 16)", True)):
