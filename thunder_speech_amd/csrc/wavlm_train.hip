@@ -214,7 +214,7 @@ __global__ __launch_bounds__(256) void wt_bwd_dkv_kernel(const WtArgs a) {
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       s16x8 ga[2], qa[2], pb[2], sb[2];
-      dkv_operands(ga, qa, pb, sb, wt, ks, g);
+      dkv_operands(ga, qa, pb, sb, wt, ks, g, g.tr_off);
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt)
 #pragma unroll

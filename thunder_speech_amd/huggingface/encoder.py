@@ -9,7 +9,7 @@ call per stage.  Both published families (group-norm / post-LN: wav2vec2-base-96
 WavLM runs the same sequence with its gated relative-position attention (csrc/wavlm.hip, include/thunder_speech_amd_wavlm.h) in place of
 the wav2vec2 one (fine-tuning in mixed precision only: csrc/wavlm_train.hip); wav2vec2-conformer (rotary) runs conformer blocks behind the same
 front end (huggingface/conformer.py, inference only); MMS (config.adapter_attn_dim: an attention adapter behind every pre-LN layer) and the head_dim 80
-of MMS-1B / XLS-R 1B run on csrc/mms.hip (include/thunder_speech_amd_mms.h, inference only); training mode (fine-tuning with the conv feature extractor frozen) runs
+of MMS-1B / XLS-R 1B run on csrc/mms.hip and the head_dim 80 kernel of csrc/w2v_attn.hip (include/thunder_speech_amd_mms.h, inference only); training mode (fine-tuning with the conv feature extractor frozen) runs
 through huggingface/train.py; no CPU fallback."""
 from __future__ import annotations
 
@@ -414,7 +414,7 @@ class Wav2Vec2Plan:
             _lib.check(L.ts_wavlm_rel_bias(self.rel_embed.data_ptr(), self.abs_bucket.data_ptr(), self.nb, self.md, self.heads, t,
                                            rel_bias.data_ptr(), stream), "ts_wavlm_rel_bias")
         elif self.mms_attention:
-            att_ws = None                              # head_dim 80 in bf16 mode: the fused kernel of csrc/mms.hip, no [t][t] scores
+            att_ws = None                              # head_dim 80 in bf16 mode: ts_mms_attention_fwd (the fused kernel of csrc/w2v_attn.hip), no [t][t] scores
         else:
             att_ws = self._buf(L.ts_w2v_attention_workspace_bytes(b, t, self.heads, self.prec), dtype=torch.uint8)
 

@@ -2,7 +2,7 @@
 forward and backward are C-ABI launches (csrc/gemm_f32.hip for every product, csrc/w2v_train.hip for the rest).  `transformers.WavLMModel`
 trains on the same chain in mixed precision, with its gated relative-position attention on csrc/wavlm_train.hip (WavLMGate, WavLMRelBias,
 WavLMAttentionFused).  In mixed precision the attention core is fused at head_dim 64 (AttentionFused, csrc/w2v_attn_train.hip) and at head_dim 80
-(AttentionFused80, csrc/mms_train.hip: the XLS-R 1B geometry); every other head dimension, and f32 training, take the materialised Attention node.
+(AttentionFused80, ts_mms_attention_train_* of csrc/mms_train.hip on the head_dim 80 kernels of csrc/w2v_attn_train.hip: the XLS-R 1B geometry); every other head dimension, and f32 training, take the materialised Attention node.
 MMS checkpoints (config.adapter_attn_dim) train adapter-only: the base frozen (HuggingFaceEncoderAdapt.adapter_finetuning), the attention adapter
 behind every layer one fused node (AttnAdapter, csrc/mms_adapter_train.hip).
 
@@ -530,7 +530,7 @@ class AttentionFused(torch.autograd.Function):
 
 
 class AttentionFused80(torch.autograd.Function):
-    """AttentionFused at head_dim 80 (XLS-R 1B / MMS geometry: hidden 1280, 16 heads; csrc/mms_train.hip, include/thunder_speech_amd_mms_train.h):
+    """AttentionFused at head_dim 80 (XLS-R 1B / MMS geometry: hidden 1280, 16 heads; csrc/mms_train.hip on the kernels of csrc/w2v_attn_train.hip, include/thunder_speech_amd_mms_train.h):
     the same contract, node shape and saved tensors on the ts_mms_attention_train_* entry points."""
     ENTRY = "ts_mms_attention_train"
 

@@ -1,18 +1,18 @@
 """MMS-1B inference on the HIP path (random weights): hidden 1280, 48 layers, 16 heads (head_dim 80), FFN 5120, layer-norm convs, pre-LN,
 adapter_attn_dim 16; 16 x 20 s, bf16 -- eager and graphed, next to the same geometry without adapters (XLS-R 1B) -- and the per-launch times of
-the two kernels of csrc/mms.hip at that step's geometry (t = 999 frames):
+the two launches of csrc/mms.hip at that step's geometry (t = 999 frames):
   ts_mms_attention_fwd     against ts_w2v_attention_fwd on the same head_dim-80 input (which materialises the [t][t] scores)
   ts_mms_attn_adapter_fwd  (adapter + the LayerNorm behind it) against a plain ts_w2v_layernorm_fwd over the same rows, next to its HBM floor
 python tools/bench_mms.py [--batch 16] [--seconds 20] [--layers 48] [--steps 5] [--out FILE.md]
 
 --train: mixed-precision fine-tuning steps (train_precision="bf16": training forward, backward of a probe loss, AdamW) at the XLS-R 1B geometry
 without adapters, 8 x 10 s, attention dropout 0.1, with the fused head_dim 80 attention node (huggingface/train.py AttentionFused80,
-csrc/mms_train.hip) and with train.FUSED_ATTENTION = False (the materialised `Attention` node) -- same process, alternating blocks, device events,
+csrc/mms_train.hip, csrc/w2v_attn_train.hip) and with train.FUSED_ATTENTION = False (the materialised `Attention` node) -- same process, alternating blocks, device events,
 rotated inputs, peak allocated memory of both -- and the per-call times of ts_mms_attention_train_fwd / _bwd at that step's t next to the
 head_dim 64 calls at the same batch, t and heads (c = 1024).
 python tools/bench_mms.py --train [--batch 8] [--seconds 10] [--layers 48] [--steps 10] [--out FILE.md]
 --train-kernels: only issues those launches, for a kernel trace (rocprofv3 --kernel-trace --stats -- python tools/bench_mms.py --train-kernels):
-the four launches of the new path are mt_fwd_kernel, mt_rowdot_kernel, mt_bwd_dq_kernel and mt_bwd_dkv_kernel.
+the four launches of the head_dim 80 path are attn_fwd_train_kernel<80>, attn_rowdot80_kernel, attn_bwd_dq_kernel<80> and attn_bwd_dkv_kernel<80>.
 
 --train-adapters: adapter-only fine-tuning of the MMS-1B geometry (adapter_attn_dim 16, HuggingFaceEncoderAdapt.adapter_finetuning(): the base frozen,
 the 48 attention adapters trained; huggingface/train.py AttnAdapter, csrc/mms_adapter_train.hip), 8 x 10 s, train_precision="bf16" -- ms per step
@@ -80,7 +80,7 @@ def time_attention(a, t=999, heads=16, reps=20):
     calls = {
         "ts_w2v_attention_fwd, head_dim 80 (materialised scores)": lambda: L.ts_w2v_attention_fwd(qkv.data_ptr(), b, t, c, heads, None, 1, ctx.data_ptr(),
                                                                                                    ws.data_ptr(), s),
-        "ts_mms_attention_fwd (mms_flash_attn_kernel)": lambda: L.ts_mms_attention_fwd(qkv.data_ptr(), b, t, c, heads, None, ctx.data_ptr(), s),
+        "ts_mms_attention_fwd (w2v_flash_attn_kernel<80>)": lambda: L.ts_mms_attention_fwd(qkv.data_ptr(), b, t, c, heads, None, ctx.data_ptr(), s),
     }
     return _best_of_blocks(calls, reps), ws_bytes
 
