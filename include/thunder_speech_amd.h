@@ -26,7 +26,7 @@ extern "C" {
 #define TS_EINVAL (-1)       /* bad argument / unsupported shape */
 #define TS_EUNSUPPORTED (-2) /* valid reference configuration this build has no kernel for */
 
-#define TS_ABI_VERSION 14
+#define TS_ABI_VERSION 15
 
 /* Library identification: ABI version and the gfx target the code objects were built for. */
 int ts_abi_version(void);
@@ -149,6 +149,19 @@ int ts_gemm_f32(const void* a, int64_t a_rs, int64_t a_cs, int64_t sa, int64_t s
 int ts_gemm_f32_b2(const void* a, int64_t a_rs, int64_t a_cs, int64_t sa, int64_t sa2, int64_t ska, const void* b, int64_t b_rs, int64_t b_cs,
                    int64_t sb, int64_t sb2, int64_t skb, void* c, int64_t ldc, int64_t sc, int64_t sc2, const float* bias, int32_t m, int32_t n,
                    int32_t k, int32_t nkb, int32_t batch, int32_t batch2, int32_t beta, void* stream);
+/* ABI v15.  What ts_gemm_f32 (batch2 = 1, sa2 = sb2 = 0) / ts_gemm_f32_b2 would launch for these arguments, computed by the function the launcher
+ * itself launches from.  a, b, c are used as ADDRESSES only (NULL or not, alignment); nothing is dereferenced.  a_kc / b_kc = 1 when the
+ * contraction index is the contiguous one of A (a_cs == 1) / B (b_rs == 1): with in_bf16 they name the instantiation, one of eight.  vec_a / vec_b
+ * = 1 when that operand is fetched with vector loads (base 16-byte aligned, 8 for bf16; row pitch, both batch strides and the outer contraction
+ * stride all multiples of 4 -- also where batch, batch2 or nkb is 1 and the stride is never used), 0 for the element-by-element path.  grid_x =
+ * ceil(m / 128) ceil(n / 128) output tiles, grid_z = batch x batch2, stages = ceil(k / 16) stages per outer contraction step (the last one
+ * partial when k % 16 != 0; nkb x stages in all).  Host code only: no launch, no stream, no device call.  Returns what the entry points
+ * return: TS_EINVAL for a NULL operand or output, a size <= 0 or ldc < n; TS_EUNSUPPORTED when neither stride of an operand is 1 or
+ * batch x batch2 > 65535; TS_EINVAL also for a NULL result pointer of the query. */
+int ts_gemm_f32_launch_config(const void* a, int64_t a_rs, int64_t a_cs, int64_t sa, int64_t sa2, int64_t ska, const void* b, int64_t b_rs,
+                              int64_t b_cs, int64_t sb, int64_t sb2, int64_t skb, const void* c, int64_t ldc, int32_t m, int32_t n, int32_t k,
+                              int32_t nkb, int32_t batch, int32_t batch2, int32_t in_bf16, int32_t* a_kc, int32_t* b_kc, int32_t* vec_a,
+                              int32_t* vec_b, int32_t* grid_x, int32_t* grid_z, int32_t* stages);
 
 /* ------------------------------------------------------------------------------------------------
  * wav2vec2 fine-tuning (csrc/w2v_train.hip): what the backward pass of transformers.Wav2Vec2Model needs besides GEMMs (the reference trains
@@ -604,6 +617,27 @@ int ts_gemm_nt_bf16_splitk(const void* x, int64_t lda, const void* w, int64_t ld
 int ts_gemm_nt_bf16_packed(const void* x, int64_t lda, const void* w, int64_t ldw, const void* w_frag, const float* bias, const float* res,
                            int64_t ld_res, float* y, int64_t ldc, void* y_bf16, int64_t ld16, int64_t rows, int32_t n, int32_t k, int32_t gelu,
                            void* stream);
+/* ABI v15.  What ts_gemm_nt_bf16 (w_frag NULL) / ts_gemm_nt_bf16_packed (w_frag given) would launch for these arguments, computed by the function
+ * the launcher itself launches from; act by code as ts_conformer_linear_fwd (0 none, 1 GELU, 2 SiLU), batch = grid y (1 for the two entry points,
+ * the clips of ts_w2v_conv_fwd).  x, w, w_frag, res, y, y_bf16 are used as ADDRESSES only (NULL or not, alignment); nothing is dereferenced.
+ * n_mt = row tiles (256 rows; 128 with w_frag), n_nt = ceil(n / 256) column tiles, blk_c = column tiles per block of the tile walk (4, 3, 2 or 1:
+ * the largest that divides n_nt), grid_x = n_mt n_nt, grid_y = batch, threads = 512 (256 with w_frag), lds_bytes = the dynamic LDS,
+ * instantiation = one of TS_GEMM_NT_*, epilogue = TS_GEMM_NT_EPILOGUE_BF16 when only y_bf16 is wanted and there is no residual (the result tile is
+ * staged as bf16), else TS_GEMM_NT_EPILOGUE_F32.  Host code only: no launch, no stream, no device call.  Returns what the entry points return:
+ * TS_EINVAL for a NULL x / w, neither y nor y_bf16, a size <= 0, act outside 0..2, lda < 0, ldw < k, an output or residual pitch < n;
+ * TS_EUNSUPPORTED for n % 32, k % 32, lda % 8, ldw % 8, ldc % 4, ld16 % 8, ld_res % 4, a base that is not 16-byte aligned (x, w, w_frag, res, y,
+ * y_bf16), byte offsets ((rows - 1) lda + k) 2 or ((n - 1) ldw + k) 2 that reach 2^31 - 1, more than 2^31 - 1 tiles or batch > 65535;
+ * TS_EINVAL also for a NULL result pointer of the query. */
+#define TS_GEMM_NT_LDS_TWO_ROW 0          /* both operands through the LDS ring, 256 x 256 tile, two wave rows */
+#define TS_GEMM_NT_LDS_TWO_ROW_SILU 1
+#define TS_GEMM_NT_PACKED_HALF_TILE 2     /* packed weights from L2 into registers, 128 x 256 tile, one wave row */
+#define TS_GEMM_NT_PACKED_HALF_TILE_SILU 3
+#define TS_GEMM_NT_EPILOGUE_BF16 0
+#define TS_GEMM_NT_EPILOGUE_F32 1
+int ts_gemm_nt_launch_config(const void* x, int64_t lda, const void* w, int64_t ldw, const void* w_frag, const void* res, int64_t ld_res,
+                             const void* y, int64_t ldc, const void* y_bf16, int64_t ld16, int64_t rows, int32_t n, int32_t k, int32_t act,
+                             int32_t batch, int32_t* n_mt, int32_t* n_nt, int32_t* blk_c, int32_t* grid_x, int32_t* grid_y, int32_t* threads,
+                             int32_t* lds_bytes, int32_t* instantiation, int32_t* epilogue);
 /* y[r][:n] = act(x[r][:k] W^T + bias) + res[r][:n];  W [n][k]; bias / res (f32) may be NULL; act bit 0: GELU (erf), bit 1:
  * only y_bf16 is wanted (y is then scratch space for the f32 GEMM result).  res == y (same pitch): the product is accumulated into y
  * in place (the residual stream).  lda / ldc / ld_res: row pitches in elements. */

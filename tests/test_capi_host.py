@@ -39,7 +39,7 @@ def test_library_builds_and_exports_every_declared_symbol():
 def test_library_loads_and_answers_version_queries():
     from thunder_speech_amd import _lib
     L = _lib.lib()
-    assert L.ts_abi_version() == _lib.ABI_VERSION == 14
+    assert L.ts_abi_version() == _lib.ABI_VERSION == 15
     assert L.ts_build_target() == b"gfx950"
     for t in (1, 127, 128, 129, 751, 1501, 2001):
         assert L.ts_time_pitch(t) == _lib.time_pitch(t) and _lib.time_pitch(t) % 128 == 0 and _lib.time_pitch(t) >= t
@@ -120,7 +120,7 @@ def test_derived_signatures_pin_every_type_mapping():
     from thunder_speech_amd import _lib
     S, P = _lib.SIGNATURES, ctypes.POINTER
     i32, i64, u64, f32, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_void_p
-    assert len(S) == 121 and list(S) == _lib.EXPORTED_SYMBOLS
+    assert len(S) == 123 and list(S) == _lib.EXPORTED_SYMBOLS
     assert S["ts_abi_version"] == (ctypes.c_int, [])
     assert S["ts_build_target"][0] is ctypes.c_char_p
     assert S["ts_time_pitch"] == (ctypes.c_int, [i32])                                      # int
@@ -132,12 +132,16 @@ def test_derived_signatures_pin_every_type_mapping():
     assert S["ts_train_pwconv_wgrad_multi"][1] == [P(_lib.WgradItem), i32, vp]
     assert S["ts_ctc_launch_config"] == (ctypes.c_int, [i32, i32, vp, vp, vp, vp])           # int32_t* (outputs)
     assert S["ts_frontend_launch_config"] == (ctypes.c_int, [P(_lib.FrontendDesc), vp, vp, vp, vp])
+    assert S["ts_gemm_nt_launch_config"] == (ctypes.c_int, [vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, i64, i64, i32, i32, i32, i32] + [vp] * 9)
+    assert S["ts_gemm_f32_launch_config"] == (ctypes.c_int, [vp, i64, i64, i64, i64, i64] * 2 + [vp, i64] + [i32] * 7 + [vp] * 7)
+    assert [_lib.DEFINES["TS_GEMM_NT_" + n] for n in ("LDS_TWO_ROW", "LDS_TWO_ROW_SILU", "PACKED_HALF_TILE", "PACKED_HALF_TILE_SILU", "EPILOGUE_BF16",
+                                                       "EPILOGUE_F32")] == [0, 1, 2, 3, 0, 1]
     args = S["ts_train_dropout"][1]
     assert args[5] is f32 and args[6] is u64 and args[2] is i64
     assert len(S["ts_gemm_f32"][1]) == 23 and S["ts_gemm_f32"][1][:2] == [vp, i64]
     assert S["ts_train_wgrad_reduce_multi"][1] == [vp, vp, vp, vp, i32, vp]                   # void* const*, const int64_t*
     assert S["ts_w2v_mask_embed"][1][1] is vp                                               # const uint8_t*
-    assert (_lib.ABI_VERSION, _lib.TS_EINVAL, _lib.TS_EUNSUPPORTED, _lib.GUARD_BYTES) == (14, -1, -2, 1024)
+    assert (_lib.ABI_VERSION, _lib.TS_EINVAL, _lib.TS_EUNSUPPORTED, _lib.GUARD_BYTES) == (15, -1, -2, 1024)
     assert (_lib.TCS_IN_TAILZERO, _lib.TCS_OUT_ZERO_TAIL, _lib.TCS_TAPS_PHASE) == (1, 2, 4)
 
 
@@ -457,7 +461,7 @@ _ASAN_DRIVER = r'''
 import ctypes as C, sys
 L = C.CDLL(sys.argv[1])
 i32, i64, vp = C.c_int32, C.c_int64, C.c_void_p
-assert L.ts_abi_version() == 14
+assert L.ts_abi_version() == 15
 L.ts_build_target.restype = C.c_char_p
 assert L.ts_build_target() == b"gfx950"
 assert [L.ts_time_pitch(t) for t in (1, 128, 751, 1501)] == [512, 512, 1152, 1920]

@@ -78,6 +78,11 @@ def test_unaligned_pitches_take_the_element_path():
     p = torch.randn(t, t, generator=g).cuda()
     v = torch.randn(t, 3 * hd + 2, generator=g).cuda()
     out = torch.empty(t, hd + 1, device="cuda")
+    import ctypes
+    cfg = [ctypes.c_int32(-1) for _ in range(7)]                                  # a_kc, b_kc, vec_a, vec_b, grid_x, grid_z, stages
+    assert _lib.lib().ts_gemm_f32_launch_config(p.data_ptr(), t, 1, 0, 0, 0, v.data_ptr(), v.stride(0), 1, 0, 0, 0, out.data_ptr(), out.stride(0), t, hd, t,
+                                                1, 1, 1, 0, *[ctypes.byref(o) for o in cfg]) == 0
+    assert [o.value for o in cfg] == [1, 0, 0, 0, 3, 1, 19]                        # both operands element by element: it is the path it names
     st = _lib.lib().ts_gemm_f32(p.data_ptr(), t, 1, 0, 0, v.data_ptr(), v.stride(0), 1, 0, 0, out.data_ptr(), out.stride(0), 0, None, t, hd, t, 1, 1, 0, 0, 0,
                                 torch.cuda.current_stream().cuda_stream)
     _lib.check(st, "ts_gemm_f32")

@@ -46,7 +46,7 @@ def test_no_name_is_declared_twice_and_the_older_headers_are_at_their_versions()
     assert len(headers) == 7
     names = [n for h in headers for n in _declared(h)]
     assert len(names) == len(set(names))
-    assert len(_declared(os.path.join(ROOT, "include", "thunder_speech_amd.h"))) == 121 and _lib.ABI_VERSION == 14
+    assert len(_declared(os.path.join(ROOT, "include", "thunder_speech_amd.h"))) == 123 and _lib.ABI_VERSION == 15
     assert (_lib.WAVLM_ABI_VERSION, _lib.WAVLM_TRAIN_ABI_VERSION, _lib.CONFORMER_ABI_VERSION, _lib.MMS_ABI_VERSION,
             _lib.MMS_TRAIN_ABI_VERSION) == (1, 1, 1, 1, 1)
     for table in (_lib.SIGNATURES, _lib.WAVLM_SIGNATURES, _lib.WAVLM_TRAIN_SIGNATURES, _lib.CONFORMER_SIGNATURES, _lib.MMS_SIGNATURES,

@@ -71,7 +71,7 @@ def test_companion_header_is_bound_and_exported_and_the_core_abi_is_unchanged():
     assert wavlm == sorted(["ts_wavlm_abi_version", "ts_wavlm_rel_bias", "ts_wavlm_attention_workspace_bytes", "ts_wavlm_attention_fwd"])
     assert sorted(_lib.WAVLM_SIGNATURES) == wavlm and _lib.WAVLM_ABI_VERSION == 1
     core = _declared(os.path.join(ROOT, "include", "thunder_speech_amd.h"))
-    assert sorted(_lib.SIGNATURES) == core and _lib.EXPORTED_SYMBOLS == list(_lib.SIGNATURES) and len(core) == 121
+    assert sorted(_lib.SIGNATURES) == core and _lib.EXPORTED_SYMBOLS == list(_lib.SIGNATURES) and len(core) == 123
     assert not set(wavlm) & set(core)
     vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
     assert _lib.WAVLM_SIGNATURES["ts_wavlm_attention_fwd"][1] == [vp, i32, i32, i32, i32, vp, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp]

@@ -209,17 +209,40 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmF32Args g) {
 // stored; along K the last partial stage is fetched element by element -- any other operand element by element throughout.
 // Two batch levels: grid.z = batch x batch2, operand offsets z1 s? + z2 s?2 ((clip, head) of the attention products; (group, tap) of the
 // positional conv's weight gradient).
+// What gemm_f32_b2 launches for a set of arguments: the argument checks, the instantiation (a_kc, b_kc: the contraction index is the contiguous
+// one of A / B), the fetch path of each operand and the grid.  gemm_f32_b2 launches from this and ts_gemm_f32_launch_config reports it; nothing
+// here touches the device.
+struct GemmF32Launch {
+  bool a_kc, b_kc, vec_a, vec_b;
+  int grid_x, grid_z;
+  int stages;                                        // 16-deep stages per outer contraction step, the last one partial when K % 16 != 0
+};
+static int gemm_f32_launch_config(bool in_bf16, const void* a, long long a_rs, long long a_cs, long long sa, long long sa2, long long ska,
+                                  const void* b, long long b_rs, long long b_cs, long long sb, long long sb2, long long skb, const void* c,
+                                  long long ldc, int M, int N, int K, int nkb, int batch, int batch2, GemmF32Launch* l) {
+  if (!a || !b || !c || M <= 0 || N <= 0 || K <= 0 || nkb <= 0 || batch <= 0 || batch2 <= 0 || ldc < N) return TS_EINVAL;
+  if ((long long)batch * batch2 > 65535) return TS_EUNSUPPORTED;
+  l->a_kc = a_cs == 1; l->b_kc = b_rs == 1;
+  if ((!l->a_kc && a_rs != 1) || (!l->b_kc && b_cs != 1)) return TS_EUNSUPPORTED;
+  const long long a_ld = l->a_kc ? a_rs : a_cs, b_ld = l->b_kc ? b_cs : b_rs;
+  const uintptr_t al = in_bf16 ? 7 : 15;
+  l->vec_a = !(a_ld % 4 || sa % 4 || sa2 % 4 || ska % 4 || (reinterpret_cast<uintptr_t>(a) & al));
+  l->vec_b = !(b_ld % 4 || sb % 4 || sb2 % 4 || skb % 4 || (reinterpret_cast<uintptr_t>(b) & al));
+  const long long tiles = (long long)((M + BM - 1) / BM) * ((N + BN - 1) / BN);
+  if (tiles > 0x7fffffffll) return TS_EUNSUPPORTED;
+  l->grid_x = (int)tiles;
+  l->grid_z = batch * batch2;
+  l->stages = (K + BK - 1) / BK;
+  return TS_OK;
+}
+
 int gemm_f32_b2(hipStream_t stream, bool in_bf16, const void* a, long long a_rs, long long a_cs, long long sa, long long ska, const void* b,
                 long long b_rs, long long b_cs, long long sb, long long skb, void* c, long long ldc, long long sc, bool out_bf16, const float* bias,
                 int M, int N, int K, int nkb, int batch, bool beta, int batch2, long long sa2, long long sb2, long long sc2) {
-  if (!a || !b || !c || M <= 0 || N <= 0 || K <= 0 || nkb <= 0 || batch <= 0 || batch2 <= 0 || ldc < N) return TS_EINVAL;
-  if ((long long)batch * batch2 > 65535) return TS_EUNSUPPORTED;
-  const bool a_kc = a_cs == 1, b_kc = b_rs == 1;
-  if ((!a_kc && a_rs != 1) || (!b_kc && b_cs != 1)) return TS_EUNSUPPORTED;
-  const long long a_ld = a_kc ? a_rs : a_cs, b_ld = b_kc ? b_cs : b_rs;
-  const uintptr_t al = in_bf16 ? 7 : 15;
-  const bool vec_a = !(a_ld % 4 || sa % 4 || sa2 % 4 || ska % 4 || (reinterpret_cast<uintptr_t>(a) & al));
-  const bool vec_b = !(b_ld % 4 || sb % 4 || sb2 % 4 || skb % 4 || (reinterpret_cast<uintptr_t>(b) & al));
+  GemmF32Launch l{};
+  const int cst = gemm_f32_launch_config(in_bf16, a, a_rs, a_cs, sa, sa2, ska, b, b_rs, b_cs, sb, sb2, skb, c, ldc, M, N, K, nkb, batch, batch2, &l);
+  if (cst != TS_OK) return cst;
+  const bool a_kc = l.a_kc, b_kc = l.b_kc, vec_a = l.vec_a, vec_b = l.vec_b;
   GemmF32Args g{};
   g.a = a; g.b = b; g.c = c; g.bias = bias;
   g.a_rs = a_rs; g.a_cs = a_cs; g.b_rs = b_rs; g.b_cs = b_cs; g.ldc = ldc;
@@ -227,7 +250,7 @@ int gemm_f32_b2(hipStream_t stream, bool in_bf16, const void* a, long long a_rs,
   g.sa2 = sa2; g.sb2 = sb2; g.sc2 = sc2; g.nb2 = batch2;
   g.M = M; g.N = N; g.K = K; g.nkb = nkb; g.beta = beta ? 1 : 0; g.out_bf16 = out_bf16 ? 1 : 0;
   g.vec_a = vec_a ? 1 : 0; g.vec_b = vec_b ? 1 : 0;
-  const dim3 grid((unsigned)(((M + BM - 1) / BM) * ((N + BN - 1) / BN)), 1, (unsigned)(batch * batch2));
+  const dim3 grid((unsigned)l.grid_x, 1, (unsigned)l.grid_z);
   (void)hipGetLastError();
 #define TS_GF(AK, BK_, BF_) hipLaunchKernelGGL((gemm_f32_kernel<AK, BK_, BF_>), grid, dim3(256), 0, stream, g)
   if (in_bf16) {
@@ -261,4 +284,18 @@ extern "C" int ts_gemm_f32_b2(const void* a, int64_t a_rs, int64_t a_cs, int64_t
                               int32_t n, int32_t k, int32_t nkb, int32_t batch, int32_t batch2, int32_t beta, void* stream) {
   return ts::gemm_f32_b2(reinterpret_cast<hipStream_t>(stream), false, a, a_rs, a_cs, sa, ska, b, b_rs, b_cs, sb, skb, c, ldc, sc, false, bias, m, n, k,
                          nkb, batch, beta != 0, batch2, sa2, sb2, sc2);
+}
+
+/* what ts_gemm_f32 (batch2 = 1, sa2 = sb2 = 0) / ts_gemm_f32_b2 would launch; see include/thunder_speech_amd.h */
+extern "C" int ts_gemm_f32_launch_config(const void* a, int64_t a_rs, int64_t a_cs, int64_t sa, int64_t sa2, int64_t ska, const void* b, int64_t b_rs,
+                                         int64_t b_cs, int64_t sb, int64_t sb2, int64_t skb, const void* c, int64_t ldc, int32_t m, int32_t n, int32_t k,
+                                         int32_t nkb, int32_t batch, int32_t batch2, int32_t in_bf16, int32_t* a_kc, int32_t* b_kc, int32_t* vec_a,
+                                         int32_t* vec_b, int32_t* grid_x, int32_t* grid_z, int32_t* stages) {
+  if (!a_kc || !b_kc || !vec_a || !vec_b || !grid_x || !grid_z || !stages) return TS_EINVAL;
+  ts::GemmF32Launch l{};
+  const int st = ts::gemm_f32_launch_config(in_bf16 != 0, a, a_rs, a_cs, sa, sa2, ska, b, b_rs, b_cs, sb, sb2, skb, c, ldc, m, n, k, nkb, batch, batch2, &l);
+  if (st != TS_OK) return st;
+  *a_kc = l.a_kc ? 1 : 0; *b_kc = l.b_kc ? 1 : 0; *vec_a = l.vec_a ? 1 : 0; *vec_b = l.vec_b ? 1 : 0;
+  *grid_x = l.grid_x; *grid_z = l.grid_z; *stages = l.stages;
+  return TS_OK;
 }

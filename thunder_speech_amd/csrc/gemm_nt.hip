@@ -369,10 +369,19 @@ int gemm_nt_pack_w(hipStream_t stream, const void* w, long long ldw, int N, int 
   return hip_status(hipGetLastError());
 }
 
-// wf: w in fragment order (gemm_nt_pack_w) or null
-static int gemm_nt_bf16_sw(hipStream_t stream, const void* x, long long lda, long long sx, const void* w, long long ldw, const float* bias,
-                           const float* res, long long ld_res, float* y, long long ldc, void* y16, long long ld16, long long sy, long long M, int N, int K,
-                           int act, int batch, const void* wf, long long sw) {
+// What gemm_nt_bf16_sw launches for a set of arguments: every argument check of the product and the whole launch geometry, as a function of the
+// addresses (their alignment and whether they are given), pitches and sizes alone.  gemm_nt_bf16_sw launches from this and
+// ts_gemm_nt_launch_config reports it; nothing here touches the device.
+struct GemmNtLaunch {
+  int n_mt, n_nt, blk_c;                           // row tiles (of `rows_per_tile`), column tiles of 256, column tiles per block of the tile walk
+  int grid_x, grid_y, threads;
+  int lds;                                         // dynamic LDS bytes
+  bool packed, silu;                               // gemm_nt_kernel<packed, packed ? 1 : 2, silu>
+  bool ep_f32;                                     // epilogue through the f32 staging (f32 result and / or residual); false: the bf16-only staged tile
+};
+static int gemm_nt_launch_config(const void* x, long long lda, long long sx, const void* w, long long ldw, const void* res, long long ld_res,
+                                 const void* y, long long ldc, const void* y16, long long ld16, long long sy, long long M, int N, int K, int act,
+                                 int batch, const void* wf, GemmNtLaunch* c) {
   if (!x || !w || (!y && !y16) || M <= 0 || N <= 0 || K <= 0 || batch <= 0 || act < 0 || act > 2) return TS_EINVAL;
   if (N % 32 || K % GKH || lda % 8 || ldw % 8 || ldw < K) return TS_EUNSUPPORTED;
   if ((y && (ldc % 4 || (reinterpret_cast<uintptr_t>(y) & 15))) || (y16 && (ld16 % 8 || (reinterpret_cast<uintptr_t>(y16) & 15))) ||
@@ -381,41 +390,54 @@ static int gemm_nt_bf16_sw(hipStream_t stream, const void* x, long long lda, lon
   if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(w) & 15) || (sx % 8)) return TS_EUNSUPPORTED;
   // 32-bit buffer offsets: the last row reads up to ((M - 1) lda + K) elements (overlapping conv rows have K > lda)
   if (((M - 1) * lda + K) * 2 >= (1ll << 31) - 1 || ((long long)(N - 1) * ldw + K) * 2 >= (1ll << 31) - 1) return TS_EUNSUPPORTED;
+  if (wf && (reinterpret_cast<uintptr_t>(wf) & 15)) return TS_EUNSUPPORTED;
+  c->packed = wf != nullptr;
+  c->silu = act == 2;
+  c->ep_f32 = y || res;
+  // packed weights: 128-row tiles, two workgroups per CU
+  const int tile_rows = c->packed ? 128 : GM;
+  const long long n_mt = (M + tile_rows - 1) / tile_rows;
+  c->n_nt = (N + GN - 1) / GN;
+  if (n_mt * c->n_nt > 0x7fffffffll || batch > 65535) return TS_EUNSUPPORTED;      // grid limits
+  c->n_mt = (int)n_mt;
+  c->blk_c = c->n_nt % 4 == 0 ? 4 : (c->n_nt % 3 == 0 ? 3 : (c->n_nt % 2 == 0 ? 2 : 1));
+  c->grid_x = c->n_mt * c->n_nt;
+  c->grid_y = batch;
+  c->threads = c->packed ? 256 : 512;
+  c->lds = c->packed ? 4 * 128 * 144 : GEMM_LDS;
+  return TS_OK;
+}
+
+// wf: w in fragment order (gemm_nt_pack_w) or null
+static int gemm_nt_bf16_sw(hipStream_t stream, const void* x, long long lda, long long sx, const void* w, long long ldw, const float* bias,
+                           const float* res, long long ld_res, float* y, long long ldc, void* y16, long long ld16, long long sy, long long M, int N, int K,
+                           int act, int batch, const void* wf, long long sw) {
+  GemmNtLaunch c{};
+  const int cst = gemm_nt_launch_config(x, lda, sx, w, ldw, res, ld_res, y, ldc, y16, ld16, sy, M, N, K, act, batch, wf, &c);
+  if (cst != TS_OK) return cst;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return TS_EINVAL;
-  static bool attr[2][64] = {};     // the attribute belongs to the (function, device) pair
-  const int silu = act == 2 ? 1 : 0;
-  if (!attr[silu][dev]) {
-    if (hipFuncSetAttribute(silu ? reinterpret_cast<const void*>(gemm_nt_kernel<false, 2, true>) : reinterpret_cast<const void*>(gemm_nt_kernel<false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS) != hipSuccess)
-      return TS_EUNSUPPORTED;
-    attr[silu][dev] = true;
+  const int silu = c.silu ? 1 : 0;
+  const void* const fn = c.packed ? (silu ? reinterpret_cast<const void*>(gemm_nt_kernel<true, 1, true>) : reinterpret_cast<const void*>(gemm_nt_kernel<true, 1>))
+                                  : (silu ? reinterpret_cast<const void*>(gemm_nt_kernel<false, 2, true>) : reinterpret_cast<const void*>(gemm_nt_kernel<false>));
+  static bool attr[2][2][64] = {};  // the attribute belongs to the (function, device) pair
+  if (!attr[c.packed ? 1 : 0][silu][dev]) {
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, c.lds) != hipSuccess) return TS_EUNSUPPORTED;
+    attr[c.packed ? 1 : 0][silu][dev] = true;
   }
-  if (wf && (reinterpret_cast<uintptr_t>(wf) & 15)) return TS_EUNSUPPORTED;
   GemmArgs a;
   a.x = static_cast<const unsigned short*>(x); a.w = static_cast<const unsigned short*>(w); a.wf = static_cast<const unsigned short*>(wf); a.bias = bias; a.res = res; a.y = y;
   a.y16 = static_cast<unsigned short*>(y16);
   a.lda = lda; a.ldw = ldw; a.ld_res = ld_res; a.ldc = ldc; a.ld16 = ld16; a.sx = sx; a.sy = sy; a.sw = sw;
   a.M = (int)M; a.N = N; a.K = K; a.act = act == 1 ? 1 : 0;
-  a.n_mt = (int)((M + GM - 1) / GM); a.n_nt = (N + GN - 1) / GN;
-  a.blk_c = a.n_nt % 4 == 0 ? 4 : (a.n_nt % 3 == 0 ? 3 : (a.n_nt % 2 == 0 ? 2 : 1));
+  a.n_mt = c.n_mt; a.n_nt = c.n_nt; a.blk_c = c.blk_c;
   (void)hipGetLastError();
-  const dim3 grid((unsigned)(a.n_mt * a.n_nt), (unsigned)batch);
-  if (wf) {                                        // packed weights: 128-row tiles, two workgroups per CU
-    constexpr int LDS_H = 4 * 128 * 144;
-    static bool attr_h[2][64] = {};
-    if (!attr_h[silu][dev]) {
-      if (hipFuncSetAttribute(silu ? reinterpret_cast<const void*>(gemm_nt_kernel<true, 1, true>) : reinterpret_cast<const void*>(gemm_nt_kernel<true, 1>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_H) != hipSuccess)
-        return TS_EUNSUPPORTED;
-      attr_h[silu][dev] = true;
-    }
-    a.n_mt = (int)((M + 127) / 128);
-    const dim3 grid_h((unsigned)(a.n_mt * a.n_nt), (unsigned)batch);
-    if (silu) hipLaunchKernelGGL((gemm_nt_kernel<true, 1, true>), grid_h, dim3(256), LDS_H, stream, a);
-    else hipLaunchKernelGGL((gemm_nt_kernel<true, 1>), grid_h, dim3(256), LDS_H, stream, a);
-  } else if (silu) hipLaunchKernelGGL((gemm_nt_kernel<false, 2, true>), grid, dim3(512), GEMM_LDS, stream, a);
-  else hipLaunchKernelGGL(gemm_nt_kernel<false>, grid, dim3(512), GEMM_LDS, stream, a);
+  const dim3 grid((unsigned)c.grid_x, (unsigned)c.grid_y), block((unsigned)c.threads);
+  if (c.packed) {
+    if (silu) hipLaunchKernelGGL((gemm_nt_kernel<true, 1, true>), grid, block, c.lds, stream, a);
+    else hipLaunchKernelGGL((gemm_nt_kernel<true, 1>), grid, block, c.lds, stream, a);
+  } else if (silu) hipLaunchKernelGGL((gemm_nt_kernel<false, 2, true>), grid, block, c.lds, stream, a);
+  else hipLaunchKernelGGL(gemm_nt_kernel<false>, grid, block, c.lds, stream, a);
   return hip_status(hipGetLastError());
 }
 
@@ -461,4 +483,20 @@ extern "C" int ts_gemm_nt_bf16_packed(const void* x, int64_t lda, const void* w,
                                       int32_t gelu, void* stream) {
   if (!w_frag || lda < 0 || ldw < k || (y && ldc < n) || (y_bf16 && ld16 < n) || (res && ld_res < n)) return TS_EINVAL;
   return ts::gemm_nt_bf16((hipStream_t)stream, x, lda, 0, w, ldw, bias, res, ld_res, y, ldc, y_bf16, ld16, 0, rows, n, k, gelu, 1, w_frag);
+}
+
+/* what ts_gemm_nt_bf16 (w_frag NULL) / ts_gemm_nt_bf16_packed would launch, act by code as ts_conformer_linear_fwd; see include/thunder_speech_amd.h */
+extern "C" int ts_gemm_nt_launch_config(const void* x, int64_t lda, const void* w, int64_t ldw, const void* w_frag, const void* res, int64_t ld_res,
+                                        const void* y, int64_t ldc, const void* y_bf16, int64_t ld16, int64_t rows, int32_t n, int32_t k, int32_t act,
+                                        int32_t batch, int32_t* n_mt, int32_t* n_nt, int32_t* blk_c, int32_t* grid_x, int32_t* grid_y, int32_t* threads,
+                                        int32_t* lds_bytes, int32_t* instantiation, int32_t* epilogue) {
+  if (!n_mt || !n_nt || !blk_c || !grid_x || !grid_y || !threads || !lds_bytes || !instantiation || !epilogue) return TS_EINVAL;
+  if (lda < 0 || ldw < k || (y && ldc < n) || (y_bf16 && ld16 < n) || (res && ld_res < n)) return TS_EINVAL;
+  ts::GemmNtLaunch c{};
+  const int st = ts::gemm_nt_launch_config(x, lda, 0, w, ldw, res, ld_res, y, ldc, y_bf16, ld16, 0, rows, n, k, act, batch, w_frag, &c);
+  if (st != TS_OK) return st;
+  *n_mt = c.n_mt; *n_nt = c.n_nt; *blk_c = c.blk_c; *grid_x = c.grid_x; *grid_y = c.grid_y; *threads = c.threads; *lds_bytes = c.lds;
+  *instantiation = (c.packed ? TS_GEMM_NT_PACKED_HALF_TILE : TS_GEMM_NT_LDS_TWO_ROW) + (c.silu ? 1 : 0);
+  *epilogue = c.ep_f32 ? TS_GEMM_NT_EPILOGUE_F32 : TS_GEMM_NT_EPILOGUE_BF16;
+  return TS_OK;
 }
