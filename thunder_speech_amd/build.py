@@ -34,7 +34,8 @@ def needs_build() -> bool:
     out = lib_path()
     if not os.path.exists(out):
         return True
-    deps = sources() + glob.glob(os.path.join(PKG, "csrc", "*.hpp")) + glob.glob(os.path.join(ROOT, "include", "*.h"))
+    deps = sources() + glob.glob(os.path.join(PKG, "csrc", "*.hpp")) + glob.glob(os.path.join(ROOT, "include", "*.h")) + \
+        glob.glob(os.path.join(ROOT, "include", "thunder_speech_amd", "*.h"))
     return any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps)
 
 
@@ -97,7 +98,8 @@ def build_asan(verbose: bool = True) -> str:
         obj = os.path.join(bdir, os.path.basename(src) + ".o")
         objs.append(obj)
         if os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(d) for d in [src] + glob.glob(os.path.join(PKG, "csrc", "*.hpp")) +
-                                                                 glob.glob(os.path.join(ROOT, "include", "*.h"))):
+                                                                 glob.glob(os.path.join(ROOT, "include", "*.h")) +
+                                                                 glob.glob(os.path.join(ROOT, "include", "thunder_speech_amd", "*.h"))):
             continue
         cmd = [hipcc, f"--offload-arch={ARCH}", "-O2", "-g", "-std=c++17", "-fPIC", "-fsanitize=address,undefined", "-Wno-option-ignored",
                "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc"),

@@ -111,6 +111,11 @@ static inline int gemm_nt(hipStream_t stream, bool bf16, long long m, int n, int
   return gemm_f32(stream, bf16, x, lda, 1, sx, 0, w, 1, ldw, sw, 0, y, ldc, sy, y16, nullptr, (int)m, n, k, 1, batch, beta != 0.f);
 }
 
+// csrc/w2v_posconv.hip: out [B][T][C] f32 = grouped conv of src (bf16 operands) on the matrix-core positional-conv kernel, nothing added; c / groups == 64,
+// `front` zero rows in front of each clip; the caller has checked the arguments (csrc/posconv_stack_train.hip)
+int posconv_raw_conv(hipStream_t stream, const float* src, int batch, int t, int c, const void* w_taps_bf16, int kernel, int groups, int front, float* out,
+                     void* workspace);
+
 // compute units of the current device (one process per GPU: looked up once)
 inline int cu_count() {
   static int n_cu = 0;

@@ -6,6 +6,7 @@
 //   ts_w2v_groupconv_fwd   y = conv(x) + b, same padding: a layer of data2vec-audio's stacked positional convs (per-tap GEMMs)
 //   ts_w2v_posconv_train   fine-tuning forward (also saves the conv result z) and data gradient (the same product over the flipped taps)
 //   ts_w2v_posconv_wgrad   fine-tuning weight gradient, w2v_posconv_wgrad_kernel
+//   posconv_raw_conv       the conv alone (the kernel's raw-accumulator epilogue), behind ts_posconv_stack_conv of csrc/posconv_stack_train.hip
 #include "w2v_rows.hpp"
 
 namespace ts {
@@ -64,6 +65,9 @@ struct PcArgs {
   int plain;                       // training, data gradient: y = x + conv (no bias, no GELU)
 };
 
+// RAW: the third epilogue, out = conv(src) -- the accumulator as it is, no bias, no GELU, no residual (ts_posconv_stack_conv: a layer of data2vec-audio's
+// positional stack in training, whose bias + LayerNorm + GELU are a row kernel of csrc/posconv_stack_train.hip).  <false> is the kernel as it was.
+template <bool RAW>
 __global__ __launch_bounds__(256) void w2v_posconv_mfma_kernel(const PcArgs a) {
   extern __shared__ __attribute__((aligned(16))) char win[];                  // [PC_TT + k - 1][PC_PITCH]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -117,7 +121,8 @@ __global__ __launch_bounds__(256) void w2v_posconv_mfma_kernel(const PcArgs a) {
       const int t = t0 + wm * 64 + 32 * mt + 8 * (i >> 2) + 4 * half + (i & 3);
       if (t < a.t) {
         const size_t o = ((size_t)b * a.t + t) * a.c + co;
-        if (a.plain) a.y[o] = a.x[o] + acc[mt][i];
+        if constexpr (RAW) a.y[o] = acc[mt][i];
+        else if (a.plain) a.y[o] = a.x[o] + acc[mt][i];
         else {
           if (a.z) a.z[o] = acc[mt][i];
           a.y[o] = a.x[o] + gelu_erf(acc[mt][i] + bv);
@@ -239,6 +244,21 @@ __global__ __launch_bounds__(256) void w2v_posconv_wgrad_kernel(const PwArgs a) 
 
 using namespace ts;
 
+// out = conv(src) on w2v_posconv_mfma_kernel<true>; the arguments were checked by ts_posconv_stack_conv (csrc/posconv_stack_train.hip), its only caller.
+// `front` zero rows in front of each clip in the padded bf16 copy (workspace: ts_w2v_posconv_train_workspace bytes).
+int ts::posconv_raw_conv(hipStream_t stream, const float* src, int batch, int t, int c, const void* w_taps_bf16, int kernel, int groups, int front, float* out,
+                         void* workspace) {
+  const int prow = t + kernel;
+  unsigned short* const xp = static_cast<unsigned short*>(workspace);
+  const long long total = ((long long)batch * prow + 1) * c;
+  hipLaunchKernelGGL(posconv_pad16_kernel, dim3(nblk(total / 4)), dim3(256), 0, stream, src, xp, t, c, prow, front, total);
+  PcArgs pa{};
+  pa.xp = xp; pa.w = static_cast<const unsigned short*>(w_taps_bf16); pa.y = out;
+  pa.t = t; pa.c = c; pa.k = kernel; pa.groups = groups;
+  hipLaunchKernelGGL(w2v_posconv_mfma_kernel<true>, dim3((t + PC_TT - 1) / PC_TT, groups, batch), dim3(256), (size_t)(PC_TT + kernel - 1) * PC_PITCH, stream, pa);
+  return hip_status(hipGetLastError());
+}
+
 extern "C" int64_t ts_w2v_posconv_workspace_bytes(int32_t batch, int32_t t, int32_t c, int32_t kernel) {
   if (batch <= 0 || t <= 0 || c <= 0 || kernel <= 0) return TS_EINVAL;
   return (int64_t)2 * batch * (t + kernel) * c * sizeof(float);
@@ -263,7 +283,7 @@ static int posconv_impl(const float* x, int32_t batch, int32_t t, int32_t c, con
     PcArgs pa{};
     pa.xp = reinterpret_cast<const unsigned short*>(xp); pa.w = static_cast<const unsigned short*>(w_taps); pa.bias = bias; pa.x = x; pa.y = y;
     pa.t = t; pa.c = c; pa.k = kernel; pa.groups = groups;
-    hipLaunchKernelGGL(w2v_posconv_mfma_kernel, dim3((t + PC_TT - 1) / PC_TT, groups, batch), dim3(256), win_lds, stream, pa);
+    hipLaunchKernelGGL(w2v_posconv_mfma_kernel<false>, dim3((t + PC_TT - 1) / PC_TT, groups, batch), dim3(256), win_lds, stream, pa);
     return hip_status(hipGetLastError());
   }
   // all clips at once: output row r (over the padded row space) = sum_j xp[r + j] W_j^T, per group; rows between clips are waste
@@ -336,6 +356,6 @@ extern "C" int ts_w2v_posconv_train(const float* src, const float* res, int32_t 
   PcArgs pa{};
   pa.xp = xp; pa.w = static_cast<const unsigned short*>(w_taps_bf16); pa.bias = backward ? nullptr : bias; pa.x = res; pa.y = y;
   pa.t = t; pa.c = c; pa.k = kernel; pa.groups = groups; pa.z = backward ? nullptr : z; pa.plain = backward ? 1 : 0;
-  hipLaunchKernelGGL(w2v_posconv_mfma_kernel, dim3((t + PC_TT - 1) / PC_TT, groups, batch), dim3(256), win_lds, stream, pa);
+  hipLaunchKernelGGL(w2v_posconv_mfma_kernel<false>, dim3((t + PC_TT - 1) / PC_TT, groups, batch), dim3(256), win_lds, stream, pa);
   return hip_status(hipGetLastError());
 }

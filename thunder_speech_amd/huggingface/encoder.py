@@ -49,6 +49,9 @@ def feat_extract_output_lengths(conv_kernel, conv_stride, lengths: torch.Tensor,
 # (inference only): the wav2vec2 front end and adapter around conformer blocks (huggingface/conformer.py, csrc/conformer.hip,
 # include/thunder_speech_amd_conformer.h).  Others (sew's squeezed encoder, sew-d, the conformer's relative-position variant ...) have layers this
 # library holds no kernels for and raise.
+# Fine-tuning (huggingface/train.py, TRAINABLE_MODEL_TYPES): every family above but the conformer.  hubert, unispeech and unispeech-sat train on the
+# wav2vec2 chain (f32 and mixed precision); data2vec-audio on it with one autograd node per layer of its positional stack (PosConvStackLayer,
+# csrc/posconv_stack_train.hip, include/thunder_speech_amd/posconv_stack_train.h); wavlm in mixed precision only.
 SUPPORTED_MODEL_TYPES = ("wav2vec2", "hubert", "data2vec-audio", "unispeech", "unispeech-sat", "wavlm", "wav2vec2-conformer")
 CONFORMER_ACTIVATIONS = ("swish", "silu", "gelu")
 
@@ -510,6 +513,11 @@ class HuggingFaceEncoderAdapt(nn.Module):
         self.original_encoder = encoder
         if hasattr(self.original_encoder, "freeze_feature_encoder"):
             self.original_encoder.freeze_feature_encoder()
+        elif hasattr(getattr(self.original_encoder, "feature_extractor", None), "_freeze_parameters"):
+            # HubertModel and UniSpeechSatModel have no freeze_feature_encoder (only their ForCTC wrappers do), so the reference leaves their conv
+            # feature extractor trainable.  The training path here has no backward for those convolutions and refuses an unfrozen one by name:
+            # freeze it the way freeze_feature_encoder would, so that .train() works on a loaded checkpoint of either family
+            self.original_encoder.feature_extractor._freeze_parameters()
         self.mask_input = mask_input
         self._cache = _PackedCache()
         _check_config(encoder.config)

@@ -5,6 +5,8 @@ WavLMAttentionFused).  In mixed precision the attention core is fused at head_di
 (AttentionFused80, ts_mms_attention_train_* of csrc/mms_train.hip on the head_dim 80 kernels of csrc/w2v_attn_train.hip: the XLS-R 1B geometry); every other head dimension, and f32 training, take the materialised Attention node.
 MMS checkpoints (config.adapter_attn_dim) train adapter-only: the base frozen (HuggingFaceEncoderAdapt.adapter_finetuning), the attention adapter
 behind every layer one fused node (AttnAdapter, csrc/mms_adapter_train.hip).
+`HubertModel`, `UniSpeechModel` and `UniSpeechSatModel` train on the wav2vec2 chain as it is (HuBERT's feature-projection LayerNorm is optional);
+`Data2VecAudioModel` trains on it with its stacked positional convs as one node per layer (PosConvStackLayer, csrc/posconv_stack_train.hip).
 
 The reference fine-tunes HuggingFace CTC checkpoints through `BaseCTCModule.training_step` (src/thunder/module.py:102-127) with the conv feature
 extractor frozen (`_HuggingFaceEncoderAdapt.__init__`, src/thunder/huggingface/compatibility.py:27-28 -> `freeze_feature_encoder()`); autograd
@@ -748,6 +750,94 @@ class PosConvGelu(torch.autograd.Function):
         return dx, dwk, db
 
 
+class PosConvStackLayer(torch.autograd.Function):
+    """a = gelu(LayerNorm_no_affine(grouped_conv1d(x, w, padding = k // 2)[..., :T] + b; eps 1e-5)): one layer of Data2VecAudioPositionalConvEmbedding
+    (csrc/posconv_stack_train.hip, include/thunder_speech_amd/posconv_stack_train.h).  wk [k][groups][out][in] f32 as in PosConvGelu (data2vec's conv
+    weights are plain parameters: a permuted view, so autograd carries d wk straight back to `conv.weight`); x [B, T, C] time-major.
+    Mixed precision at 64 channels per group (data2vec-audio-large): the conv and its data gradient on the matrix-core kernel's raw-accumulator
+    epilogue (ts_posconv_stack_conv), the weight gradient on ts_w2v_posconv_wgrad.  Everything else (f32 training, other group widths: data2vec-audio-base
+    has 48): the three products as one f32 GEMM each over a zero-padded copy, as PosConvGelu's f32 branch.  Bias + LayerNorm + GELU are one fused row
+    launch forward and one (+ an ordered sum for the bias gradient) backward in both branches; the node keeps z and recomputes the row statistics."""
+    EPS = 1e-5                                           # nn.LayerNorm's default: the layer's norm is built without config.layer_norm_eps
+
+    @staticmethod
+    def forward(ctx, x, wk, bias):
+        x, wk, bias = _f32c(x), _f32c(wk), _f32c(bias)
+        b, t, c = x.shape
+        k, g, cg, _ = wk.shape
+        L = _lib.lib()
+        tp = t + k
+        ctx.mixed = k > 1 and PosConvGelu._mixed_ok(k, cg)
+        z = torch.empty_like(x)
+        if ctx.mixed:
+            w16 = wk.to(torch.bfloat16)
+            ws = torch.empty(L.ts_posconv_stack_conv_workspace(b, t, c, k), dtype=torch.uint8, device=x.device)
+            _lib.check(L.ts_posconv_stack_conv(x.data_ptr(), b, t, c, w16.data_ptr(), k, g, 0, z.data_ptr(), ws.data_ptr(), _s(x)), "ts_posconv_stack_conv")
+            kept = x
+        else:
+            xp = torch.empty(b, tp, c, dtype=torch.float32, device=x.device)
+            _lib.check(L.ts_w2v_pad_rows(x.data_ptr(), xp.data_ptr(), b, t, tp, k // 2, c, 0, _s(x)), "ts_w2v_pad_rows")
+            m = b * tp - k                                                   # rows of the padded row space that have all k taps
+            zp = torch.zeros(b, tp, c, dtype=torch.float32, device=x.device)
+            # zp[r][g cg + o] = sum_j sum_i xp[r + j][g cg + i] wk[j][g][o][i]
+            _gemm(xp, c, 1, wk, 1, cg, zp, c, m, cg, cg, sa=cg, ska=c, sb=cg * cg, skb=g * cg * cg, sc=cg, nkb=k, batch=g)
+            _lib.check(L.ts_w2v_pad_rows(zp.data_ptr(), z.data_ptr(), b, t, tp, 0, c, 1, _s(x)), "ts_w2v_pad_rows")
+            kept = xp
+        a = torch.empty_like(x)
+        _lib.check(L.ts_posconv_stack_norm_gelu_fwd(z.data_ptr(), bias.data_ptr(), PosConvStackLayer.EPS, b * t, c, a.data_ptr(), _s(x)),
+                   "ts_posconv_stack_norm_gelu_fwd")
+        ctx.save_for_backward(kept, z, wk, bias)
+        ctx.geom = (b, t, c)
+        return a
+
+    @staticmethod
+    def backward(ctx, da):
+        kept, z, wk, bias = ctx.saved_tensors
+        b, t, c = ctx.geom
+        k, g, cg, _ = wk.shape
+        da = _f32c(da)
+        L = _lib.lib()
+        tp = t + k
+        m = b * tp - k
+        dz = torch.empty_like(da)
+        db = torch.empty(c, dtype=torch.float32, device=da.device)
+        ws = torch.empty(L.ts_posconv_stack_norm_gelu_bwd_workspace(b * t, c), dtype=torch.uint8, device=da.device)
+        _lib.check(L.ts_posconv_stack_norm_gelu_bwd(z.data_ptr(), bias.data_ptr(), da.data_ptr(), PosConvStackLayer.EPS, b * t, c, dz.data_ptr(), db.data_ptr(),
+                                                    ws.data_ptr(), _s(da)), "ts_posconv_stack_norm_gelu_bwd")
+        dx = dwk = None
+        if ctx.mixed:
+            x = kept
+            if ctx.needs_input_grad[0]:
+                # dx = conv^T(dz): the same kernel over dz with the taps flipped and each tap's [out][in] block transposed
+                wb16 = wk.flip(0).transpose(2, 3).contiguous().to(torch.bfloat16)
+                ws = torch.empty(L.ts_posconv_stack_conv_workspace(b, t, c, k), dtype=torch.uint8, device=da.device)
+                dx = torch.empty_like(da)
+                _lib.check(L.ts_posconv_stack_conv(dz.data_ptr(), b, t, c, wb16.data_ptr(), k, g, 1, dx.data_ptr(), ws.data_ptr(), _s(da)), "ts_posconv_stack_conv")
+            if ctx.needs_input_grad[1]:
+                dwk = torch.empty_like(wk)
+                ws = torch.empty(L.ts_w2v_posconv_wgrad_workspace(b, t, c, k), dtype=torch.uint8, device=da.device)
+                _lib.check(L.ts_w2v_posconv_wgrad(dz.data_ptr(), x.data_ptr(), b, t, c, k, g, dwk.data_ptr(), ws.data_ptr(), _s(da)), "ts_w2v_posconv_wgrad")
+            return dx, dwk, (db if ctx.needs_input_grad[2] else None)
+        xp = kept
+        # d zp in the padded row space behind k - 1 zero rows: dbuf[k - 1 + r] = d zp[r]
+        dbuf = torch.empty((k - 1) + b * tp, c, dtype=torch.float32, device=da.device)
+        dbuf[: k - 1].zero_()
+        dzp = dbuf[k - 1:].view(b, tp, c)
+        _lib.check(L.ts_w2v_pad_rows(dz.data_ptr(), dzp.data_ptr(), b, t, tp, 0, c, 0, _s(da)), "ts_w2v_pad_rows")
+        if ctx.needs_input_grad[0]:
+            # d xp[q][g cg + i] = sum_j' sum_o dbuf[q + j'][g cg + o] wk[k - 1 - j'][g][o][i]
+            dxp = torch.empty(b, tp, c, dtype=torch.float32, device=da.device)
+            _gemm(dbuf, c, 1, wk, cg, 1, dxp, c, b * tp, cg, cg, sa=cg, ska=c, sb=cg * cg, skb=-g * cg * cg, sc=cg, nkb=k, batch=g,
+                  b_off=(k - 1) * g * cg * cg)
+            dx = torch.empty_like(da)
+            _lib.check(L.ts_w2v_pad_rows(dxp.data_ptr(), dx.data_ptr(), b, t, tp, k // 2, c, 1, _s(da)), "ts_w2v_pad_rows")
+        if ctx.needs_input_grad[1]:
+            # d wk[j][g][o][i] = sum_r d zp[r][g cg + o] xp[r + j][g cg + i]   (rows between the clips hold d zp = 0)
+            dwk = torch.empty_like(wk)
+            _gemm(dzp, 1, c, xp, c, 1, dwk, cg, cg, cg, m, sa=cg, sa2=0, sb=cg, sb2=c, sc=cg * cg, sc2=g * cg * cg, batch=g, batch2=k)
+        return dx, dwk, (db if ctx.needs_input_grad[2] else None)
+
+
 def compute_mask_indices(batch: int, t: int, mask_prob: float, mask_length: int, lengths=None, min_masks: int = 0) -> np.ndarray:
     """SpecAugment-style time masks of transformers' `_compute_mask_indices` (modeling_wav2vec2.py; the published algorithm, numpy's global
     RNG like the original): per clip, `int(mask_prob * len / mask_length + eps)` spans (at least `min_masks`) of `mask_length` frames at distinct
@@ -794,6 +884,9 @@ def train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
         _MIXED = False
 
 
+TRAINABLE_MODEL_TYPES = ("wav2vec2", "wavlm", "hubert", "unispeech", "unispeech-sat", "data2vec-audio")
+
+
 def refuse_untrainable(adapt, mixed: bool) -> None:
     """Raise NotImplementedError, by name, for a configuration this training path has no backward for (no device work: the WavLM adapter calls it
     before its GPU check).  `mixed`: train_precision == "bf16"."""
@@ -806,10 +899,10 @@ def refuse_untrainable(adapt, mixed: bool) -> None:
         # the gated relative-position attention trains on the fused mixed-precision kernels only (csrc/wavlm_train.hip): there is no
         # materialised-probability WavLM path to fall back to
         raise NotImplementedError('HIP fine-tuning path: model_type=\'wavlm\' trains with train_precision="bf16" and the fused attention only')
-    if model_type not in ("wav2vec2", "wavlm"):
-        # hubert / data2vec-audio run the inference path (huggingface/encoder.py); their training-mode forward (no feature-projection LayerNorm,
-        # stacked positional convs) has no autograd nodes here
-        raise NotImplementedError(f"HIP fine-tuning path: model_type={cfg.model_type!r} is inference-only (wav2vec2 and wavlm checkpoints fine-tune)")
+    if model_type not in TRAINABLE_MODEL_TYPES:
+        # wav2vec2-conformer runs the inference path only (huggingface/conformer.py): its blocks have no autograd nodes here.  hubert, unispeech and
+        # unispeech-sat train on the wav2vec2 chain (hubert's feature-projection LayerNorm is optional), data2vec-audio on it with PosConvStackLayer
+        raise NotImplementedError(f"HIP fine-tuning path: model_type={cfg.model_type!r} is inference-only ({', '.join(TRAINABLE_MODEL_TYPES)} checkpoints fine-tune)")
     if getattr(cfg, "add_adapter", False):
         raise NotImplementedError("HIP fine-tuning path: add_adapter=True is inference-only (the adapter layers have no backward here)")
     if has_attn_adapters(cfg):
@@ -845,7 +938,9 @@ def _train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
     c, heads = int(cfg.hidden_size), int(cfg.num_attention_heads)
     eps = float(cfg.layer_norm_eps)
     fp, en = enc.feature_projection, enc.encoder
-    h = LayerNorm.apply(feats, None, fp.layer_norm.weight, fp.layer_norm.bias, eps)
+    h = feats
+    if getattr(fp, "layer_norm", None) is not None:         # HubertFeatureProjection has none with feat_proj_layer_norm=False (hubert-base)
+        h = LayerNorm.apply(h, None, fp.layer_norm.weight, fp.layer_norm.bias, eps)
     h = linear(h, fp.projection.weight, fp.projection.bias)
     h = dropout(h, float(cfg.feat_proj_dropout))
     key_len = None
@@ -858,21 +953,33 @@ def _train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
             h = MaskEmbed.apply(h, torch.from_numpy(m.astype(np.uint8)).to(dev), enc.masked_spec_embed)
     if key_len is not None:
         h = MaskRows.apply(h, key_len)
-    # positional conv: weight norm over dim 2 on the parameters (torch ops on [C][C/g][k] only), conv + GELU + residual on the kernels
-    conv = en.pos_conv_embed.conv
-    if hasattr(conv, "parametrizations"):
-        wg, wv = conv.parametrizations.weight.original0, conv.parametrizations.weight.original1
-    else:
-        wg, wv = conv.weight_g, conv.weight_v
     g = int(cfg.num_conv_pos_embedding_groups)
-    kpos = int(cfg.num_conv_pos_embeddings)
-    w_eff = wg * wv / wv.pow(2).sum(dim=(0, 1), keepdim=True).sqrt()
-    wk = w_eff.view(g, c // g, c // g, kpos).permute(3, 0, 1, 2).contiguous()
-    h = PosConvGelu.apply(h, wk, conv.bias)
-    stable = bool(getattr(cfg, "do_stable_layer_norm", False))
+    d2v = getattr(cfg, "model_type", "wav2vec2") == "data2vec-audio"
+    stable = bool(getattr(cfg, "do_stable_layer_norm", False)) and not d2v       # Data2VecAudioEncoder is post-LN only
     p_hid, p_act, p_att = float(cfg.hidden_dropout), float(cfg.activation_dropout), float(cfg.attention_dropout)
-    if not stable:
-        h = LayerNorm.apply(h, None, en.layer_norm.weight, en.layer_norm.bias, eps)
+    if d2v:
+        # Data2VecAudioPositionalConvEmbedding: num_conv_pos_embeddings layers of conv (conv_pos_kernel_size taps, plain weights) -> affine-free
+        # LayerNorm -> GELU, one node each; NO row masking between them (transformers zeroes the padded rows once, in front of the stack, and from
+        # layer 2 on they are non-zero and reach the valid frames); then encoder.layer_norm(h + stack(h)) as the residual LayerNorm node
+        kpos = int(cfg.conv_pos_kernel_size)
+        p = h
+        for pl in en.pos_conv_embed.layers:
+            wk = pl.conv.weight.view(g, c // g, c // g, kpos).permute(3, 0, 1, 2).contiguous()
+            p = PosConvStackLayer.apply(p, wk, pl.conv.bias)
+        h = LayerNorm.apply(p, h, en.layer_norm.weight, en.layer_norm.bias, eps)
+    else:
+        # positional conv: weight norm over dim 2 on the parameters (torch ops on [C][C/g][k] only), conv + GELU + residual on the kernels
+        conv = en.pos_conv_embed.conv
+        if hasattr(conv, "parametrizations"):
+            wg, wv = conv.parametrizations.weight.original0, conv.parametrizations.weight.original1
+        else:
+            wg, wv = conv.weight_g, conv.weight_v
+        kpos = int(cfg.num_conv_pos_embeddings)
+        w_eff = wg * wv / wv.pow(2).sum(dim=(0, 1), keepdim=True).sqrt()
+        wk = w_eff.view(g, c // g, c // g, kpos).permute(3, 0, 1, 2).contiguous()
+        h = PosConvGelu.apply(h, wk, conv.bias)
+        if not stable:
+            h = LayerNorm.apply(h, None, en.layer_norm.weight, en.layer_norm.bias, eps)
     h = dropout(h, p_hid)
     rb = None
     if wavlm:
