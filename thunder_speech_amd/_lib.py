@@ -1,6 +1,7 @@
 """ctypes binding of the C ABI declared in include/thunder_speech_amd.h and its companions include/thunder_speech_amd_wavlm.h,
 include/thunder_speech_amd_wavlm_train.h, include/thunder_speech_amd_conformer.h, include/thunder_speech_amd_mms.h,
-include/thunder_speech_amd_mms_train.h, include/thunder_speech_amd_mms_adapter_train.h and include/thunder_speech_amd/posconv_stack_train.h.
+include/thunder_speech_amd_mms_train.h, include/thunder_speech_amd_mms_adapter_train.h, include/thunder_speech_amd/posconv_stack_train.h and
+thunder_speech_amd/abi/sew.h.
 
 The header is the only copy of the ABI: `read_header` derives every prototype, struct and TS_* constant from it and
 `lib()` applies the result, so a new entry point needs the header and its .hip definition and nothing here.  A C type
@@ -16,7 +17,7 @@ import os
 import re
 from typing import Optional
 
-from .build import ROOT, lib_path
+from .build import PKG, ROOT, lib_path
 
 HEADER = os.path.join(ROOT, "include", "thunder_speech_amd.h")
 WAVLM_HEADER = os.path.join(ROOT, "include", "thunder_speech_amd_wavlm.h")    # companion ABI, versioned on its own
@@ -27,6 +28,7 @@ MMS_HEADER = os.path.join(ROOT, "include", "thunder_speech_amd_mms.h")          
 MMS_TRAIN_HEADER = os.path.join(ROOT, "include", "thunder_speech_amd_mms_train.h")        # fifth companion (head_dim 80 fine-tuning), versioned on its own
 MMS_ADAPTER_TRAIN_HEADER = os.path.join(ROOT, "include", "thunder_speech_amd_mms_adapter_train.h")    # sixth companion (adapter fine-tuning), versioned on its own
 POSCONV_STACK_TRAIN_HEADER = os.path.join(ROOT, "include", "thunder_speech_amd", "posconv_stack_train.h")   # seventh companion (data2vec-audio fine-tuning), versioned on its own; new companions live in that directory
+SEW_HEADER = os.path.join(PKG, "abi", "sew.h")          # eighth companion (SEW inference), versioned on its own; inside the package (the header count of include/ is pinned)
 
 # Parameters and struct fields: these scalars, `[const] <struct>*` as POINTER(struct), every other pointer to one of
 # _POINTEES (const or not, any depth) as c_void_p.  Return types: _RETURNS only.
@@ -100,7 +102,9 @@ MMS_ADAPTER_TRAIN_SIGNATURES, _, MMS_ADAPTER_TRAIN_DEFINES = _read_installed_hea
 MMS_ADAPTER_TRAIN_ABI_VERSION = MMS_ADAPTER_TRAIN_DEFINES["TS_MMS_ADAPTER_TRAIN_ABI_VERSION"]
 POSCONV_STACK_TRAIN_SIGNATURES, _, POSCONV_STACK_TRAIN_DEFINES = _read_installed_header(POSCONV_STACK_TRAIN_HEADER)
 POSCONV_STACK_TRAIN_ABI_VERSION = POSCONV_STACK_TRAIN_DEFINES["TS_POSCONV_STACK_TRAIN_ABI_VERSION"]
-TcsDesc, FrontendDesc, WgradItem = STRUCTS["ts_tcs_desc"], STRUCTS["ts_frontend_desc"], STRUCTS["ts_wgrad_item"]
+SEW_SIGNATURES, _, SEW_DEFINES = _read_installed_header(SEW_HEADER)
+SEW_ABI_VERSION = SEW_DEFINES["TS_SEW_ABI_VERSION"]
+TcsDesc, FrontendDesc, WgradItem =STRUCTS["ts_tcs_desc"], STRUCTS["ts_frontend_desc"], STRUCTS["ts_wgrad_item"]
 TcsLaunch = STRUCTS["ts_tcs_launch"]
 EXPORTED_SYMBOLS = list(SIGNATURES)
 ABI_VERSION = DEFINES["TS_ABI_VERSION"]
@@ -129,11 +133,11 @@ def lib() -> C.CDLL:
     import torch  # noqa: F401  -- must initialise its bundled HIP runtime BEFORE our code object is loaded
     L = C.CDLL(path)
     missing = [s for s in EXPORTED_SYMBOLS + list(WAVLM_SIGNATURES) + list(WAVLM_TRAIN_SIGNATURES) + list(CONFORMER_SIGNATURES) + list(MMS_SIGNATURES) +
-               list(MMS_TRAIN_SIGNATURES) + list(MMS_ADAPTER_TRAIN_SIGNATURES) + list(POSCONV_STACK_TRAIN_SIGNATURES) if not hasattr(L, s)]
+               list(MMS_TRAIN_SIGNATURES) + list(MMS_ADAPTER_TRAIN_SIGNATURES) + list(POSCONV_STACK_TRAIN_SIGNATURES) + list(SEW_SIGNATURES) if not hasattr(L, s)]
     if missing:
         raise RuntimeError(f"thunder_speech_amd: {path} does not export {missing}; rebuild it")
     for name, (restype, argtypes) in {**SIGNATURES, **WAVLM_SIGNATURES, **WAVLM_TRAIN_SIGNATURES, **CONFORMER_SIGNATURES, **MMS_SIGNATURES,
-                                      **MMS_TRAIN_SIGNATURES, **MMS_ADAPTER_TRAIN_SIGNATURES, **POSCONV_STACK_TRAIN_SIGNATURES}.items():
+                                      **MMS_TRAIN_SIGNATURES, **MMS_ADAPTER_TRAIN_SIGNATURES, **POSCONV_STACK_TRAIN_SIGNATURES, **SEW_SIGNATURES}.items():
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     if L.ts_abi_version() != ABI_VERSION:
@@ -160,6 +164,9 @@ def lib() -> C.CDLL:
     if L.ts_posconv_stack_train_abi_version() != POSCONV_STACK_TRAIN_ABI_VERSION:
         raise RuntimeError(f"thunder_speech_amd: {path} reports positional-stack training ABI {L.ts_posconv_stack_train_abi_version()}, the header "
                            f"{POSCONV_STACK_TRAIN_HEADER} declares {POSCONV_STACK_TRAIN_ABI_VERSION}; rebuild it")
+    if L.ts_sew_abi_version() != SEW_ABI_VERSION:
+        raise RuntimeError(f"thunder_speech_amd: {path} reports SEW ABI {L.ts_sew_abi_version()}, the header {SEW_HEADER} "
+                           f"declares {SEW_ABI_VERSION}; rebuild it")
     _lib = L
     return L
 

@@ -8,7 +8,8 @@ difference); the arithmetic runs in `Wav2Vec2Plan`, which keeps packed fp32 devi
 call per stage.  Both published families (group-norm / post-LN: wav2vec2-base-960h, -large-960h; layer-norm / pre-LN: -large-lv60, xlsr);
 WavLM runs the same sequence with its gated relative-position attention (csrc/wavlm.hip, include/thunder_speech_amd_wavlm.h) in place of
 the wav2vec2 one (fine-tuning in mixed precision only: csrc/wavlm_train.hip); wav2vec2-conformer (rotary) runs conformer blocks behind the same
-front end (huggingface/conformer.py, inference only); MMS (config.adapter_attn_dim: an attention adapter behind every pre-LN layer) and the head_dim 80
+front end (huggingface/conformer.py, inference only); SEW runs the post-LN layers at 1 / squeeze_factor of the frame rate between csrc/sew.hip's
+squeeze and an upsampling GEMM (huggingface/sew.py, thunder_speech_amd/abi/sew.h, inference only); MMS (config.adapter_attn_dim: an attention adapter behind every pre-LN layer) and the head_dim 80
 of MMS-1B / XLS-R 1B run on csrc/mms.hip and the head_dim 80 kernel of csrc/w2v_attn.hip (include/thunder_speech_amd_mms.h, inference only); training mode (fine-tuning with the conv feature extractor frozen) runs
 through huggingface/train.py; no CPU fallback."""
 from __future__ import annotations
@@ -47,12 +48,13 @@ def feat_extract_output_lengths(conv_kernel, conv_stride, lengths: torch.Tensor,
 # norm, pre-LN): the wav2vec2 layers with WavLMAttention's gated relative-position bias in the attention core (csrc/wavlm.hip, head_dim 64 -- every
 # published WavLM -- fine-tuned with train_precision="bf16" only, csrc/wavlm_train.hip); wav2vec2-conformer with rotary position embeddings
 # (inference only): the wav2vec2 front end and adapter around conformer blocks (huggingface/conformer.py, csrc/conformer.hip,
-# include/thunder_speech_amd_conformer.h).  Others (sew's squeezed encoder, sew-d, the conformer's relative-position variant ...) have layers this
-# library holds no kernels for and raise.
+# include/thunder_speech_amd_conformer.h); sew (inference only): wav2vec2's post-LN layers at 1 / squeeze_factor of the frame rate between a
+# strided positional conv added to an average pool and an upsampling projection (huggingface/sew.py, csrc/sew.hip, thunder_speech_amd/abi/sew.h).
+# Others (sew-d's disentangled attention, the conformer's relative-position variant ...) have layers this library holds no kernels for and raise.
 # Fine-tuning (huggingface/train.py, TRAINABLE_MODEL_TYPES): every family above but the conformer.  hubert, unispeech and unispeech-sat train on the
 # wav2vec2 chain (f32 and mixed precision); data2vec-audio on it with one autograd node per layer of its positional stack (PosConvStackLayer,
 # csrc/posconv_stack_train.hip, include/thunder_speech_amd/posconv_stack_train.h); wavlm in mixed precision only.
-SUPPORTED_MODEL_TYPES = ("wav2vec2", "hubert", "data2vec-audio", "unispeech", "unispeech-sat", "wavlm", "wav2vec2-conformer")
+SUPPORTED_MODEL_TYPES = ("wav2vec2", "hubert", "data2vec-audio", "unispeech", "unispeech-sat", "wavlm", "wav2vec2-conformer", "sew")
 CONFORMER_ACTIVATIONS = ("swish", "silu", "gelu")
 
 
@@ -112,9 +114,29 @@ def has_attn_adapters(cfg) -> bool:
             and getattr(cfg, "model_type", "wav2vec2") == "wav2vec2")
 
 
+def _check_sew_config(cfg, bad: list) -> None:
+    """sew: head_dim 64 (the fused attention with key lengths), erf GELU throughout, no adapter (SEWModel has none)."""
+    heads, hidden, groups = int(cfg.num_attention_heads), int(cfg.hidden_size), int(cfg.num_conv_pos_embedding_groups)
+    if hidden != 64 * heads:
+        bad.append(f"model_type='sew' with head_dim={hidden // heads} (the attention kernel with key lengths takes head_dim 64, as every published SEW)")
+    if getattr(cfg, "hidden_act", "gelu") != "gelu":
+        bad.append(f"model_type='sew' with hidden_act={cfg.hidden_act!r} (gelu runs)")
+    if getattr(cfg, "feat_extract_activation", "gelu") != "gelu":
+        bad.append(f"model_type='sew' with feat_extract_activation={cfg.feat_extract_activation!r} (gelu runs: the conv feature extractor, the positional "
+                   "conv and the upsampler share it)")
+    if int(getattr(cfg, "squeeze_factor", 2)) < 1:
+        bad.append(f"model_type='sew' with squeeze_factor={cfg.squeeze_factor}")
+    if groups < 1 or hidden % groups:
+        bad.append(f"model_type='sew' with hidden_size={hidden} not a multiple of num_conv_pos_embedding_groups={groups}")
+    if getattr(cfg, "add_adapter", False):
+        bad.append("model_type='sew' with add_adapter=True (SEWModel has no adapter)")
+
+
 def _check_config(cfg) -> None:
     bad = []
-    if getattr(cfg, "model_type", "wav2vec2") not in SUPPORTED_MODEL_TYPES:
+    if getattr(cfg, "model_type", "wav2vec2") == "sew-d":
+        bad.append(f"model_type='sew-d' (its disentangled attention has no HIP kernel; supported: {', '.join(SUPPORTED_MODEL_TYPES)})")
+    elif getattr(cfg, "model_type", "wav2vec2") not in SUPPORTED_MODEL_TYPES:
         bad.append(f"model_type={cfg.model_type!r} (supported: {', '.join(SUPPORTED_MODEL_TYPES)})")
     if getattr(cfg, "conv_pos_batch_norm", False):
         bad.append("conv_pos_batch_norm=True")
@@ -124,6 +146,11 @@ def _check_config(cfg) -> None:
         _check_conformer_config(cfg, bad)
         if bad:
             raise NotImplementedError("wav2vec2-conformer HIP path: unsupported configuration: " + ", ".join(bad))
+        return
+    if getattr(cfg, "model_type", "wav2vec2") == "sew":
+        _check_sew_config(cfg, bad)
+        if bad:
+            raise NotImplementedError("sew HIP path: unsupported configuration: " + ", ".join(bad))
         return
     if getattr(cfg, "hidden_act", "gelu") != "gelu" or getattr(cfg, "feat_extract_activation", "gelu") != "gelu":
         bad.append("activation != gelu")
@@ -205,25 +232,14 @@ class Wav2Vec2Plan:
         else:
             # weight_norm(dim=2): w[:, :, j] = g[j] v[:, :, j] / ||v[:, :, j]||
             p = "encoder.pos_conv_embed.conv."
-            if p + "parametrizations.weight.original0" in sd:
-                g, v = f(p + "parametrizations.weight.original0"), f(p + "parametrizations.weight.original1")
-            else:
-                g, v = f(p + "weight_g"), f(p + "weight_v")
-            w_eff = g * v / v.pow(2).sum(dim=(0, 1), keepdim=True).sqrt()                    # [C][C/g][k]
+            w_eff = self._weight_normed(sd, f, p)                                             # [C][C/g][k]
             self.pos_w = gw(w_eff.view(self.groups, cg, cg, self.kpos).permute(3, 0, 1, 2))   # [k][g][out][in]
             self.pos_b = f(p + "bias")
         self.enc_ln = (f("encoder.layer_norm.weight"), f("encoder.layer_norm.bias"))
         self._pack_adapter(cfg, sd, f)
         for i in range(self.n_layers):
             q = f"encoder.layers.{i}."
-            self.layers.append(dict(
-                wqkv=gw(torch.cat([f(q + f"attention.{n}_proj.weight") for n in "qkv"], 0)),
-                bqkv=torch.cat([f(q + f"attention.{n}_proj.bias") for n in "qkv"], 0).contiguous(),
-                wo=gw(f(q + "attention.out_proj.weight")), bo=f(q + "attention.out_proj.bias"),
-                ln1=(f(q + "layer_norm.weight"), f(q + "layer_norm.bias")),
-                w1=gw(f(q + "feed_forward.intermediate_dense.weight")), b1=f(q + "feed_forward.intermediate_dense.bias"),
-                w2=gw(f(q + "feed_forward.output_dense.weight")), b2=f(q + "feed_forward.output_dense.bias"),
-                ln2=(f(q + "final_layer_norm.weight"), f(q + "final_layer_norm.bias"))))
+            self.layers.append(self._pack_layer(f, gw, q))
             if q + "adapter_layer.linear_1.weight" in sd:
                 # Wav2Vec2AttnAdapterLayer (MMS): LayerNorm (eps 1e-5) -> linear_1 [a][c] -> ReLU -> linear_2 [c][a], added to the residual stream
                 self.attn_adapter_keys += [q + "adapter_layer." + k for k in ("norm.weight", "norm.bias", "linear_1.weight", "linear_1.bias",
@@ -240,6 +256,27 @@ class Wav2Vec2Plan:
             self.nb, self.md = int(cfg.num_buckets), int(cfg.max_bucket_distance)
             self.rel_embed = f("encoder.layers.0.attention.rel_attn_embed.weight")                      # [num_buckets][H]
             self.abs_bucket = wavlm_bucket_table(self.nb, self.md).to(self.device).contiguous()
+
+    @staticmethod
+    def _weight_normed(sd, f, p: str) -> torch.Tensor:
+        """The effective weight [C][C/g][k] of the weight_norm(dim=2) conv under the key prefix `p`: w[:, :, j] = g[j] v[:, :, j] / ||v[:, :, j]||."""
+        if p + "parametrizations.weight.original0" in sd:
+            g, v = f(p + "parametrizations.weight.original0"), f(p + "parametrizations.weight.original1")
+        else:
+            g, v = f(p + "weight_g"), f(p + "weight_v")
+        return g * v / v.pow(2).sum(dim=(0, 1), keepdim=True).sqrt()
+
+    @staticmethod
+    def _pack_layer(f, gw, q: str) -> dict:
+        """The weights of the transformer layer under the key prefix `q` (wav2vec2's names; SEW's layers carry the same ones)."""
+        return dict(
+            wqkv=gw(torch.cat([f(q + f"attention.{n}_proj.weight") for n in "qkv"], 0)),
+            bqkv=torch.cat([f(q + f"attention.{n}_proj.bias") for n in "qkv"], 0).contiguous(),
+            wo=gw(f(q + "attention.out_proj.weight")), bo=f(q + "attention.out_proj.bias"),
+            ln1=(f(q + "layer_norm.weight"), f(q + "layer_norm.bias")),
+            w1=gw(f(q + "feed_forward.intermediate_dense.weight")), b1=f(q + "feed_forward.intermediate_dense.bias"),
+            w2=gw(f(q + "feed_forward.output_dense.weight")), b2=f(q + "feed_forward.output_dense.bias"),
+            ln2=(f(q + "final_layer_norm.weight"), f(q + "final_layer_norm.bias")))
 
     def _pack_projection(self, f, gw) -> None:
         """The feature projection: optional LayerNorm (config.layer_norm_eps), then the linear layer -- GEMM operand `gw`."""
@@ -411,8 +448,38 @@ class Wav2Vec2Plan:
             _lib.check(L.ts_w2v_posconv_fwd(h.data_ptr(), b, t, c, self.pos_w.data_ptr(), self.pos_b.data_ptr(), self.kpos, self.groups,
                                             self.prec, hp.data_ptr(), None, ws.data_ptr(), stream), "ts_w2v_posconv_fwd")
         del ws
+        attention = self._attention(L, stream, b, t, key_len)
+        if self.stable_ln:
+            # pre-LN family: h += attn(LN(h)); h += ffn(LN(h)); one LayerNorm after the last layer
+            assert pos_res is None
+            h = hp
+            y, x_op = None, None                        # LN(h) for what comes next, when the previous layer's adapter launch computed it
+            for i, lw in enumerate(self.layers):
+                if x_op is None:
+                    _, x_op = self._ln(L, stream, h, lw["ln1"], want_f32=False)
+                self._linear(L, stream, attention(x_op, lw), lw["wo"], lw["bo"], into=h)        # h += attn W^T (+ bias in the epilogue)
+                _, x_op = self._ln(L, stream, h, lw["ln2"], want_f32=False)
+                _, f1_op = self._linear(L, stream, x_op, lw["w1"], lw["b1"], act=1, want_op=True)
+                self._linear(L, stream, f1_op, lw["w2"], lw["b2"], into=h)
+                x_op = None
+                if "ad" in lw:
+                    # MMS: h += adapter(h); the launch also computes the LayerNorm that reads h next -- layer i + 1's, or the encoder's
+                    last = i + 1 == len(self.layers)
+                    y, x_op = self._attn_adapter(L, stream, h, lw["ad"], self.enc_ln if last else self.layers[i + 1]["ln1"], last)
+            if self.layers and "ad" in self.layers[-1]:
+                h = y
+            else:
+                h, _ = self._ln(L, stream, h, self.enc_ln, want_op=False)
+            return self._adapter(L, stream, h) if self.adapter else h
+        h, _ = self._post_ln_layers(L, stream, hp, pos_res, attention)
+        return self._adapter(L, stream, h) if self.adapter else h
+
+    def _attention(self, L, stream, b, t, key_len):
+        """The attention of one layer at `t` frames as a function (x_op, lw) -> context operand, with the workspace (WavLM: and the position bias)
+        every layer of this forward shares.  key_len: int32 [B] valid keys per clip on the device, or None."""
+        c = self.hidden
         if self.wavlm:
-            att_ws = self._buf(L.ts_wavlm_attention_workspace_bytes(b, t, self.heads, self.prec), dtype=torch.uint8)
+            att_ws =self._buf(L.ts_wavlm_attention_workspace_bytes(b, t, self.heads, self.prec), dtype=torch.uint8)
             rel_bias = self._buf(self.heads, 2 * t - 1)
             _lib.check(L.ts_wavlm_rel_bias(self.rel_embed.data_ptr(), self.abs_bucket.data_ptr(), self.nb, self.md, self.heads, t,
                                            rel_bias.data_ptr(), stream), "ts_wavlm_rel_bias")
@@ -421,8 +488,8 @@ class Wav2Vec2Plan:
         else:
             att_ws = self._buf(L.ts_w2v_attention_workspace_bytes(b, t, self.heads, self.prec), dtype=torch.uint8)
 
-        def attention(x_op):
-            # x_op: the attention's input as the QKV GEMM reads it -- WavLM's gate is computed from the same rows
+        def attention(x_op, lw):
+            # x_op: the attention's input as the QKV GEMM reads it -- WavLM's gate is computed from the same rows; lw: the layer's weights
             _, qkv_op = self._linear(L, stream, x_op, lw["wqkv"], lw["bqkv"], want_op=True)
             ctx_op = self._buf(b, t, c, dtype=torch.bfloat16 if self.prec else torch.float32)
             if self.wavlm:
@@ -439,38 +506,20 @@ class Wav2Vec2Plan:
                                               att_ws.data_ptr(), stream), "ts_w2v_attention_fwd")
             return ctx_op
 
-        if self.stable_ln:
-            # pre-LN family: h += attn(LN(h)); h += ffn(LN(h)); one LayerNorm after the last layer
-            assert pos_res is None
-            h = hp
-            y, x_op = None, None                        # LN(h) for what comes next, when the previous layer's adapter launch computed it
-            for i, lw in enumerate(self.layers):
-                if x_op is None:
-                    _, x_op = self._ln(L, stream, h, lw["ln1"], want_f32=False)
-                self._linear(L, stream, attention(x_op), lw["wo"], lw["bo"], into=h)        # h += attn W^T (+ bias in the epilogue)
-                _, x_op = self._ln(L, stream, h, lw["ln2"], want_f32=False)
-                _, f1_op = self._linear(L, stream, x_op, lw["w1"], lw["b1"], act=1, want_op=True)
-                self._linear(L, stream, f1_op, lw["w2"], lw["b2"], into=h)
-                x_op = None
-                if "ad" in lw:
-                    # MMS: h += adapter(h); the launch also computes the LayerNorm that reads h next -- layer i + 1's, or the encoder's
-                    last = i + 1 == len(self.layers)
-                    y, x_op = self._attn_adapter(L, stream, h, lw["ad"], self.enc_ln if last else self.layers[i + 1]["ln1"], last)
-            if self.layers and "ad" in self.layers[-1]:
-                h = y
-            else:
-                h, _ = self._ln(L, stream, h, self.enc_ln, want_op=False)
-            return self._adapter(L, stream, h) if self.adapter else h
-        # post-LN family: LayerNorm before the layers, after each residual add inside them
+        return attention
+
+    def _post_ln_layers(self, L, stream, hp, pos_res, attention):
+        """The post-LN family's chain (wav2vec2-base, hubert, data2vec-audio, wavlm-base, SEW at its squeezed frame rate): encoder.layer_norm over
+        hp (+ pos_res) before the layers, a LayerNorm after each residual add inside them.  -> (f32 result, its GEMM-operand copy)."""
         h, h_op = self._ln(L, stream, hp, self.enc_ln, res=pos_res)
         for lw in self.layers:
             # the projections accumulate into the residual stream inside the GEMM; their biases ride in the LayerNorm launch
-            self._linear(L, stream, attention(h_op), lw["wo"], None, into=h)
+            self._linear(L, stream, attention(h_op, lw), lw["wo"], None, into=h)
             h, h_op = self._ln(L, stream, h, lw["ln1"], xbias=lw["bo"])
             _, f1_op = self._linear(L, stream, h_op, lw["w1"], lw["b1"], act=1, want_op=True)
             self._linear(L, stream, f1_op, lw["w2"], None, into=h)
             h, h_op = self._ln(L, stream, h, lw["ln2"], xbias=lw["b2"])
-        return self._adapter(L, stream, h) if self.adapter else h
+        return h, h_op
 
     def _adapter(self, L, stream, h: torch.Tensor) -> torch.Tensor:
         """Wav2Vec2Adapter.forward (eval): [B, T, C] -> [B, T'', output_hidden_size]."""
@@ -528,6 +577,9 @@ class HuggingFaceEncoderAdapt(nn.Module):
         if getattr(cfg, "model_type", "wav2vec2") == "wav2vec2-conformer":
             from .conformer import ConformerPlan
             return self._cache.get(params, lambda: ConformerPlan(cfg, self.original_encoder.state_dict(), device, self.precision))
+        if getattr(cfg, "model_type", "wav2vec2") == "sew":
+            from .sew import SEWPlan
+            return self._cache.get(params, lambda: SEWPlan(cfg, self.original_encoder.state_dict(), device, self.precision))
         return self._cache.get(params, lambda: Wav2Vec2Plan(cfg, self.original_encoder.state_dict(), device, self.precision))
 
     def _plan_frozen(self, device) -> Wav2Vec2Plan:
@@ -577,6 +629,9 @@ class HuggingFaceEncoderAdapt(nn.Module):
         if self.training and getattr(self.original_encoder.config, "model_type", "wav2vec2") == "wav2vec2-conformer":
             # no conformer backward exists (BatchNorm in train mode, the depthwise conv, the rotary products): refused before any device work
             raise NotImplementedError("wav2vec2-conformer: fine-tuning is not implemented (inference only); use the module in eval mode")
+        if self.training and getattr(self.original_encoder.config, "model_type", "wav2vec2") == "sew":
+            # no backward exists for the strided positional conv, the pool or the upsampler: refused before any device work
+            raise NotImplementedError("sew: fine-tuning is not implemented (inference only); use the module in eval mode")
         if self.training and getattr(self.original_encoder.config, "model_type", "wav2vec2") == "wavlm" and self.train_precision != "bf16":
             # the gated relative-position attention trains on the fused mixed-precision kernels only (csrc/wavlm_train.hip); f32 fine-tuning would
             # need a materialised-probability path of its own
