@@ -58,8 +58,10 @@ def module_from_huggingface(model, feature_extractor, tokenizer=None) -> BaseCTC
         if hasattr(model, "lm_head"):
             decoder[2].load_state_dict(model.lm_head.state_dict())
     mask_input = bool(feature_extractor.return_attention_mask)
+    audio_transform = Wav2Vec2Preprocess(mask_input=mask_input)
+    audio_transform.sample_rate = int(getattr(feature_extractor, "sampling_rate", 16000))      # host-only record (BaseCTCModule.sample_rate)
     module = BaseCTCModule(encoder=HuggingFaceEncoderAdapt(model.base_model, mask_input=mask_input), decoder=decoder,
-                           text_transform=text_transform, audio_transform=Wav2Vec2Preprocess(mask_input=mask_input),
+                           text_transform=text_transform, audio_transform=audio_transform,
                            encoder_final_dimension=hidden)
     return module.eval()
 

@@ -200,6 +200,85 @@ class BaseCTCModule(_Base):
             _, collapsed, counts = greedy_decode(pred)
         return self.text_transform.decode_collapsed(collapsed, counts)
 
+    # ------------------------------------------------------------------------------------------------------------------
+    # "When was it said" (no reference counterpart): forced alignment of known transcripts and the spans of the greedy transcript, on the
+    # kernels of csrc/ctc_align.hip (ctc_align.py).  predict() / forward() above are untouched.
+    @property
+    def sample_rate(self) -> int:
+        """Samples per second of the waveforms the module takes (host only): the front end's `sample_rate` where it records one, else 16 000
+        (every checkpoint family this package loads)."""
+        return int(getattr(self.audio_transform, "sample_rate", 16000))
+
+    @property
+    def samples_per_frame(self) -> int:
+        """Waveform samples per frame of the logits (host only): frame f starts at f * samples_per_frame / sample_rate seconds.  Mel front
+        end: n_window_stride x the encoder's total stride; transformers families: prod(conv_stride) (SEW's squeeze and upsampler cancel),
+        times adapter_stride ** num_adapter_layers with add_adapter."""
+        cfg = getattr(getattr(self.encoder, "original_encoder", None), "config", None)
+        if cfg is not None:
+            n = 1
+            for s in cfg.conv_stride:
+                n *= int(s)
+            if getattr(cfg, "add_adapter", False):
+                n *= int(cfg.adapter_stride) ** int(cfg.num_adapter_layers)
+            return n
+        from .quartznet.blocks import MaskedConv1d
+        hops = [m.hop_length for m in self.audio_transform.modules() if hasattr(m, "hop_length")]
+        if len(hops) != 1:
+            raise NotImplementedError("samples_per_frame: the audio transform is neither the mel front end nor a transformers one")
+        n = int(hops[0])
+        for blk in self.encoder.children():
+            main = getattr(blk, "mconv", blk)                     # the main path of a block (its residual branch has strides of its own)
+            for m in main.modules():
+                if isinstance(m, MaskedConv1d):
+                    n *= int(m.stride)
+        return n
+
+    def _eval_logits(self, x: Tensor, lengths: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+        """(logits, output lengths) of the eval-mode forward under no_grad; lengths None: every clip is full length, as predict()."""
+        if not x.is_cuda:
+            raise RuntimeError("align / predict_spans: GPU tensors required (no CPU fallback)")
+        if lengths is None:
+            lengths = torch.full((x.shape[0],), x.shape[-1], dtype=torch.int32, device=x.device)
+        modes = [(m, m.training) for m in self.modules()]
+        if any(on for _, on in modes):
+            self.eval()
+        try:
+            with torch.no_grad():
+                logits, out_lengths = self(x, lengths)
+        finally:
+            if any(on for _, on in modes):                    # every submodule gets its own flag back (a frozen encoder stays in eval mode)
+                for m, on in modes:
+                    m.training = on
+                self.reset_inference_graphs()
+        if out_lengths is None:
+            out_lengths = torch.full((x.shape[0],), logits.shape[-1], dtype=torch.int32, device=x.device)
+        return logits, out_lengths
+
+    def align(self, x: Tensor, texts: List[str], lengths: Optional[Tensor] = None) -> List["AlignedClip"]:
+        """Forced alignment of `texts` to the clips `x` [batch, time]: per clip the score (sum of the best path's log-probabilities) and
+        one TokenSpan per token of the encoded transcript (token, start / end in seconds and in frames, log-probability).  A transcript that
+        does not fit its clip gives score -inf and no tokens instead of raising: one bad transcript does not fail a batch."""
+        from . import ctc_align as A
+        logits, out_lengths = self._eval_logits(x, lengths)
+        y, y_lengths = self.text_transform.encode(list(texts), device=x.device)
+        al = A.forced_align(logits, y, out_lengths, y_lengths, self.text_transform.vocab.blank_idx)
+        ids, spans, logp, counts, scores = A._to_host(al.targets, al.spans, al.span_logp, al.target_lengths, al.score)     # one copy
+        counts = [0 if scores[b] == float("-inf") else int(counts[b]) for b in range(len(counts))]
+        return A.clips_from_spans(ids, spans, logp, counts, scores, self.text_transform.vocab.itos, self.samples_per_frame, self.sample_rate)
+
+    def predict_spans(self, x: Tensor) -> List["AlignedClip"]:
+        """predict() with the positions kept: per clip the tokens of the greedy transcript (blank runs dropped) with their spans; joining
+        the tokens, with the separators read as spaces, gives predict(x) as called under no_grad (this method always runs the inference
+        forward; predict() follows the caller's grad mode, and a decoder with trainable parameters takes its f32 training path under grad).
+        The clip's score is the sum of its tokens' log-probabilities."""
+        from . import ctc_align as A
+        logits, _ = self._eval_logits(x, None)
+        gs = A.greedy_spans(logits, None, self.text_transform.vocab.blank_idx)
+        ids, spans, logp, counts = A._to_host(gs.tokens, gs.spans, gs.span_logp, gs.counts)                              # one copy
+        scores = [float(logp[b, : int(counts[b])].sum()) for b in range(len(counts))]
+        return A.clips_from_spans(ids, spans, logp, counts, scores, self.text_transform.vocab.itos, self.samples_per_frame, self.sample_rate)
+
     def training_step(self, batch, batch_idx: int) -> torch.Tensor:
         audio, audio_lengths, texts = batch
         y, y_lengths = self.text_transform.encode(texts, device=audio.device)

@@ -268,7 +268,9 @@ def FilterbankFeatures(sample_rate: int = 16000, n_window_size: int = 320, n_win
     if num_freq_masks + num_time_masks > 0:
         modules.append(Masked(SpecAugment(time_masks=num_time_masks, freq_masks=num_freq_masks, time_width=mask_time_width,
                                           freq_width=mask_freq_width)))
-    return _FilterbankFeatures(*modules)
+    features = _FilterbankFeatures(*modules)
+    features.sample_rate = int(sample_rate)        # host-only record (BaseCTCModule.sample_rate: frames -> seconds)
+    return features
 
 
 def patch_stft(filterbank: nn.Module) -> nn.Module:
