@@ -1,0 +1,422 @@
+"""CTC prefix beam search on the GPU (thunder_speech_amd/abi/ctc_beam.h, csrc/ctc_beam.hip) through the raw C ABI and through two model families.
+
+The reference is `_search` below: the header's algorithm restated with prefixes as tuples (no hashes, no trie, no pruning of candidates) over an
+arithmetic chosen by the caller -- float64 in the LOG domain (`_Log`) for the comparisons, `fractions.Fraction` (`_Exact`) for the tie rule.
+Nothing of the package takes part in it.  Independent of that restatement, the exhaustive cases compare every score with the CTC log-likelihood of
+its label string from a plain float64 alpha recursion (`_ctc_ll`).
+
+Tolerance of a score: 2^-23 max(1, |score|) -- the one f32 rounding (2^-24 relative) plus float64 noise.
+
+The margin condition (asserted by every test that demands equal tokens): a decision of the search -- which candidates a frame keeps, in which
+order the final beam comes out -- is only determined if the keys it compares differ by more than the two computations' errors.  Per frame a
+mass goes through: its class's softmax probability (a difference, an exp, a sum over V, a quotient: < 8 ulp relative), at most two products and
+the sum for tot, the stay's second product and sum, the merged child's sum and the key's sum (8 more roundings); the log-domain reference does
+the same steps as log-add-exps (a difference, an exp, a log1p and a sum each, the last two with an ABSOLUTE error of an ulp of the partial sum's
+magnitude M).  Fewer than 32 ulp per frame on either side, errors adding up linearly over the T frames: two log keys closer than
+E = 64 T 2^-53 max(1, M) may fall either way, and the test requires the smallest gap (last kept key against first dropped key over all frames,
+and neighbouring keys of the final beam) to exceed E.  The fixtures' margins were measured on the CPU before the seeds were fixed (>= 1e-6
+against E ~ 1e-10); the assertion stays in the test.
+
+Ratios error / bound are printed as `RATIO|kind|ratio|case` (profiles/ctc_beam.md records the largest)."""
+import itertools
+import json
+import math
+from fractions import Fraction
+
+import numpy as np
+import pytest
+import torch
+
+NEG = float("-inf")
+U53 = 2.0 ** -53
+
+
+def _tol(score):
+    return 2.0 ** -23 * max(1.0, abs(score))
+
+
+# ---- the reference -------------------------------------------------------------------------------------------------------------------------------
+class _Log:
+    """float64, log domain."""
+    zero, one = NEG, 0.0
+
+    @staticmethod
+    def add(a, b):
+        if a == NEG:
+            return b
+        if b == NEG:
+            return a
+        return max(a, b) + math.log1p(math.exp(-abs(a - b)))
+
+    @staticmethod
+    def mul(a, b):
+        return a + b
+
+    @staticmethod
+    def probs(col):
+        col = col.astype(np.float64)
+        m = col.max()
+        return col - (m + math.log(np.exp(col - m).sum()))
+
+    @staticmethod
+    def log(a):
+        return a
+
+
+class _Exact:
+    """Exact rationals; only for logits whose softmax is rational (all equal)."""
+    zero, one = Fraction(0), Fraction(1)
+    add = staticmethod(lambda a, b: a + b)
+    mul = staticmethod(lambda a, b: a * b)
+
+    @staticmethod
+    def probs(col):
+        assert (col == col[0]).all()
+        return [Fraction(1, len(col))] * len(col)
+
+    @staticmethod
+    def log(a):
+        return math.log(a) if a > 0 else NEG
+
+
+def _search(x, blank, width, cap, dom=_Log):
+    """x [V, T] f32 -> (final beam [(prefix, frames, key)], smallest decision gap, largest |key|): section 1 of the header, word by word."""
+    V, T = x.shape
+    cap = min(cap, V - 1)
+    beam = [((), (), dom.one, dom.zero)]                                  # prefix, frames, p_b, p_nb
+    gap, big = math.inf, 0.0
+    for t in range(T):
+        p = dom.probs(x[:, t])
+        cands = sorted(sorted((c for c in range(V) if c != blank), key=lambda c: (-float(x[c, t]), c))[:cap])     # raw logits; ascending class order
+        slot = {e[0]: j for j, e in enumerate(beam)}
+        stay = [[dom.mul(dom.add(pb, pnb), p[blank]), dom.mul(pnb, p[pre[-1]]) if pre else dom.zero] for pre, _, pb, pnb in beam]
+        children = []
+        for pre, fr, pb, pnb in beam:                                      # children in (parent slot, class index) order
+            tot = dom.add(pb, pnb)
+            for c in cands:
+                mass = dom.mul(pb if pre and pre[-1] == c else tot, p[c])
+                if pre + (c,) in slot:
+                    j = slot[pre + (c,)]
+                    stay[j][1] = dom.add(stay[j][1], mass)
+                else:
+                    children.append((pre + (c,), fr + (t,), dom.zero, mass))
+        allc = [(e[0], e[1], s[0], s[1]) for e, s in zip(beam, stay)] + children
+        keys = [dom.add(c[2], c[3]) for c in allc]
+        order = [k for k in sorted(range(len(allc)), key=lambda k: (-keys[k], k)) if keys[k] != dom.zero]
+        if len(order) > width:
+            gap = min(gap, float(dom.log(keys[order[width - 1]])) - float(dom.log(keys[order[width]])))
+        beam = [allc[k] for k in order[:width]]
+        big = max([big] + [abs(float(dom.log(keys[k]))) for k in order[:width]])
+    final = [(pre, fr, dom.add(pb, pnb)) for pre, fr, pb, pnb in beam]
+    for (_, _, k0), (_, _, k1) in zip(final, final[1:]):
+        gap = min(gap, float(dom.log(k0)) - float(dom.log(k1)))
+    return final, gap, big
+
+
+def _ctc_ll(lp, labels, blank):
+    """log p(labels | x) by the alpha recursion in float64; lp [V, T] log-probabilities."""
+    T = lp.shape[1]
+    ext = [blank]
+    for c in labels:
+        ext += [c, blank]
+    if T == 0:
+        return 0.0 if not labels else NEG
+    alpha = np.full(len(ext), NEG)
+    alpha[0] = lp[blank, 0]
+    if len(ext) > 1:
+        alpha[1] = lp[ext[1], 0]
+    for t in range(1, T):
+        new = np.full(len(ext), NEG)
+        for s in range(len(ext)):
+            a = alpha[s]
+            if s >= 1:
+                a = _Log.add(a, alpha[s - 1])
+            if s >= 2 and ext[s] != blank and ext[s] != ext[s - 2]:
+                a = _Log.add(a, alpha[s - 2])
+            new[s] = a + lp[ext[s], t] if a != NEG else NEG
+        alpha = new
+    return _Log.add(alpha[-1], alpha[-2] if len(ext) > 1 else NEG)
+
+
+def _log_softmax64(x):
+    x = x.astype(np.float64)
+    m = x.max(0, keepdims=True)
+    return x - (m + np.log(np.exp(x - m).sum(0, keepdims=True)))
+
+
+# ---- the launch ------------------------------------------------------------------------------------------------------------------------------------
+def _launch(logits, n_frames, blank, width, cap, n_best, lengths=None, graph=False):
+    """logits: CPU f32 [B, V, pitch]; returns numpy (tokens, frames, lengths, scores, counts)."""
+    from thunder_speech_amd import _lib
+    L = _lib.lib()
+    b, v, pitch = logits.shape
+    lg = logits.cuda()
+    il = None if lengths is None else torch.tensor(lengths, dtype=torch.int32).cuda()
+    nbytes = L.ts_ctc_beam_workspace_bytes(b, n_frames, width, cap)
+    assert nbytes > 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    out = [torch.full((b, n_best, n_frames), -7, dtype=torch.int32, device="cuda"), torch.full((b, n_best, n_frames), -7, dtype=torch.int32, device="cuda"),
+           torch.full((b, n_best), -7, dtype=torch.int32, device="cuda"), torch.full((b, n_best), 7.0, dtype=torch.float32, device="cuda"),
+           torch.full((b,), -7, dtype=torch.int32, device="cuda")]
+
+    def call():
+        st = L.ts_ctc_beam_search(lg.data_ptr(), b, v, n_frames, pitch, None if il is None else il.data_ptr(), blank, width, cap, n_best,
+                                  *[o.data_ptr() for o in out], ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        assert st == 0, st
+
+    if not graph:
+        call()
+        torch.cuda.synchronize()
+        return [o.cpu().numpy() for o in out]
+    call()
+    torch.cuda.synchronize()
+    eager = [o.cpu().numpy().copy() for o in out]
+    for o in out:
+        o.fill_(-9)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(g, stream=side):
+            call()
+    for o in out:
+        o.fill_(-9)
+    g.replay()
+    torch.cuda.synchronize()
+    return eager, [o.cpu().numpy() for o in out]
+
+
+def _compare(name, got, i, x, blank, width, cap, n_best, want_margin=True, dom=_Log):
+    """Utterance i of `got` against the reference on x [V, T]: tokens, frames, lengths, counts equal, scores within the tolerance."""
+    tokens, frames, lengths, scores, counts = got
+    n_frames = tokens.shape[2]
+    final, gap, big = _search(x, blank, width, cap, dom)
+    T = x.shape[1]
+    e = 64 * max(T, 1) * U53 * max(1.0, big)
+    if want_margin:
+        print(f"RATIO|beam-margin|{e / gap if gap < math.inf else 0.0:.3e}|{name}[{i}] E / smallest decision gap (E {e:.3e}, gap {gap:.3e})")
+        assert gap > e, f"{name}[{i}]: the fixture no longer meets the margin condition ({gap:.3e} <= {e:.3e}); pick another seed"
+    want = final[:n_best]
+    assert int(counts[i]) == len(want), f"{name}[{i}]: {counts[i]} hypotheses, reference {len(want)}"
+    worst = 0.0
+    for n in range(n_best):
+        if n >= len(want):
+            assert lengths[i, n] == 0 and scores[i, n] == NEG and not tokens[i, n].any() and not frames[i, n].any()
+            continue
+        pre, fr, key = want[n]
+        assert int(lengths[i, n]) == len(pre), f"{name}[{i}] rank {n}: length {lengths[i, n]}, reference {len(pre)}"
+        assert tokens[i, n, : len(pre)].tolist() == list(pre), f"{name}[{i}] rank {n}: tokens"
+        assert frames[i, n, : len(pre)].tolist() == list(fr), f"{name}[{i}] rank {n}: frames"
+        assert not tokens[i, n, len(pre):].any() and not frames[i, n, len(pre):].any()
+        ref = float(dom.log(key))
+        worst = max(worst, abs(float(scores[i, n]) - ref) / _tol(ref))
+        assert abs(float(scores[i, n]) - ref) <= _tol(ref), f"{name}[{i}] rank {n}: score {scores[i, n]!r}, reference {ref!r}"
+    print(f"RATIO|beam-score|{worst:.3e}|{name}[{i}] (T {T}, {len(want)} hypotheses)")
+    return final
+
+
+def _randn(seed, shape, scale=3.0):
+    return (scale * np.random.Generator(np.random.PCG64(seed)).standard_normal(shape)).astype(np.float32)
+
+
+# ---- 1. exhaustive: scores are exact CTC likelihoods -------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("T", [1, 3, 5])
+def test_unpruned_search_lists_every_feasible_string_with_its_ctc_likelihood(T):
+    """V = 3, beam 64, both labels candidates in every frame: all 63 strings of up to 5 labels fit the beam, nothing is pruned, and the score of a
+    string is its exact CTC log-likelihood."""
+    blank = 1
+    x = _randn(100 + T, (3, T))
+    tokens, frames, lengths, scores, counts = _launch(torch.from_numpy(x)[None].contiguous(), T, blank, 64, 2, 64)
+    lp = _log_softmax64(x)
+    strings = [s for n in range(T + 1) for s in itertools.product((0, 2), repeat=n)]
+    ll = {s: _ctc_ll(lp, list(s), blank) for s in strings}
+    want = sorted((s for s in strings if ll[s] > NEG), key=lambda s: -ll[s])
+    assert len(want) == {1: 3, 3: 9, 5: 25}[T]
+    gaps = [ll[a] - ll[b] for a, b in zip(want, want[1:])]
+    assert min(gaps) > 1e-6                                              # the order is determined
+    assert int(counts[0]) == len(want)
+    worst = 0.0
+    for n, s in enumerate(want):
+        assert tokens[0, n, : lengths[0, n]].tolist() == list(s), f"rank {n}"
+        worst = max(worst, abs(float(scores[0, n]) - ll[s]) / _tol(ll[s]))
+        assert abs(float(scores[0, n]) - ll[s]) <= _tol(ll[s]), f"rank {n}: {scores[0, n]!r} against {ll[s]!r}"
+        assert all(0 <= f < T for f in frames[0, n, : lengths[0, n]]) and sorted(frames[0, n, : lengths[0, n]]) == frames[0, n, : lengths[0, n]].tolist()
+    assert (scores[0, len(want):] == NEG).all() and not lengths[0, len(want):].any() and not tokens[0, len(want):].any()
+    print(f"RATIO|beam-exhaustive-score|{worst:.3e}|T {T}, {len(want)} strings")
+
+
+# ---- 2. equality against the reference ---------------------------------------------------------------------------------------------------------
+def _peaky(seed, v, n_frames, blank, transcript):
+    """Logits of a planted transcript: a dominant blank, each label on one or two frames (two frames of one label collapse, equal labels around a
+    blank do not)."""
+    g = np.random.Generator(np.random.PCG64(seed))
+    x = g.standard_normal((v, n_frames)).astype(np.float32)
+    x[blank] += 6.0
+    t = 2
+    for k, c in enumerate(transcript):
+        for _ in range(1 + k % 2):
+            x[c, t] += 9.0
+            t += 1
+        if k % 3 != 2 or (k + 1 < len(transcript) and transcript[k + 1] == c):
+            t += 1 + k % 2                                               # a blank gap: always between equal labels, else two times out of three
+    assert t < n_frames
+    return x
+
+
+EQUAL = [  # name, V, T, beam_width, token_cap, blank, utterances, seed
+    ("v5-t41-w4-c4", 5, 41, 4, 4, 0, 2, 0),
+    ("v8-t60-w8-c4", 8, 60, 8, 4, 7, 2, 1),
+    ("v29-t120-w16-c8", 29, 120, 16, 8, 0, 2, 2),
+    ("v32-t150-w64-c16", 32, 150, 64, 16, 31, 1, 3),
+    ("v257-t50-w32-c32", 257, 50, 32, 32, 128, 2, 4),
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,v,T,width,cap,blank,utts,seed", EQUAL, ids=[c[0] for c in EQUAL])
+def test_equals_the_reference_where_the_margin_condition_holds(name, v, T, width, cap, blank, utts, seed):
+    x = _randn(seed, (utts, v, T))
+    n_best = min(width, 8)
+    got = _launch(torch.from_numpy(x), T, blank, width, cap, n_best)
+    for i in range(utts):
+        _compare(name, got, i, x[i], blank, width, cap, n_best)
+
+
+@pytest.mark.gpu
+def test_peaky_logits_with_repeated_labels_equal_the_reference():
+    """A planted transcript with doubled letters: the merge rule (a child that is already in the beam) and the `c == last` rule decide the text."""
+    blank, transcript = 3, [5, 5, 2, 7, 7, 7, 1, 5, 2, 2, 9, 4, 4]
+    x = np.stack([_peaky(11, 12, 64, blank, transcript), _peaky(12, 12, 64, blank, transcript[::-1])])
+    got = _launch(torch.from_numpy(x), 64, blank, 8, 4, 8)
+    for i in range(2):
+        final = _compare("peaky", got, i, x[i], blank, 8, 4, 8)
+        assert any(a == b for a, b in zip(final[0][0], final[0][0][1:]))   # the best hypothesis keeps a doubled label
+    assert got[0][0, 0, : got[2][0, 0]].tolist() == transcript and got[0][1, 0, : got[2][1, 0]].tolist() == transcript[::-1]
+
+
+# ---- 3. the tie rule, exactly ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("T,width,cap,blank", [(7, 8, 3, 0), (20, 8, 3, 2), (20, 5, 2, 0), (13, 64, 2, 3)])
+def test_all_zero_logits_follow_the_candidate_order_exactly(T, width, cap, blank):
+    """V = 4, every probability 1/4: every mass is a dyadic rational, exact in f64, and full of ties.  The kernel must equal the Fraction
+    restatement, in which equal keys fall in candidate order and the lowest classes win the token cap."""
+    x = np.zeros((4, T), np.float32)
+    got = _launch(torch.from_numpy(x)[None].contiguous(), T, blank, width, cap, width)
+    _compare(f"ties-t{T}-w{width}-c{cap}", got, 0, x, blank, width, cap, width, want_margin=False, dom=_Exact)
+
+
+# ---- 4. lengths and edges ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("use_lengths", [True, False])
+def test_lengths_pitch_and_cells_beyond_the_length(use_lengths):
+    """Mixed input_len in one batch (0, 1, n_frames and one in between), pitch > n_frames, NaN in every cell the kernels must not read."""
+    v, n, pitch, blank, width, cap, n_best = 6, 37, 48, 2, 6, 3, 3
+    lengths = [0, 1, n, 20] if use_lengths else None
+    x = np.full((4, v, pitch), np.nan, np.float32)
+    for i in range(4):
+        T = lengths[i] if use_lengths else n
+        x[i, :, :T] = _randn(20 + i, (v, T))
+    got = _launch(torch.from_numpy(x), n, blank, width, cap, n_best, lengths)
+    for i in range(4):
+        T = lengths[i] if use_lengths else n
+        _compare("lengths" if use_lengths else "no-lengths", got, i, x[i, :, :T], blank, width, cap, n_best)
+    if use_lengths:                                                      # T = 0: the empty string with score 0
+        assert got[4][0] == 1 and got[3][0, 0] == 0.0 and got[2][0, 0] == 0 and (got[3][0, 1:] == NEG).all()
+        # lengths outside [0, n_frames] are clamped
+        clamped = _launch(torch.from_numpy(x), n, blank, width, cap, n_best, [-3, 1, n + 50, 20])
+        for a, b in zip(got, clamped):
+            assert a.tobytes() == b.tobytes()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,v,T,width,cap,n_best,blank,seed", [
+    ("cap-beyond-v", 4, 30, 8, 64, 8, 0, 30),                            # token_cap >= V - 1: clamped
+    ("cap-equals-v-1", 5, 30, 8, 4, 2, 4, 31),
+    ("beam-1", 9, 45, 1, 8, 1, 0, 32),                                   # one prefix: no selection to speak of
+    ("beam-1-cap-1", 9, 45, 1, 1, 1, 3, 33),
+    ("n-best-below-beam", 9, 45, 16, 4, 3, 8, 34),
+    ("odd-beam", 7, 33, 7, 3, 7, 1, 35),
+])
+def test_edges_of_the_three_widths(name, v, T, width, cap, n_best, blank, seed):
+    x = _randn(seed, (2, v, T))
+    got = _launch(torch.from_numpy(x), T, blank, width, cap, n_best)
+    for i in range(2):
+        _compare(name, got, i, x[i], blank, width, cap, n_best)
+
+
+# ---- 5. graph capture --------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_a_captured_call_replays_the_eager_bits():
+    x = _randn(40, (3, 29, 90))
+    eager, replay = _launch(torch.from_numpy(x), 90, 0, 16, 8, 4, [90, 51, 7], graph=True)
+    for a, b in zip(eager, replay):
+        assert a.tobytes() == b.tobytes()
+    assert eager[4].tolist() == [4, 4, 4]
+
+
+# ---- 6. through the module ---------------------------------------------------------------------------------------------------------------------
+def _quartznet():
+    from oracle import tcs as otcs
+    from thunder_speech_amd.quartznet.compatibility import build_synthetic_quartznet
+    arch = otcs.quartznet_arch(repeat_blocks=1)
+    module = build_synthetic_quartznet(repeat_blocks=1, encoder_state=otcs.synth_encoder_state(arch, seed=0, calibrate=True),
+                                       decoder_state=otcs.synth_decoder_state(1024, 29, seed=1, gain=4.0))
+    return module.cuda().eval(), 16000
+
+
+def _wav2vec2(tmp_path):
+    transformers = pytest.importorskip("transformers")
+    from thunder_speech_amd.huggingface.compatibility import module_from_huggingface
+    tokens = ["<pad>", "<s>", "</s>", "<unk>", "|"] + [chr(97 + i) for i in range(26)] + ["'"]
+    vocab = tmp_path / "vocab.json"
+    vocab.write_text(json.dumps({t: i for i, t in enumerate(tokens)}))
+    tokenizer = transformers.Wav2Vec2CTCTokenizer(str(vocab))
+    torch.manual_seed(3)
+    cfg = transformers.Wav2Vec2Config(vocab_size=len(tokens), hidden_size=64, num_hidden_layers=2, num_attention_heads=4, intermediate_size=128,
+                                      conv_dim=(32, 32, 32), conv_stride=(5, 2, 2), conv_kernel=(10, 3, 2), num_conv_pos_embeddings=16,
+                                      num_conv_pos_embedding_groups=4, pad_token_id=0, mask_time_prob=0.0)
+    model = transformers.Wav2Vec2ForCTC(cfg).eval()
+    with torch.no_grad():
+        model.lm_head.weight.mul_(20.0)                                # a head that prefers something: the transcripts are not empty
+    module = module_from_huggingface(model, transformers.Wav2Vec2FeatureExtractor(return_attention_mask=True), tokenizer)
+    return module.cuda().eval(), 3000
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("family", ["quartznet", "wav2vec2"])
+def test_predict_beam_and_predict_nbest_through_the_module(family, tmp_path):
+    module, n0 = _quartznet() if family == "quartznet" else _wav2vec2(tmp_path)
+    spf, sr = module.samples_per_frame, module.sample_rate
+    rng = np.random.Generator(np.random.PCG64(7))
+    x = torch.from_numpy((0.1 * rng.standard_normal((2, n0))).astype(np.float32)).cuda()
+    blank, tt = module.text_transform.vocab.blank_idx, module.text_transform
+    full = torch.full((2,), n0, dtype=torch.int32, device=x.device)
+    with torch.no_grad():
+        logits, _ = module(x, full)
+    lg = logits.float().cpu().numpy()
+    width, cap, n_best = 8, 4, 4
+    texts = module.predict_beam(x, beam_width=width, token_cap=cap)
+    nbest = module.predict_nbest(x, n_best, beam_width=width, token_cap=cap)
+    assert len(texts) == len(nbest) == 2
+    for b in range(2):
+        final, gap, big = _search(lg[b], blank, width, cap)
+        e = 64 * lg.shape[2] * U53 * max(1.0, big)
+        print(f"RATIO|beam-margin|{e / gap:.3e}|{family}[{b}] E / smallest decision gap (T {lg.shape[2]})")
+        assert gap > e, f"{family}[{b}]: the fixture no longer meets the margin condition ({gap:.3e} <= {e:.3e})"
+        assert texts[b] == tt._ids_to_text(list(final[0][0]))
+        lp = _log_softmax64(lg[b])
+        hyps = nbest[b]
+        assert len(hyps) == min(n_best, len(final))
+        assert all(h0.score >= h1.score for h0, h1 in zip(hyps, hyps[1:]))
+        assert hyps[0].text == texts[b]
+        for n, h in enumerate(hyps):
+            pre, fr, key = final[n]
+            assert [t.token for t in h.tokens] == [tt.vocab.itos[c] for c in pre] and [t.frame for t in h.tokens] == list(fr)
+            assert all(t.time == t.frame * spf / sr for t in h.tokens)
+            assert h.text == tt._ids_to_text(list(pre))
+            assert abs(h.score - key) <= _tol(key)
+            ll = _ctc_ll(lp, list(pre), blank)
+            assert h.score <= ll + _tol(ll), f"{family}[{b}] rank {n}: score {h.score} above the CTC log-likelihood {ll} of its text"
+    if family == "wav2vec2":
+        assert any(t for t in texts)

@@ -279,6 +279,29 @@ class BaseCTCModule(_Base):
         scores = [float(logp[b, : int(counts[b])].sum()) for b in range(len(counts))]
         return A.clips_from_spans(ids, spans, logp, counts, scores, self.text_transform.vocab.itos, self.samples_per_frame, self.sample_rate)
 
+    # ------------------------------------------------------------------------------------------------------------------
+    # CTC prefix beam search (no reference counterpart), on the kernels of csrc/ctc_beam.hip (ctc_beam.py).  predict() is untouched.
+    def predict_beam(self, x: Tensor, beam_width: int = 16, token_cap: int = 8) -> List[str]:
+        """Transcription by CTC prefix beam search: per clip the transcript whose alignments carry the most probability among the
+        `beam_width` prefixes kept per frame (predict() follows the single best path instead).  Every clip is treated as full length."""
+        from . import ctc_align as A
+        from . import ctc_beam as B
+        logits, _ = self._eval_logits(x, None)
+        res = B.beam_search(logits, None, self.text_transform.vocab.blank_idx, beam_width, token_cap, 1)
+        ids, counts = A._to_host(res.tokens[:, 0], res.lengths[:, 0])                                                    # one copy
+        return self.text_transform.decode_collapsed(torch.from_numpy(ids), torch.from_numpy(counts))
+
+    def predict_nbest(self, x: Tensor, n_best: int, beam_width: int = 16, token_cap: int = 8) -> List[List["Hypothesis"]]:
+        """The `n_best` best transcripts of each clip under CTC prefix beam search, best first: text, score (log of the summed probability
+        of the transcript's surviving alignments) and per token the frame and time at which it entered the hypothesis."""
+        from . import ctc_align as A
+        from . import ctc_beam as B
+        logits, _ = self._eval_logits(x, None)
+        res = B.beam_search(logits, None, self.text_transform.vocab.blank_idx, beam_width, token_cap, n_best)
+        tokens, frames, lengths, scores, counts = A._to_host(res.tokens, res.frames, res.lengths, res.scores, res.counts)  # one copy
+        return B.hypotheses_from_tables(tokens, frames, lengths, scores, counts, self.text_transform.vocab.itos, self.text_transform._ids_to_text,
+                                        self.samples_per_frame, self.sample_rate)
+
     def training_step(self, batch, batch_idx: int) -> torch.Tensor:
         audio, audio_lengths, texts = batch
         y, y_lengths = self.text_transform.encode(texts, device=audio.device)
