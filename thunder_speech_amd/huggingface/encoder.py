@@ -8,7 +8,7 @@ difference); the arithmetic runs in `Wav2Vec2Plan`, which keeps packed fp32 devi
 call per stage.  Both published families (group-norm / post-LN: wav2vec2-base-960h, -large-960h; layer-norm / pre-LN: -large-lv60, xlsr);
 WavLM runs the same sequence with its gated relative-position attention (csrc/wavlm.hip, include/thunder_speech_amd_wavlm.h) in place of
 the wav2vec2 one (fine-tuning in mixed precision only: csrc/wavlm_train.hip); wav2vec2-conformer (rotary) runs conformer blocks behind the same
-front end (huggingface/conformer.py, inference only); SEW runs the post-LN layers at 1 / squeeze_factor of the frame rate between csrc/sew.hip's
+front end (huggingface/conformer.py; fine-tuning in mixed precision only: huggingface/conformer_train.py, csrc/conformer_train.hip); SEW runs the post-LN layers at 1 / squeeze_factor of the frame rate between csrc/sew.hip's
 squeeze and an upsampling GEMM (huggingface/sew.py, thunder_speech_amd/abi/sew.h, inference only); MMS (config.adapter_attn_dim: an attention adapter behind every pre-LN layer) and the head_dim 80
 of MMS-1B / XLS-R 1B run on csrc/mms.hip and the head_dim 80 kernel of csrc/w2v_attn.hip (include/thunder_speech_amd_mms.h, inference only); training mode (fine-tuning with the conv feature extractor frozen) runs
 through huggingface/train.py; no CPU fallback."""
@@ -47,11 +47,12 @@ def feat_extract_output_lengths(conv_kernel, conv_stride, lengths: torch.Tensor,
 # encoder arithmetic unchanged: tests/test_oracle_w2v.py checks the oracle against both); wavlm (base / base-plus: group norm, post-LN; large: layer
 # norm, pre-LN): the wav2vec2 layers with WavLMAttention's gated relative-position bias in the attention core (csrc/wavlm.hip, head_dim 64 -- every
 # published WavLM -- fine-tuned with train_precision="bf16" only, csrc/wavlm_train.hip); wav2vec2-conformer with rotary position embeddings
-# (inference only): the wav2vec2 front end and adapter around conformer blocks (huggingface/conformer.py, csrc/conformer.hip,
+# (fine-tuned with train_precision="bf16" only, huggingface/conformer_train.py): the wav2vec2 front end and adapter around conformer blocks (huggingface/conformer.py, csrc/conformer.hip,
 # include/thunder_speech_amd_conformer.h); sew (inference only): wav2vec2's post-LN layers at 1 / squeeze_factor of the frame rate between a
 # strided positional conv added to an average pool and an upsampling projection (huggingface/sew.py, csrc/sew.hip, thunder_speech_amd/abi/sew.h).
 # Others (sew-d's disentangled attention, the conformer's relative-position variant ...) have layers this library holds no kernels for and raise.
-# Fine-tuning (huggingface/train.py, TRAINABLE_MODEL_TYPES): every family above but the conformer.  hubert, unispeech and unispeech-sat train on the
+# Fine-tuning (huggingface/train.py, TRAINABLE_MODEL_TYPES): every family above but the conformer, which trains on the chain of
+# huggingface/conformer_train.py, and sew.  hubert, unispeech and unispeech-sat train on the
 # wav2vec2 chain (f32 and mixed precision); data2vec-audio on it with one autograd node per layer of its positional stack (PosConvStackLayer,
 # csrc/posconv_stack_train.hip, include/thunder_speech_amd/posconv_stack_train.h); wavlm in mixed precision only.
 SUPPORTED_MODEL_TYPES = ("wav2vec2", "hubert", "data2vec-audio", "unispeech", "unispeech-sat", "wavlm", "wav2vec2-conformer", "sew")
@@ -576,6 +577,10 @@ class HuggingFaceEncoderAdapt(nn.Module):
         cfg = self.original_encoder.config
         if getattr(cfg, "model_type", "wav2vec2") == "wav2vec2-conformer":
             from .conformer import ConformerPlan
+            # the plan folds running_mean / running_var into bn_scale / bn_shift: a train-mode forward changes those buffers without touching a
+            # parameter (no optimizer step), so they belong to the key
+            params += [buf for layer in self.original_encoder.encoder.layers
+                       for buf in (layer.conv_module.batch_norm.running_mean, layer.conv_module.batch_norm.running_var) if buf is not None]
             return self._cache.get(params, lambda: ConformerPlan(cfg, self.original_encoder.state_dict(), device, self.precision))
         if getattr(cfg, "model_type", "wav2vec2") == "sew":
             from .sew import SEWPlan
@@ -626,9 +631,12 @@ class HuggingFaceEncoderAdapt(nn.Module):
         return out
 
     def forward(self, audio: torch.Tensor, audio_lengths: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        if self.training and getattr(self.original_encoder.config, "model_type", "wav2vec2") == "wav2vec2-conformer":
-            # no conformer backward exists (BatchNorm in train mode, the depthwise conv, the rotary products): refused before any device work
-            raise NotImplementedError("wav2vec2-conformer: fine-tuning is not implemented (inference only); use the module in eval mode")
+        conformer = getattr(self.original_encoder.config, "model_type", "wav2vec2") == "wav2vec2-conformer"
+        if self.training and conformer:
+            # the conformer trains on a chain of its own, in mixed precision only (huggingface/conformer_train.py, csrc/conformer_train.hip):
+            # train_precision="fp32", an adapter, mask_feature_prob, an unfrozen feature extractor are refused by name, before any device work
+            from .conformer_train import refuse_untrainable as refuse_untrainable_conformer
+            refuse_untrainable_conformer(self)
         if self.training and getattr(self.original_encoder.config, "model_type", "wav2vec2") == "sew":
             # no backward exists for the strided positional conv, the pool or the upsampler: refused before any device work
             raise NotImplementedError("sew: fine-tuning is not implemented (inference only); use the module in eval mode")
@@ -648,7 +656,10 @@ class HuggingFaceEncoderAdapt(nn.Module):
         if self.training:
             # fine-tuning (module.py:102-127 through this adapter): transformers' training-mode forward -- frozen conv feature extractor, time
             # masking, dropouts, LayerDrop -- as a chain of autograd nodes on the HIP kernels (huggingface/train.py), f32 arithmetic
-            from .train import train_forward
+            if conformer:
+                from .conformer_train import train_forward
+            else:
+                from .train import train_forward
             h = train_forward(self, x, audio_lengths if self.mask_input else None)
         else:
             h = self._plan(x.device).forward(x, audio_lengths if self.mask_input else None)

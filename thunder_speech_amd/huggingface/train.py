@@ -183,14 +183,16 @@ class LinearMixed(torch.autograd.Function):
 class FFNActLinear(torch.autograd.Function):
     """output_dense(dropout(gelu(z + b1))) of a wav2vec2 feed-forward block in mixed precision, as ONE node: the activation goes straight from z to the bf16
     operands of the second linear (ts_w2v_ffn_act_cast: the f32 activation is never stored), and the backward runs the data-gradient product into a buffer that
-    the fused dropout-backward x gelu' launch (ts_w2v_ffn_act_bwd) turns into dz.  Same products, split-K rules and Philox mask as BiasGelu -> Dropout -> LinearMixed."""
+    the fused dropout-backward x gelu' launch (ts_w2v_ffn_act_bwd) turns into dz.  Same products, split-K rules and Philox mask as BiasGelu -> Dropout -> LinearMixed.
+    `act` (the code of huggingface/conformer.py's CONFORMER_ACTS; the conformer chain passes it): 1, the default, is the GELU pair above; any other code goes to
+    the act-aware pair ts_conformer_ffn_act_cast / _bwd (csrc/conformer_train.hip: 2 = SiLU)."""
 
     @staticmethod
     def supported(c_mid: int, n: int) -> bool:
         return c_mid % 32 == 0 and n % 32 == 0
 
     @staticmethod
-    def forward(ctx, z, b1, w2, b2, p_drop, seed):
+    def forward(ctx, z, b1, w2, b2, p_drop, seed, act=1):
         z, w2 = _f32c(z), _f32c(w2)
         n, k = w2.shape                                   # k = the intermediate width
         rows = z.numel() // k
@@ -198,13 +200,18 @@ class FFNActLinear(torch.autograd.Function):
         rp = _pad32(rows)
         x16 = torch.empty(rows, k, dtype=torch.bfloat16, device=z.device)
         xt16 = torch.empty(k, rp, dtype=torch.bfloat16, device=z.device) if ctx.needs_input_grad[2] else None
-        _lib.check(L.ts_w2v_ffn_act_cast(z.data_ptr(), b1.data_ptr() if b1 is not None else None, rows, k, float(p_drop), int(seed), x16.data_ptr(),
-                                         xt16.data_ptr() if xt16 is not None else None, rp, rp, _s(z)), "ts_w2v_ffn_act_cast")
+        if act == 1:
+            _lib.check(L.ts_w2v_ffn_act_cast(z.data_ptr(), b1.data_ptr() if b1 is not None else None, rows, k, float(p_drop), int(seed), x16.data_ptr(),
+                                             xt16.data_ptr() if xt16 is not None else None, rp, rp, _s(z)), "ts_w2v_ffn_act_cast")
+        else:
+            _lib.check(L.ts_conformer_ffn_act_cast(z.data_ptr(), b1.data_ptr() if b1 is not None else None, rows, k, int(act), float(p_drop), int(seed),
+                                                   x16.data_ptr(), xt16.data_ptr() if xt16 is not None else None, rp, rp, _s(z)), "ts_conformer_ffn_act_cast")
         w16, wt16 = _cast(w2, n, k, True, ctx.needs_input_grad[0])
         y = torch.empty(*z.shape[:-1], n, dtype=torch.float32, device=z.device)
         _gemm_nt_splitk(x16, k, w16, k, y, rows, n, k, bias=_f32c(b2) if b2 is not None else None, min_k=2048)
         ctx.save_for_backward(z, b1, xt16, wt16)
         ctx.geom = (rows, n, k, z.shape, float(p_drop), int(seed), b2 is not None)
+        ctx.act = int(act)
         return y
 
     @staticmethod
@@ -225,15 +232,19 @@ class FFNActLinear(torch.autograd.Function):
             da = torch.empty(rows, k, dtype=torch.float32, device=dy.device)
             _gemm_nt_splitk(dy16, n, wt16, _pad32(n), da, rows, k, n)
             dz = torch.empty(zshape, dtype=torch.float32, device=dy.device)
-            _lib.check(L.ts_w2v_ffn_act_bwd(z.data_ptr(), b1.data_ptr() if b1 is not None else None, k, da.data_ptr(), p_drop, seed, dz.data_ptr(), dz.numel(), _s(dy)),
-                       "ts_w2v_ffn_act_bwd")
+            if ctx.act == 1:
+                _lib.check(L.ts_w2v_ffn_act_bwd(z.data_ptr(), b1.data_ptr() if b1 is not None else None, k, da.data_ptr(), p_drop, seed, dz.data_ptr(), dz.numel(), _s(dy)),
+                           "ts_w2v_ffn_act_bwd")
+            else:
+                _lib.check(L.ts_conformer_ffn_act_bwd(z.data_ptr(), b1.data_ptr() if b1 is not None else None, k, ctx.act, da.data_ptr(), p_drop, seed, dz.data_ptr(),
+                                                      dz.numel(), _s(dy)), "ts_conformer_ffn_act_bwd")
             if b1 is not None and ctx.needs_input_grad[1]:
                 db1 = _colsum(dz, rows, k)
         if ctx.needs_input_grad[2]:
             dw = torch.empty(n, k, dtype=torch.float32, device=dy.device)
             rp = _pad32(rows)
             _gemm_nt_splitk(dyt16, rp, xt16, rp, dw, n, k, rp)
-        return dz, db1, dw, db2, None, None
+        return dz, db1, dw, db2, None, None, None
 
 
 FUSED_FFN_ACT = True        # mixed mode: FFNActLinear for gelu -> dropout -> output_dense (False: the three separate nodes, for A/B)
@@ -900,7 +911,7 @@ def refuse_untrainable(adapt, mixed: bool) -> None:
         # materialised-probability WavLM path to fall back to
         raise NotImplementedError('HIP fine-tuning path: model_type=\'wavlm\' trains with train_precision="bf16" and the fused attention only')
     if model_type not in TRAINABLE_MODEL_TYPES:
-        # wav2vec2-conformer runs the inference path only (huggingface/conformer.py): its blocks have no autograd nodes here.  hubert, unispeech and
+        # wav2vec2-conformer trains on a chain of its own (huggingface/conformer_train.py, mixed precision only), not on this one.  hubert, unispeech and
         # unispeech-sat train on the wav2vec2 chain (hubert's feature-projection LayerNorm is optional), data2vec-audio on it with PosConvStackLayer
         raise NotImplementedError(f"HIP fine-tuning path: model_type={cfg.model_type!r} is inference-only ({', '.join(TRAINABLE_MODEL_TYPES)} checkpoints fine-tune)")
     if getattr(cfg, "add_adapter", False):
