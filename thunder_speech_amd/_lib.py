@@ -1,7 +1,8 @@
 """ctypes binding of the C ABI declared in include/thunder_speech_amd.h and its companions include/thunder_speech_amd_wavlm.h,
 include/thunder_speech_amd_wavlm_train.h, include/thunder_speech_amd_conformer.h, include/thunder_speech_amd_mms.h,
 include/thunder_speech_amd_mms_train.h, include/thunder_speech_amd_mms_adapter_train.h, include/thunder_speech_amd/posconv_stack_train.h,
-thunder_speech_amd/abi/sew.h, thunder_speech_amd/abi/ctc_align.h, thunder_speech_amd/abi/ctc_beam.h and thunder_speech_amd/abi/conformer_train.h.
+thunder_speech_amd/abi/sew.h, thunder_speech_amd/abi/ctc_align.h, thunder_speech_amd/abi/ctc_beam.h, thunder_speech_amd/abi/conformer_train.h and
+thunder_speech_amd/abi/train/sew_train.h.
 
 The header is the only copy of the ABI: `read_header` derives every prototype, struct and TS_* constant from it and
 `lib()` applies the result, so a new entry point needs the header and its .hip definition and nothing here.  A C type
@@ -32,6 +33,8 @@ SEW_HEADER = os.path.join(PKG, "abi", "sew.h")          # eighth companion (SEW 
 CTC_ALIGN_HEADER = os.path.join(PKG, "abi", "ctc_align.h")    # ninth companion (forced alignment, greedy spans), versioned on its own; next to sew.h
 CTC_BEAM_HEADER = os.path.join(PKG, "abi", "ctc_beam.h")      # tenth companion (prefix beam search, n-best), versioned on its own; next to ctc_align.h
 CONFORMER_TRAIN_HEADER = os.path.join(PKG, "abi", "conformer_train.h")    # eleventh companion (wav2vec2-conformer fine-tuning), versioned on its own; next to ctc_beam.h
+
+SEW_TRAIN_HEADER = os.path.join(PKG, "abi", "train", "sew_train.h")    # twelfth companion (SEW fine-tuning), versioned on its own; in abi/train/ (the header count of abi/ is pinned too)
 
 # Parameters and struct fields: these scalars, `[const] <struct>*` as POINTER(struct), every other pointer to one of
 # _POINTEES (const or not, any depth) as c_void_p.  Return types: _RETURNS only.
@@ -113,6 +116,8 @@ CTC_BEAM_SIGNATURES, _, CTC_BEAM_DEFINES = _read_installed_header(CTC_BEAM_HEADE
 CTC_BEAM_ABI_VERSION = CTC_BEAM_DEFINES["TS_CTC_BEAM_ABI_VERSION"]
 CONFORMER_TRAIN_SIGNATURES, _, CONFORMER_TRAIN_DEFINES = _read_installed_header(CONFORMER_TRAIN_HEADER)
 CONFORMER_TRAIN_ABI_VERSION = CONFORMER_TRAIN_DEFINES["TS_CONFORMER_TRAIN_ABI_VERSION"]
+SEW_TRAIN_SIGNATURES, _, SEW_TRAIN_DEFINES = _read_installed_header(SEW_TRAIN_HEADER)
+SEW_TRAIN_ABI_VERSION = SEW_TRAIN_DEFINES["TS_SEW_TRAIN_ABI_VERSION"]
 TcsDesc, FrontendDesc, WgradItem =STRUCTS["ts_tcs_desc"], STRUCTS["ts_frontend_desc"], STRUCTS["ts_wgrad_item"]
 TcsLaunch = STRUCTS["ts_tcs_launch"]
 EXPORTED_SYMBOLS = list(SIGNATURES)
@@ -143,12 +148,12 @@ def lib() -> C.CDLL:
     L = C.CDLL(path)
     missing = [s for s in EXPORTED_SYMBOLS + list(WAVLM_SIGNATURES) + list(WAVLM_TRAIN_SIGNATURES) + list(CONFORMER_SIGNATURES) + list(MMS_SIGNATURES) +
                list(MMS_TRAIN_SIGNATURES) + list(MMS_ADAPTER_TRAIN_SIGNATURES) + list(POSCONV_STACK_TRAIN_SIGNATURES) + list(SEW_SIGNATURES) +
-               list(CTC_ALIGN_SIGNATURES) + list(CTC_BEAM_SIGNATURES) + list(CONFORMER_TRAIN_SIGNATURES) if not hasattr(L, s)]
+               list(CTC_ALIGN_SIGNATURES) + list(CTC_BEAM_SIGNATURES) + list(CONFORMER_TRAIN_SIGNATURES) + list(SEW_TRAIN_SIGNATURES) if not hasattr(L, s)]
     if missing:
         raise RuntimeError(f"thunder_speech_amd: {path} does not export {missing}; rebuild it")
     for name, (restype, argtypes) in {**SIGNATURES, **WAVLM_SIGNATURES, **WAVLM_TRAIN_SIGNATURES, **CONFORMER_SIGNATURES, **MMS_SIGNATURES,
                                       **MMS_TRAIN_SIGNATURES, **MMS_ADAPTER_TRAIN_SIGNATURES, **POSCONV_STACK_TRAIN_SIGNATURES, **SEW_SIGNATURES,
-                                      **CTC_ALIGN_SIGNATURES, **CTC_BEAM_SIGNATURES, **CONFORMER_TRAIN_SIGNATURES}.items():
+                                      **CTC_ALIGN_SIGNATURES, **CTC_BEAM_SIGNATURES, **CONFORMER_TRAIN_SIGNATURES, **SEW_TRAIN_SIGNATURES}.items():
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     if L.ts_abi_version() != ABI_VERSION:
@@ -187,6 +192,9 @@ def lib() -> C.CDLL:
     if L.ts_conformer_train_abi_version() != CONFORMER_TRAIN_ABI_VERSION:
         raise RuntimeError(f"thunder_speech_amd: {path} reports conformer training ABI {L.ts_conformer_train_abi_version()}, the header "
                            f"{CONFORMER_TRAIN_HEADER} declares {CONFORMER_TRAIN_ABI_VERSION}; rebuild it")
+    if L.ts_sew_train_abi_version() != SEW_TRAIN_ABI_VERSION:
+        raise RuntimeError(f"thunder_speech_amd: {path} reports SEW training ABI {L.ts_sew_train_abi_version()}, the header "
+                           f"{SEW_TRAIN_HEADER} declares {SEW_TRAIN_ABI_VERSION}; rebuild it")
     _lib = L
     return L
 

@@ -35,7 +35,8 @@ def needs_build() -> bool:
     if not os.path.exists(out):
         return True
     deps = sources() + glob.glob(os.path.join(PKG, "csrc", "*.hpp")) + glob.glob(os.path.join(ROOT, "include", "*.h")) + \
-        glob.glob(os.path.join(ROOT, "include", "thunder_speech_amd", "*.h")) + glob.glob(os.path.join(PKG, "abi", "*.h"))
+        glob.glob(os.path.join(ROOT, "include", "thunder_speech_amd", "*.h")) + glob.glob(os.path.join(PKG, "abi", "*.h")) + \
+        glob.glob(os.path.join(PKG, "abi", "train", "*.h"))
     return any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps)
 
 
@@ -100,7 +101,7 @@ def build_asan(verbose: bool = True) -> str:
         if os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(d) for d in [src] + glob.glob(os.path.join(PKG, "csrc", "*.hpp")) +
                                                                  glob.glob(os.path.join(ROOT, "include", "*.h")) +
                                                                  glob.glob(os.path.join(ROOT, "include", "thunder_speech_amd", "*.h")) +
-                                                                 glob.glob(os.path.join(PKG, "abi", "*.h"))):
+                                                                 glob.glob(os.path.join(PKG, "abi", "*.h")) + glob.glob(os.path.join(PKG, "abi", "train", "*.h"))):
             continue
         cmd = [hipcc, f"--offload-arch={ARCH}", "-O2", "-g", "-std=c++17", "-fPIC", "-fsanitize=address,undefined", "-Wno-option-ignored",
                "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc"), "-I" + os.path.join(PKG, "abi"),

@@ -9,6 +9,7 @@
 #include "w2v_rows.hpp"
 
 #include "sew.h"
+#include "sew_squeeze.hpp"
 
 namespace ts {
 
@@ -23,12 +24,10 @@ namespace ts {
 //   straight from L2, prefetched a block of four taps ahead.  Epilogue: + bias, GELU, + the average pool of the fp32 x, coalesced along channels.
 // With 24 channels per group the padded copy and the packed weights carry zeros in channels 24 .. 31 of each slot: the same kernel.
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int SQ_TT = 128;         // output frames per workgroup
-constexpr int SQ_PITCH = 144;      // bytes per staged row (64 bf16 + 16)
-constexpr int SQ_SLOT = 32;        // channels per group in the padded copy and the packed weights
+// (SQ_TT output frames per workgroup, SQ_PITCH bytes per staged row, SQ_SLOT channels per group in the padded copy and the packed weights, SQ_LDS_MAX:
+// csrc/sew_squeeze.hpp, shared with the training launches of csrc/sew_train.hip)
 constexpr int SQ_TB = 4;           // taps per block of prefetched weights
 constexpr int SQ_SB = 6;           // staging loads in flight per thread
-constexpr size_t SQ_LDS_MAX = 64 * 1024;
 
 struct SqArgs {
   const unsigned short* xp;        // [B][prow][groups x 32] bf16, k / 2 zero rows in front of each clip
@@ -36,9 +35,12 @@ struct SqArgs {
   const float* bias;
   const float* x;                  // [B][T][C] fp32 (average pool)
   float* y;                        // [B][T2][C]
+  float* z;                        // SAVE_Z (ts_sew_squeeze_train_fwd): [B][T2][C], the conv result before bias and GELU
   int t, t2, c, cg, cp, k, groups, stride, prow, rpp;       // cp = groups x 32; rpp = window slots per phase
 };
 
+// SAVE_Z: the training forward, which also stores the accumulator as it is; <false> is the inference kernel as it was.
+template <bool SAVE_Z>
 __global__ __launch_bounds__(256) void sew_squeeze_mfma_kernel(const SqArgs a) {
   extern __shared__ __attribute__((aligned(16))) char win[];                  // [stride][rpp][SQ_PITCH]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -130,6 +132,7 @@ __global__ __launch_bounds__(256) void sew_squeeze_mfma_kernel(const SqArgs a) {
         const float* xr = a.x + ((size_t)b * a.t + (size_t)f * a.stride) * a.c + co;
         float pool = xr[0];
         for (int s = 1; s < a.stride; ++s) pool += xr[(size_t)s * a.c];
+        if constexpr (SAVE_Z) a.z[((size_t)b * a.t2 + f) * a.c + co] = acc[mt][i];
         a.y[((size_t)b * a.t2 + f) * a.c + co] = pool * inv + gelu_erf(acc[mt][i] + bv);
       }
     }
@@ -190,12 +193,33 @@ __global__ __launch_bounds__(256) void sew_unsqueeze_rows_kernel(const float* __
   *reinterpret_cast<f32x4*>(dst + (size_t)b * n_dst + idx) = v;
 }
 
-// rows per clip of the padded copies: t + kernel, rounded up to a multiple of the stride
-static inline long long sew_prow(int t, int kernel, int stride) { return ((long long)t + kernel + stride - 1) / stride * stride; }
-
 }  // namespace ts
 
 using namespace ts;
+
+void ts::sew_pad16(hipStream_t stream, const float* x, unsigned short* xp, int batch, int t, int c, int groups, long long prow, int front) {
+  const int cp = groups * SQ_SLOT;
+  const long long total = (long long)batch * prow * cp;
+  hipLaunchKernelGGL(sew_pad16_kernel, dim3(nblk(total / 4)), dim3(256), 0, stream, x, xp, t, c, c / groups, cp, (int)prow, front, total);
+}
+
+// the matrix-core squeeze behind its padded copy; the arguments were checked by the caller (sew_squeeze_mfma_ok included).  z: NULL, or the conv result
+int ts::sew_squeeze_mfma(hipStream_t stream, const float* x, int batch, int t, int c, const void* w_taps, const float* bias, int kernel, int groups, int stride,
+                         float* y, float* z, void* workspace) {
+  const int cg = c / groups, t2 = t / stride;
+  const long long prow = sew_prow(t, kernel, stride);
+  const int rows = (SQ_TT - 1) * stride + kernel, rpp = (rows + stride - 1) / stride;
+  const size_t win_lds = (size_t)stride * rpp * SQ_PITCH;
+  unsigned short* const xp = static_cast<unsigned short*>(workspace);
+  sew_pad16(stream, x, xp, batch, t, c, groups, prow, kernel / 2);
+  SqArgs a{};
+  a.xp = xp; a.w = static_cast<const unsigned short*>(w_taps); a.bias = bias; a.x = x; a.y = y; a.z = z;
+  a.t = t; a.t2 = t2; a.c = c; a.cg = cg; a.cp = groups * SQ_SLOT; a.k = kernel; a.groups = groups; a.stride = stride; a.prow = (int)prow; a.rpp = rpp;
+  const dim3 grid((t2 + SQ_TT - 1) / SQ_TT, (groups + 1) / 2, batch);
+  if (z) hipLaunchKernelGGL(sew_squeeze_mfma_kernel<true>, grid, dim3(256), win_lds, stream, a);
+  else hipLaunchKernelGGL(sew_squeeze_mfma_kernel<false>, grid, dim3(256), win_lds, stream, a);
+  return hip_status(hipGetLastError());
+}
 
 extern "C" int ts_sew_abi_version(void) { return TS_SEW_ABI_VERSION; }
 
@@ -218,19 +242,9 @@ extern "C" int ts_sew_squeeze_fwd(const float* x, int32_t batch, int32_t t, int3
   const long long prow = sew_prow(t, kernel, stride);
   if ((long long)batch * prow > 0x7fffffffll) return TS_EUNSUPPORTED;
   if (precision && (cg == 24 || cg == SQ_SLOT)) {
-    const int rows = (SQ_TT - 1) * stride + kernel, rpp = (rows + stride - 1) / stride;
-    const size_t win_lds = (size_t)stride * rpp * SQ_PITCH;
-    if (win_lds > SQ_LDS_MAX) return TS_EUNSUPPORTED;
+    if (!sew_squeeze_mfma_ok(cg, kernel, stride)) return TS_EUNSUPPORTED;
     TS_STREAM;
-    unsigned short* const xp = static_cast<unsigned short*>(workspace);
-    const int cp = groups * SQ_SLOT;
-    const long long total = (long long)batch * prow * cp;
-    hipLaunchKernelGGL(sew_pad16_kernel, dim3(nblk(total / 4)), dim3(256), 0, stream, x, xp, t, c, cg, cp, (int)prow, kernel / 2, total);
-    SqArgs a{};
-    a.xp = xp; a.w = static_cast<const unsigned short*>(w_taps); a.bias = bias; a.x = x; a.y = y;
-    a.t = t; a.t2 = t2; a.c = c; a.cg = cg; a.cp = cp; a.k = kernel; a.groups = groups; a.stride = stride; a.prow = (int)prow; a.rpp = rpp;
-    hipLaunchKernelGGL(sew_squeeze_mfma_kernel, dim3((t2 + SQ_TT - 1) / SQ_TT, (groups + 1) / 2, batch), dim3(256), win_lds, stream, a);
-    return hip_status(hipGetLastError());
+    return sew_squeeze_mfma(stream, x, batch, t, c, w_taps, bias, kernel, groups, stride, y, nullptr, workspace);
   }
   TS_STREAM;
   // all clips in one strided row space: output row R = sum_j xp[s R + j] W_j^T per group; clip b's frame r is row b prow / s + r, rows between clips are waste

@@ -9,7 +9,7 @@ call per stage.  Both published families (group-norm / post-LN: wav2vec2-base-96
 WavLM runs the same sequence with its gated relative-position attention (csrc/wavlm.hip, include/thunder_speech_amd_wavlm.h) in place of
 the wav2vec2 one (fine-tuning in mixed precision only: csrc/wavlm_train.hip); wav2vec2-conformer (rotary) runs conformer blocks behind the same
 front end (huggingface/conformer.py; fine-tuning in mixed precision only: huggingface/conformer_train.py, csrc/conformer_train.hip); SEW runs the post-LN layers at 1 / squeeze_factor of the frame rate between csrc/sew.hip's
-squeeze and an upsampling GEMM (huggingface/sew.py, thunder_speech_amd/abi/sew.h, inference only); MMS (config.adapter_attn_dim: an attention adapter behind every pre-LN layer) and the head_dim 80
+squeeze and an upsampling GEMM (huggingface/sew.py, thunder_speech_amd/abi/sew.h; fine-tuning in mixed precision only: huggingface/sew_train.py, csrc/sew_train.hip); MMS (config.adapter_attn_dim: an attention adapter behind every pre-LN layer) and the head_dim 80
 of MMS-1B / XLS-R 1B run on csrc/mms.hip and the head_dim 80 kernel of csrc/w2v_attn.hip (include/thunder_speech_amd_mms.h, inference only); training mode (fine-tuning with the conv feature extractor frozen) runs
 through huggingface/train.py; no CPU fallback."""
 from __future__ import annotations
@@ -48,11 +48,11 @@ def feat_extract_output_lengths(conv_kernel, conv_stride, lengths: torch.Tensor,
 # norm, pre-LN): the wav2vec2 layers with WavLMAttention's gated relative-position bias in the attention core (csrc/wavlm.hip, head_dim 64 -- every
 # published WavLM -- fine-tuned with train_precision="bf16" only, csrc/wavlm_train.hip); wav2vec2-conformer with rotary position embeddings
 # (fine-tuned with train_precision="bf16" only, huggingface/conformer_train.py): the wav2vec2 front end and adapter around conformer blocks (huggingface/conformer.py, csrc/conformer.hip,
-# include/thunder_speech_amd_conformer.h); sew (inference only): wav2vec2's post-LN layers at 1 / squeeze_factor of the frame rate between a
+# include/thunder_speech_amd_conformer.h); sew (fine-tuned with train_precision="bf16" only, huggingface/sew_train.py): wav2vec2's post-LN layers at 1 / squeeze_factor of the frame rate between a
 # strided positional conv added to an average pool and an upsampling projection (huggingface/sew.py, csrc/sew.hip, thunder_speech_amd/abi/sew.h).
 # Others (sew-d's disentangled attention, the conformer's relative-position variant ...) have layers this library holds no kernels for and raise.
 # Fine-tuning (huggingface/train.py, TRAINABLE_MODEL_TYPES): every family above but the conformer, which trains on the chain of
-# huggingface/conformer_train.py, and sew.  hubert, unispeech and unispeech-sat train on the
+# huggingface/conformer_train.py, and sew, which trains on the chain of huggingface/sew_train.py (both in mixed precision only).  hubert, unispeech and unispeech-sat train on the
 # wav2vec2 chain (f32 and mixed precision); data2vec-audio on it with one autograd node per layer of its positional stack (PosConvStackLayer,
 # csrc/posconv_stack_train.hip, include/thunder_speech_amd/posconv_stack_train.h); wavlm in mixed precision only.
 SUPPORTED_MODEL_TYPES = ("wav2vec2", "hubert", "data2vec-audio", "unispeech", "unispeech-sat", "wavlm", "wav2vec2-conformer", "sew")
@@ -637,9 +637,13 @@ class HuggingFaceEncoderAdapt(nn.Module):
             # train_precision="fp32", an adapter, mask_feature_prob, an unfrozen feature extractor are refused by name, before any device work
             from .conformer_train import refuse_untrainable as refuse_untrainable_conformer
             refuse_untrainable_conformer(self)
-        if self.training and getattr(self.original_encoder.config, "model_type", "wav2vec2") == "sew":
-            # no backward exists for the strided positional conv, the pool or the upsampler: refused before any device work
-            raise NotImplementedError("sew: fine-tuning is not implemented (inference only); use the module in eval mode")
+        sew = getattr(self.original_encoder.config, "model_type", "wav2vec2") == "sew"
+        if self.training and sew:
+            # sew trains on a chain of its own, in mixed precision only (huggingface/sew_train.py, csrc/sew_train.hip: the squeeze's backward runs on the
+            # matrix-core kernels): train_precision="fp32", a group width other than 24 / 32, mask_feature_prob, an unfrozen feature extractor are
+            # refused by name, before any device work
+            from .sew_train import refuse_untrainable as refuse_untrainable_sew
+            refuse_untrainable_sew(self)
         if self.training and getattr(self.original_encoder.config, "model_type", "wav2vec2") == "wavlm" and self.train_precision != "bf16":
             # the gated relative-position attention trains on the fused mixed-precision kernels only (csrc/wavlm_train.hip); f32 fine-tuning would
             # need a materialised-probability path of its own
@@ -658,6 +662,8 @@ class HuggingFaceEncoderAdapt(nn.Module):
             # masking, dropouts, LayerDrop -- as a chain of autograd nodes on the HIP kernels (huggingface/train.py), f32 arithmetic
             if conformer:
                 from .conformer_train import train_forward
+            elif sew:
+                from .sew_train import train_forward
             else:
                 from .train import train_forward
             h = train_forward(self, x, audio_lengths if self.mask_input else None)

@@ -15,7 +15,8 @@ checkpoint.  With s = config.squeeze_factor, k = config.num_conv_pos_embeddings,
     6. upsample: gelu(linear C -> s C) over all B T2 rows in one GEMM, read row-major as [B][s T2][C]; zero rows up to T (ts_sew_unsqueeze_rows,
        only when T % s != 0: otherwise the GEMM's output already is the result)
 
-Inference only.  T, T2 and every buffer shape are host integers, the key lengths are computed on the device: the forward captures into a hipGraph."""
+This module is the inference plan; train mode runs the same six steps as autograd nodes, in mixed precision only (huggingface/sew_train.py,
+csrc/sew_train.hip).  T, T2 and every buffer shape are host integers, the key lengths are computed on the device: the forward captures into a hipGraph."""
 from __future__ import annotations
 
 from typing import Dict, Optional
