@@ -40,6 +40,7 @@ class Hypothesis:
     text: str
     score: float
     tokens: List[BeamToken] = field(default_factory=list)
+    lm_score: Optional[float] = None      # unweighted log10 LM score (tokens and </s>) of a search with LM fusion (ctc_lm.py); None without
 
 
 def beam_search(logits: Tensor, lengths: Optional[Tensor] = None, blank_idx: int = 0, beam_width: int = 16, token_cap: int = 8,
@@ -73,9 +74,10 @@ def beam_search(logits: Tensor, lengths: Optional[Tensor] = None, blank_idx: int
 
 
 def hypotheses_from_tables(tokens, frames, lengths, scores, counts, itos: List[str], to_text: Callable[[List[int]], str], samples_per_frame: int,
-                           sample_rate: int) -> List[List[Hypothesis]]:
+                           sample_rate: int, lm_scores=None) -> List[List[Hypothesis]]:
     """Host tables (numpy: tokens / frames [B, N, T'], lengths / scores [B, N], counts [B]) -> per clip its hypotheses, best first.
-    `to_text` joins ids into the transcript (the text transform's rule); frame f is at f * samples_per_frame / sample_rate seconds."""
+    `to_text` joins ids into the transcript (the text transform's rule); frame f is at f * samples_per_frame / sample_rate seconds.
+    `lm_scores` [B, N], of a search with LM fusion, fills `lm_score`."""
     out = []
     for b in range(len(counts)):
         clip = []
@@ -83,6 +85,6 @@ def hypotheses_from_tables(tokens, frames, lengths, scores, counts, itos: List[s
             ln = int(lengths[b, n])
             ids = [int(i) for i in tokens[b, n, :ln]]
             toks = [BeamToken(itos[i], int(f), int(f) * samples_per_frame / sample_rate) for i, f in zip(ids, frames[b, n, :ln])]
-            clip.append(Hypothesis(to_text(ids), float(scores[b, n]), toks))
+            clip.append(Hypothesis(to_text(ids), float(scores[b, n]), toks, None if lm_scores is None else float(lm_scores[b, n])))
         out.append(clip)
     return out

@@ -1,0 +1,298 @@
+"""Token-level n-gram shallow fusion for the CTC beam search (no reference counterpart).
+
+The LM's words are the acoustic model's CTC classes: characters for QuartzNet and wav2vec2, sentencepiece pieces for Citrinet.  The host side
+(this module, numpy only) reads an ARPA file (`read_arpa`), matches its words to the classes and compiles the table to a back-off automaton
+(`NGramLM`); `NGramLM.weights(alpha, beta)` forms the f64 factors of one setting on the host, so that the device takes no exp and no log of the
+LM, and `beam_search_lm` runs the three launches of csrc/ctc_beam_lm.hip on them.  The algorithm is specified in capi/ctc_beam_lm.h.  There is
+no CPU path for the search."""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from .ctc_beam import BeamResult
+
+BOS, EOS, UNK = -1, -2, -3                       # ids of <s>, </s>, <unk> inside n-grams; classes are >= 0
+_SPECIAL = {"<s>": BOS, "</s>": EOS, "<unk>": UNK}
+NGram = Tuple[int, ...]
+
+
+def read_arpa(path_or_text: str) -> Tuple[int, List[Dict[Tuple[str, ...], Tuple[float, float]]]]:
+    """Standard ARPA text (a path, or the text itself if it holds a line break) -> (order, tables): tables[n - 1] maps every n-gram (a tuple of
+    words) to (log10 p, log10 back-off).  A missing back-off reads as 0; the highest order has none.  ValueError, naming the line, on malformed
+    input."""
+    if "\n" in path_or_text:
+        text = path_or_text
+    else:
+        with open(path_or_text, encoding="utf-8") as f:
+            text = f.read()
+    counts: Dict[int, int] = {}
+    tables: Dict[int, Dict[Tuple[str, ...], Tuple[float, float]]] = {}
+    section, seen_data, ended = None, False, False       # section: None before \data\, 0 in the counts, n in \n-grams:
+    for no, raw in enumerate(text.splitlines(), 1):
+        line = raw.strip()
+        if not line:
+            continue
+        if ended:
+            raise ValueError(f"read_arpa: line {no}: text after \\end\\: {line!r}")
+        if line == "\\data\\":
+            if seen_data:
+                raise ValueError(f"read_arpa: line {no}: a second \\data\\")
+            seen_data, section = True, 0
+            continue
+        if not seen_data:
+            continue                                     # ARPA allows a preamble before \data\
+        if line == "\\end\\":
+            ended = True
+            continue
+        if line.startswith("\\"):
+            head = line[1:-1].split("-")[0] if line.endswith("-grams:") else ""
+            if not head.isdigit() or int(head) < 1:
+                raise ValueError(f"read_arpa: line {no}: unknown section {line!r}")
+            n = int(head)
+            if n not in counts:
+                raise ValueError(f"read_arpa: line {no}: \\{n}-grams: without an `ngram {n}=` count")
+            if n in tables or n != len(tables) + 1:
+                raise ValueError(f"read_arpa: line {no}: \\{n}-grams: out of order")
+            section, tables[n] = n, {}
+            continue
+        if section == 0:
+            body = line.replace(" ", "").replace("\t", "")
+            if not body.startswith("ngram") or "=" not in body:
+                raise ValueError(f"read_arpa: line {no}: expected `ngram N=count`, got {line!r}")
+            n, _, cnt = body[5:].partition("=")
+            if not n.isdigit() or not cnt.isdigit() or int(n) < 1 or int(n) in counts:
+                raise ValueError(f"read_arpa: line {no}: bad count line {line!r}")
+            counts[int(n)] = int(cnt)
+            continue
+        fields = line.split()
+        n, top = section, section == max(counts)
+        if len(fields) not in ((n + 1,) if top else (n + 1, n + 2)):
+            raise ValueError(f"read_arpa: line {no}: a {n}-gram line has {n + 1}{'' if top else f' or {n + 2}'} fields, got {len(fields)}: {line!r}")
+        try:
+            p = float(fields[0])
+            bo = float(fields[n + 1]) if len(fields) == n + 2 else 0.0
+        except ValueError:
+            raise ValueError(f"read_arpa: line {no}: not a number in {line!r}") from None
+        if not (math.isfinite(p) or p == -math.inf) or not math.isfinite(bo):
+            raise ValueError(f"read_arpa: line {no}: not a finite number in {line!r}")
+        gram = tuple(fields[1:n + 1])
+        if gram in tables[n]:
+            raise ValueError(f"read_arpa: line {no}: the {n}-gram {' '.join(gram)!r} twice")
+        tables[n][gram] = (p, bo)
+    if not seen_data:
+        raise ValueError("read_arpa: line 1: no \\data\\ section")
+    if not ended:
+        raise ValueError(f"read_arpa: line {len(text.splitlines())}: no \\end\\ marker")
+    if not counts:
+        raise ValueError("read_arpa: line 1: no `ngram N=count` lines")
+    order = max(counts)
+    for n in range(1, order + 1):
+        if n not in counts or n not in tables:
+            raise ValueError(f"read_arpa: line {len(text.splitlines())}: order {n} of {order} is missing")
+        if len(tables[n]) != counts[n]:
+            raise ValueError(f"read_arpa: line {len(text.splitlines())}: {len(tables[n])} {n}-grams, the \\data\\ section announces {counts[n]}")
+    return order, [tables[n] for n in range(1, order + 1)]
+
+
+@dataclass
+class BeamLMResult(BeamResult):
+    """`BeamResult` of the fused search (capi/ctc_beam_lm.h: ts_ctc_beam_lm_search); `scores` are the logs of the fused masses."""
+    lm_scores: Any = None     # f32 [B, n_best]         unweighted log10 LM score of the hypothesis, </s> included where it was applied
+
+
+@dataclass
+class LMWeights:
+    """Device tables of one (alpha, beta) setting (capi/ctc_beam_lm.h: ts_ctc_lm); `struct` holds their addresses."""
+    alpha: float
+    beta: float
+    tensors: dict
+    struct: object
+
+
+class NGramLM:
+    """A back-off n-gram LM over CTC classes, compiled to an automaton.
+
+    `grams` maps n-grams of ids (classes >= 0, BOS, EOS, UNK) to (log10 p, log10 back-off).  States: the empty context (state 0) and every
+    prefix, shorter than the order, of an n-gram -- that is every n-gram of order < N and every context of one --, numbered by (length, ids), so
+    that a back-off arc leads to a lower state.  The state after a history is the longest suffix of the history that is a state.  Per state:
+    `arcs[s]`, sorted by class, of (class, log10 p, next state = the longest suffix of context + class that is a state), and the back-off arc
+    `backoff[s]` = (log10 back-off -- 0 where the context has no line of its own --, the longest proper suffix that is a state).  State 0 has
+    an arc for every class but the blank: a class without a unigram takes <unk>'s unigram, or `unk_log10`, and leads to state 0.
+    A table that is not prefix-closed (an ARPA file of a toolkit always is) can hold a context + class that is a state without being an
+    n-gram; its state then carries an arc with the backed-off log10 p, so that the lookup equals the dictionary back-off for any table."""
+
+    def __init__(self, order: int, grams: Dict[NGram, Tuple[float, float]], n_classes: int, blank_idx: int, unk_log10: float = -10.0, dropped: int = 0):
+        self.order, self.n_classes, self.blank_idx, self.unk_log10, self.dropped = int(order), int(n_classes), int(blank_idx), float(unk_log10), int(dropped)
+        for g in grams:
+            if not 1 <= len(g) <= order or any(c == blank_idx or c >= n_classes or c < UNK for c in g):
+                raise ValueError(f"NGramLM: bad n-gram {g}")
+        # n-grams the automaton can reach: <s> only in front, </s> only at the end, <unk> only as the unigram
+        ok = lambda g: BOS not in g[1:] and EOS not in g[:-1] and (UNK not in g or g == (UNK,))
+        self.grams = {g: (float(p), float(bo)) for g, (p, bo) in grams.items() if ok(g)}
+        self.has_bos = any(g[0] == BOS for g in self.grams)
+        self.has_eos = any(g[-1] == EOS for g in self.grams)
+        self.has_unk = (UNK,) in self.grams
+        ctx = {g[:k] for g in self.grams for k in range(min(len(g), order - 1) + 1) if k == 0 or g[k - 1] >= 0 or g[k - 1] == BOS}
+        self.contexts: List[NGram] = sorted(ctx | {()}, key=lambda c: (len(c), c))
+        self.state_id: Dict[NGram, int] = {c: i for i, c in enumerate(self.contexts)}
+        self.start_state = self.state_id.get((BOS,), 0)
+        self.arcs: List[List[Tuple[int, float, int]]] = [[] for _ in self.contexts]
+        self.backoff: List[Tuple[float, int]] = [(self.grams.get(c, (0.0, 0.0))[1], self._suffix_state(c[1:])) if c else (0.0, 0) for c in self.contexts]
+        for g, (p, _) in self.grams.items():
+            if g[-1] >= 0:
+                self.arcs[self.state_id[g[:-1]]].append((g[-1], p, self._suffix_state(g[max(len(g) - order + 1, 0):] if order > 1 else ())))
+        for y in self.contexts:
+            if y and y[-1] >= 0 and y not in self.grams:                 # a state that is no n-gram: its parent state gets the backed-off arc
+                p, floor = self._chain(y[:-1], y[-1])
+                if not floor:
+                    self.arcs[self.state_id[y[:-1]]].append((y[-1], p, self.state_id[y]))
+        have = {a[0] for a in self.arcs[0]}
+        self.arcs[0] += [(c, self._chain((), c)[0], 0) for c in range(n_classes) if c != blank_idx and c not in have]
+        for a in self.arcs:
+            a.sort()
+        self.eos_log10 = [self._chain(c, EOS)[0] if self.has_eos else 0.0 for c in self.contexts]
+        self._cache: dict = {}
+
+    def _suffix_state(self, c: NGram) -> int:
+        while c not in self.state_id:
+            c = c[1:]
+        return self.state_id[c]
+
+    def _chain(self, c: NGram, w: int) -> Tuple[float, bool]:
+        """(log10 P(w | context c), whether it is the floor of a word without a unigram) by the dictionary back-off."""
+        total = 0.0
+        while True:
+            if c + (w,) in self.grams:
+                return total + self.grams[c + (w,)][0], False
+            if not c:
+                return total + (self.grams[(UNK,)][0] if self.has_unk else self.unk_log10), True
+            total += self.grams.get(c, (0.0, 0.0))[1]
+            c = c[1:]
+
+    @classmethod
+    def from_arpa(cls, path: str, itos: Sequence[str], blank_idx: int, token_of: Optional[Callable[[str], str]] = None, unk_log10: float = -10.0) -> "NGramLM":
+        """The LM of an ARPA file over the classes `itos`: a word is the class c with itos[c] == word (after `token_of(word)`, if given; the
+        first such class); <s>, </s> and <unk> are special, the blank never matches.  N-grams with any other unmatched word are dropped and
+        counted in `dropped`."""
+        order, tables = read_arpa(path)
+        ids: Dict[str, int] = {}
+        for c, tok in enumerate(itos):
+            if c != blank_idx and tok not in _SPECIAL:
+                ids.setdefault(tok, c)
+        grams, dropped = {}, 0
+        for table in tables:
+            for words, val in table.items():
+                g = tuple(_SPECIAL[w] if w in _SPECIAL else ids.get(token_of(w) if token_of else w) for w in words)
+                if None in g:
+                    dropped += 1
+                elif g not in grams:
+                    grams[g] = val
+        return cls(order, grams, len(itos), blank_idx, unk_log10, dropped)
+
+    # ---- lookup on the host (what the kernel does on the device tables) ----
+    @property
+    def n_states(self) -> int:
+        return len(self.contexts)
+
+    def step(self, state: int, c: int) -> Tuple[float, int]:
+        """(log10 P(c | state), next state): down the back-off arcs to the first state with an arc of class c."""
+        total = 0.0
+        while True:
+            for cls_, p, nxt in self.arcs[state]:
+                if cls_ == c:
+                    return total + p, nxt
+            if state == 0:
+                raise ValueError(f"NGramLM.step: class {c} has no LM id (the blank, or outside the classes)")
+            bo, state_next = self.backoff[state]
+            total, state = total + bo, state_next
+        raise AssertionError
+
+    def eos(self, state: int) -> float:
+        return self.eos_log10[state]
+
+    def score(self, labels: Sequence[int], eos: bool = False) -> float:
+        """log10 P(labels [</s>]) from the start state."""
+        s, total = self.start_state, 0.0
+        for c in labels:
+            p, s = self.step(s, int(c))
+            total += p
+        return total + (self.eos(s) if eos and self.has_eos else 0.0)
+
+    # ---- device tables ----
+    def tables(self, alpha: float, beta: float) -> Dict[str, np.ndarray]:
+        """The numpy tables of ts_ctc_lm for one setting: arc factor 10^(alpha log10 p) e^beta, back-off factor 10^(alpha log10 bo), </s> factor
+        10^(alpha log10 P(</s> | state)) (no beta), each one f64 formed here."""
+        alpha, beta = float(alpha), float(beta)
+        begin = np.zeros(self.n_states + 1, np.int32)
+        begin[1:] = np.cumsum([len(a) for a in self.arcs])
+        flat = [x for a in self.arcs for x in a]
+        arc_log = np.array([x[1] for x in flat], np.float64).reshape(-1)
+        bo_log = np.array([b[0] for b in self.backoff], np.float64)
+        eos_log = np.array(self.eos_log10, np.float64)
+        return {"arc_begin": begin, "arc_class": np.array([x[0] for x in flat], np.int32).reshape(-1),
+                "arc_next": np.array([x[2] for x in flat], np.int32).reshape(-1),
+                "arc_factor": np.power(10.0, alpha * arc_log) * math.exp(beta), "arc_log10": arc_log,
+                "bo_next": np.array([b[1] for b in self.backoff], np.int32), "bo_factor": np.power(10.0, alpha * bo_log), "bo_log10": bo_log,
+                "eos_factor": np.power(10.0, alpha * eos_log), "eos_log10": eos_log}
+
+    def weights(self, alpha: float, beta: float, device=None) -> LMWeights:
+        """The device tables of one setting, cached per (alpha, beta, device)."""
+        import torch
+        from . import _lib
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        key = (float(alpha), float(beta), str(dev))
+        if key not in self._cache:
+            if dev.type != "cuda":
+                raise RuntimeError("NGramLM.weights: GPU tensors required (no CPU fallback)")
+            t = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in self.tables(alpha, beta).items()}
+            st = _lib.CtcLm(n_states=self.n_states, n_arcs=int(t["arc_class"].numel()), start_state=self.start_state, has_eos=int(self.has_eos),
+                            **{k: v.data_ptr() for k, v in t.items()})
+            self._cache[key] = LMWeights(float(alpha), float(beta), t, st)
+        return self._cache[key]
+
+
+def beam_search_lm(logits, lm: NGramLM, alpha: float, beta: float, lengths=None, blank_idx: int = 0, beam_width: int = 16, token_cap: int = 8,
+                   n_best: int = 1, score_eos: bool = True):
+    """`beam_search` with the n-gram LM fused into the search: score = log(CTC mass of the surviving alignments) + alpha ln 10 log10 P_LM(tokens
+    [</s>]) + beta (number of tokens).  Returns a `BeamLMResult`: `BeamResult` extended by `lm_scores` (f32 [B, n_best]: the unweighted log10 LM score)."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    from .ctc_align import _logits_f32
+    lg = _logits_f32(logits, "beam_search_lm")
+    b, v, t = lg.shape
+    if b == 0 or t == 0:
+        raise ValueError("beam_search_lm: empty logits")
+    if not isinstance(lm, NGramLM):
+        raise TypeError("beam_search_lm: lm must be an NGramLM")
+    if lm.n_classes != v or lm.blank_idx != int(blank_idx):
+        raise ValueError(f"beam_search_lm: the LM was compiled for {lm.n_classes} classes with blank {lm.blank_idx}, the logits have {v} with blank {int(blank_idx)}")
+    dev = lg.device
+    il = None if lengths is None else lengths.to(device=dev, dtype=torch.int64).to(torch.int32).contiguous()
+    L = _lib.lib()
+    nbytes = L.ts_ctc_beam_lm_workspace_bytes(b, t, int(beam_width), int(token_cap))
+    if nbytes < 0:
+        _lib.check(int(nbytes), "ts_ctc_beam_lm_workspace_bytes")
+    n_best = int(n_best)
+    if not 1 <= n_best <= int(beam_width):
+        raise ValueError("beam_search_lm: 1 <= n_best <= beam_width required")
+    w = lm.weights(alpha, beta, dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    tokens = torch.empty(b, n_best, t, dtype=torch.int32, device=dev)
+    frames = torch.empty(b, n_best, t, dtype=torch.int32, device=dev)
+    out_len = torch.empty(b, n_best, dtype=torch.int32, device=dev)
+    scores = torch.empty(b, n_best, dtype=torch.float32, device=dev)
+    lm_scores = torch.empty(b, n_best, dtype=torch.float32, device=dev)
+    counts = torch.empty(b, dtype=torch.int32, device=dev)
+    st = L.ts_ctc_beam_lm_search(lg.data_ptr(), b, v, t, lg.stride(1), None if il is None else il.data_ptr(), int(blank_idx), int(beam_width),
+                                 int(token_cap), n_best, int(bool(score_eos)), C.byref(w.struct), tokens.data_ptr(), frames.data_ptr(),
+                                 out_len.data_ptr(), scores.data_ptr(), lm_scores.data_ptr(), counts.data_ptr(), ws.data_ptr(),
+                                 torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(st, "ts_ctc_beam_lm_search")
+    return BeamLMResult(tokens, frames, out_len, scores, counts, lm_scores)

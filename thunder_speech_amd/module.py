@@ -281,26 +281,42 @@ class BaseCTCModule(_Base):
 
     # ------------------------------------------------------------------------------------------------------------------
     # CTC prefix beam search (no reference counterpart), on the kernels of csrc/ctc_beam.hip (ctc_beam.py).  predict() is untouched.
-    def predict_beam(self, x: Tensor, beam_width: int = 16, token_cap: int = 8) -> List[str]:
+    def predict_beam(self, x: Tensor, beam_width: int = 16, token_cap: int = 8, lm=None, alpha: float = 0.5, beta: float = 1.0) -> List[str]:
         """Transcription by CTC prefix beam search: per clip the transcript whose alignments carry the most probability among the
-        `beam_width` prefixes kept per frame (predict() follows the single best path instead).  Every clip is treated as full length."""
+        `beam_width` prefixes kept per frame (predict() follows the single best path instead).  Every clip is treated as full length.
+        With `lm` (a ctc_lm.NGramLM over this module's classes) the n-gram LM is fused into the search on the kernels of
+        csrc/ctc_beam_lm.hip: LM weight `alpha`, token bonus `beta`."""
         from . import ctc_align as A
         from . import ctc_beam as B
         logits, _ = self._eval_logits(x, None)
-        res = B.beam_search(logits, None, self.text_transform.vocab.blank_idx, beam_width, token_cap, 1)
+        if lm is None:
+            res = B.beam_search(logits, None, self.text_transform.vocab.blank_idx, beam_width, token_cap, 1)
+        else:
+            from . import ctc_lm as M
+            res = M.beam_search_lm(logits, lm, alpha, beta, None, self.text_transform.vocab.blank_idx, beam_width, token_cap, 1)
         ids, counts = A._to_host(res.tokens[:, 0], res.lengths[:, 0])                                                    # one copy
         return self.text_transform.decode_collapsed(torch.from_numpy(ids), torch.from_numpy(counts))
 
-    def predict_nbest(self, x: Tensor, n_best: int, beam_width: int = 16, token_cap: int = 8) -> List[List["Hypothesis"]]:
+    def predict_nbest(self, x: Tensor, n_best: int, beam_width: int = 16, token_cap: int = 8, lm=None, alpha: float = 0.5,
+                      beta: float = 1.0) -> List[List["Hypothesis"]]:
         """The `n_best` best transcripts of each clip under CTC prefix beam search, best first: text, score (log of the summed probability
-        of the transcript's surviving alignments) and per token the frame and time at which it entered the hypothesis."""
+        of the transcript's surviving alignments) and per token the frame and time at which it entered the hypothesis.  With `lm` the
+        search is the fused one of predict_beam: `score` is the fused score and every hypothesis carries `lm_score`, the unweighted
+        log10 LM score of its tokens and </s>."""
         from . import ctc_align as A
         from . import ctc_beam as B
         logits, _ = self._eval_logits(x, None)
-        res = B.beam_search(logits, None, self.text_transform.vocab.blank_idx, beam_width, token_cap, n_best)
-        tokens, frames, lengths, scores, counts = A._to_host(res.tokens, res.frames, res.lengths, res.scores, res.counts)  # one copy
+        if lm is None:
+            res = B.beam_search(logits, None, self.text_transform.vocab.blank_idx, beam_width, token_cap, n_best)
+            tokens, frames, lengths, scores, counts = A._to_host(res.tokens, res.frames, res.lengths, res.scores, res.counts)  # one copy
+            lm_scores = None
+        else:
+            from . import ctc_lm as M
+            res = M.beam_search_lm(logits, lm, alpha, beta, None, self.text_transform.vocab.blank_idx, beam_width, token_cap, n_best)
+            tokens, frames, lengths, scores, counts, lm_scores = A._to_host(res.tokens, res.frames, res.lengths, res.scores, res.counts,
+                                                                            res.lm_scores)                                # one copy
         return B.hypotheses_from_tables(tokens, frames, lengths, scores, counts, self.text_transform.vocab.itos, self.text_transform._ids_to_text,
-                                        self.samples_per_frame, self.sample_rate)
+                                        self.samples_per_frame, self.sample_rate, lm_scores)
 
     def training_step(self, batch, batch_idx: int) -> torch.Tensor:
         audio, audio_lengths, texts = batch
