@@ -2,8 +2,8 @@
 include/thunder_speech_amd_wavlm_train.h, include/thunder_speech_amd_conformer.h, include/thunder_speech_amd_mms.h,
 include/thunder_speech_amd_mms_train.h, include/thunder_speech_amd_mms_adapter_train.h, include/thunder_speech_amd/posconv_stack_train.h,
 thunder_speech_amd/abi/sew.h, thunder_speech_amd/abi/ctc_align.h, thunder_speech_amd/abi/ctc_beam.h, thunder_speech_amd/abi/conformer_train.h,
-thunder_speech_amd/abi/train/sew_train.h and thunder_speech_amd/capi/ctc_beam_lm.h (beam search with n-gram LM fusion; it declares the one
-struct outside the core header, `CtcLm`, the LM tables of a call).
+thunder_speech_amd/abi/train/sew_train.h, thunder_speech_amd/capi/ctc_beam_lm.h (beam search with n-gram LM fusion; it declares the one
+struct outside the core header, `CtcLm`, the LM tables of a call) and thunder_speech_amd/lora/lora_train.h (LoRA fine-tuning).
 
 The header is the only copy of the ABI: `read_header` derives every prototype, struct and TS_* constant from it and
 `lib()` applies the result, so a new entry point needs the header and its .hip definition and nothing here.  A C type
@@ -37,6 +37,7 @@ CONFORMER_TRAIN_HEADER = os.path.join(PKG, "abi", "conformer_train.h")    # elev
 
 SEW_TRAIN_HEADER = os.path.join(PKG, "abi", "train", "sew_train.h")    # twelfth companion (SEW fine-tuning), versioned on its own; in abi/train/ (the header count of abi/ is pinned too)
 CTC_BEAM_LM_HEADER = os.path.join(PKG, "capi", "ctc_beam_lm.h")    # thirteenth companion (beam search with n-gram LM fusion), versioned on its own; in capi/ (the header counts of include/ and abi/ are pinned)
+LORA_HEADER = os.path.join(PKG, "lora", "lora_train.h")    # fourteenth companion (LoRA fine-tuning of the attention projections), versioned on its own; in lora/ (the header counts of include/, abi/ and capi/ are pinned)
 
 # Parameters and struct fields: these scalars, `[const] <struct>*` as POINTER(struct), every other pointer to one of
 # _POINTEES (const or not, any depth) as c_void_p.  Return types: _RETURNS only.
@@ -123,6 +124,8 @@ SEW_TRAIN_ABI_VERSION = SEW_TRAIN_DEFINES["TS_SEW_TRAIN_ABI_VERSION"]
 CTC_BEAM_LM_SIGNATURES, CTC_BEAM_LM_STRUCTS, CTC_BEAM_LM_DEFINES = _read_installed_header(CTC_BEAM_LM_HEADER)
 CTC_BEAM_LM_ABI_VERSION = CTC_BEAM_LM_DEFINES["TS_CTC_BEAM_LM_ABI_VERSION"]
 CtcLm = CTC_BEAM_LM_STRUCTS["ts_ctc_lm"]
+LORA_SIGNATURES, _, LORA_DEFINES = _read_installed_header(LORA_HEADER)
+LORA_ABI_VERSION = LORA_DEFINES["TS_LORA_ABI_VERSION"]
 TcsDesc, FrontendDesc, WgradItem =STRUCTS["ts_tcs_desc"], STRUCTS["ts_frontend_desc"], STRUCTS["ts_wgrad_item"]
 TcsLaunch = STRUCTS["ts_tcs_launch"]
 EXPORTED_SYMBOLS = list(SIGNATURES)
@@ -154,13 +157,13 @@ def lib() -> C.CDLL:
     missing = [s for s in EXPORTED_SYMBOLS + list(WAVLM_SIGNATURES) + list(WAVLM_TRAIN_SIGNATURES) + list(CONFORMER_SIGNATURES) + list(MMS_SIGNATURES) +
                list(MMS_TRAIN_SIGNATURES) + list(MMS_ADAPTER_TRAIN_SIGNATURES) + list(POSCONV_STACK_TRAIN_SIGNATURES) + list(SEW_SIGNATURES) +
                list(CTC_ALIGN_SIGNATURES) + list(CTC_BEAM_SIGNATURES) + list(CONFORMER_TRAIN_SIGNATURES) + list(SEW_TRAIN_SIGNATURES) +
-               list(CTC_BEAM_LM_SIGNATURES) if not hasattr(L, s)]
+               list(CTC_BEAM_LM_SIGNATURES) + list(LORA_SIGNATURES) if not hasattr(L, s)]
     if missing:
         raise RuntimeError(f"thunder_speech_amd: {path} does not export {missing}; rebuild it")
     for name, (restype, argtypes) in {**SIGNATURES, **WAVLM_SIGNATURES, **WAVLM_TRAIN_SIGNATURES, **CONFORMER_SIGNATURES, **MMS_SIGNATURES,
                                       **MMS_TRAIN_SIGNATURES, **MMS_ADAPTER_TRAIN_SIGNATURES, **POSCONV_STACK_TRAIN_SIGNATURES, **SEW_SIGNATURES,
                                       **CTC_ALIGN_SIGNATURES, **CTC_BEAM_SIGNATURES, **CONFORMER_TRAIN_SIGNATURES, **SEW_TRAIN_SIGNATURES,
-                                      **CTC_BEAM_LM_SIGNATURES}.items():
+                                      **CTC_BEAM_LM_SIGNATURES, **LORA_SIGNATURES}.items():
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     if L.ts_abi_version() != ABI_VERSION:
@@ -205,6 +208,9 @@ def lib() -> C.CDLL:
     if L.ts_ctc_beam_lm_abi_version() != CTC_BEAM_LM_ABI_VERSION:
         raise RuntimeError(f"thunder_speech_amd: {path} reports CTC beam search LM fusion ABI {L.ts_ctc_beam_lm_abi_version()}, the header "
                            f"{CTC_BEAM_LM_HEADER} declares {CTC_BEAM_LM_ABI_VERSION}; rebuild it")
+    if L.ts_lora_abi_version() != LORA_ABI_VERSION:
+        raise RuntimeError(f"thunder_speech_amd: {path} reports LoRA training ABI {L.ts_lora_abi_version()}, the header "
+                           f"{LORA_HEADER} declares {LORA_ABI_VERSION}; rebuild it")
     _lib = L
     return L
 

@@ -36,7 +36,7 @@ def needs_build() -> bool:
         return True
     deps = sources() + glob.glob(os.path.join(PKG, "csrc", "*.hpp")) + glob.glob(os.path.join(ROOT, "include", "*.h")) + \
         glob.glob(os.path.join(ROOT, "include", "thunder_speech_amd", "*.h")) + glob.glob(os.path.join(PKG, "abi", "*.h")) + \
-        glob.glob(os.path.join(PKG, "abi", "train", "*.h")) + glob.glob(os.path.join(PKG, "capi", "*.h"))
+        glob.glob(os.path.join(PKG, "abi", "train", "*.h")) + glob.glob(os.path.join(PKG, "capi", "*.h")) + glob.glob(os.path.join(PKG, "lora", "*.h"))
     return any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps)
 
 
@@ -68,7 +68,7 @@ def build(force: bool = False, verbose: bool = True, only=None) -> str:
             continue
         cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffast-math", "-fno-finite-math-only",
                "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc"), "-I" + os.path.join(PKG, "abi"),
-               "-I" + os.path.join(PKG, "capi"), f'-DTS_BUILD_TARGET="{ARCH}"', "-c", src, "-o", obj]
+               "-I" + os.path.join(PKG, "capi"), "-I" + os.path.join(PKG, "lora"), f'-DTS_BUILD_TARGET="{ARCH}"', "-c", src, "-o", obj]
         cmd[1:1] = os.environ.get("TS_CXXFLAGS", "").split()        # diagnostic builds (tools/variants.py), e.g. TS_CXXFLAGS=-DTS_STAMP
         if verbose:
             print(" ".join(cmd), flush=True)
@@ -102,11 +102,11 @@ def build_asan(verbose: bool = True) -> str:
                                                                  glob.glob(os.path.join(ROOT, "include", "*.h")) +
                                                                  glob.glob(os.path.join(ROOT, "include", "thunder_speech_amd", "*.h")) +
                                                                  glob.glob(os.path.join(PKG, "abi", "*.h")) + glob.glob(os.path.join(PKG, "abi", "train", "*.h")) +
-                                                                 glob.glob(os.path.join(PKG, "capi", "*.h"))):
+                                                                 glob.glob(os.path.join(PKG, "capi", "*.h")) + glob.glob(os.path.join(PKG, "lora", "*.h"))):
             continue
         cmd = [hipcc, f"--offload-arch={ARCH}", "-O2", "-g", "-std=c++17", "-fPIC", "-fsanitize=address,undefined", "-Wno-option-ignored",
                "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc"), "-I" + os.path.join(PKG, "abi"),
-               "-I" + os.path.join(PKG, "capi"), f'-DTS_BUILD_TARGET="{ARCH}"', "-c", src, "-o", obj]
+               "-I" + os.path.join(PKG, "capi"), "-I" + os.path.join(PKG, "lora"), f'-DTS_BUILD_TARGET="{ARCH}"', "-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         procs.append((src, subprocess.Popen(cmd)))

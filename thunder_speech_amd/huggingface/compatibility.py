@@ -78,7 +78,15 @@ def load_huggingface_checkpoint(model_name: str, target_lang: Optional[str] = No
 
     Teaching such a checkpoint a new language trains the attention adapters and the CTC head on the frozen base:
         module = load_huggingface_checkpoint(dir, target_lang=...)
-        adapters = module.encoder.adapter_finetuning(init=True)     # {name: parameter}; optimise these and module.decoder.parameters()"""
+        adapters = module.encoder.adapter_finetuning(init=True)     # {name: parameter}; optimise these and module.decoder.parameters()
+
+    Every other checkpoint on the wav2vec2 chain (wav2vec2, HuBERT, data2vec-audio, UniSpeech, WavLM, XLS-R) fine-tunes parameter-efficiently by
+    low-rank adaptation of its attention projections on the frozen base, in mixed precision:
+        module = load_huggingface_checkpoint(dir)
+        module.encoder.train_precision = "bf16"
+        lora = module.encoder.lora_finetuning(rank=16, alpha=32.0, targets=("q_proj", "v_proj"))    # {name: parameter}; optimise these and the decoder
+        ...                                                          # module.encoder.lora_state_dict() ships the adaptation without the base
+        module.encoder.merge_lora()                                  # folds W += (alpha / rank) B A into the base weights for deployment"""
     from transformers import AutoFeatureExtractor, AutoModelForCTC, AutoTokenizer
     tokenizer_kwargs = {}
     if target_lang is not None:

@@ -585,7 +585,105 @@ class HuggingFaceEncoderAdapt(nn.Module):
         if getattr(cfg, "model_type", "wav2vec2") == "sew":
             from .sew import SEWPlan
             return self._cache.get(params, lambda: SEWPlan(cfg, self.original_encoder.state_dict(), device, self.precision))
+        if getattr(self, "lora", None) is not None:
+            # eval with unmerged LoRA (a validation step during training): the plan is packed from the effective weights W + s B A, formed with
+            # merge_lora()'s f32 operations, and keyed on A and B too, so an optimizer step on them re-packs it
+            params += list(self.lora.parameters())
+
+            def build():
+                sd = dict(self.original_encoder.state_dict())
+                for i, target, _ in self._lora_items():
+                    sd[f"encoder.layers.{i}.attention.{target}.weight"] = self._lora_effective(i, target)
+                return Wav2Vec2Plan(cfg, sd, device, self.precision)
+            return self._cache.get(params, build)
         return self._cache.get(params, lambda: Wav2Vec2Plan(cfg, self.original_encoder.state_dict(), device, self.precision))
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # Low-rank adaptation (LoRA, Hu et al. 2021) of the attention projections on a frozen base (no reference counterpart): per layer and target
+    # y = x W^T + b + (alpha / rank) (x A^T) B^T with A [rank][in], B [out][rank] trainable.  Train mode (train_precision="bf16" only) keeps the
+    # two paths apart (huggingface/train.py LoRALinear, csrc/lora_train.hip): the low-rank term is a product of its own at f32 accumulation, never
+    # folded into the bf16 copy of W, where a small B would vanish in the rounding.  Eval mode runs the inference plan on the merged weight
+    # W + s B A (f32), which precision="bf16" rounds to bf16 as it rounds every weight: train and eval outputs differ by that rounding.
+    def _lora_items(self):
+        """(layer index, target name, {lora_A, lora_B}) of every LoRA pair, in layer order."""
+        return [(i, target, pair) for i, layer in enumerate(self.lora.layers) for target, pair in layer.items()]
+
+    def _lora_effective(self, i: int, target: str) -> torch.Tensor:
+        """W + s B A of one target in f32: what merge_lora() writes and what the eval-mode plan packs (the same operations: bit-equal)."""
+        pair = self.lora.layers[i][target]
+        w = getattr(self.original_encoder.encoder.layers[i].attention, target).weight
+        with torch.no_grad():
+            return w.detach().float() + self.lora_scale * (pair["lora_B"].detach().float() @ pair["lora_A"].detach().float())
+
+    def lora_finetuning(self, rank: int = 8, alpha: float = 16.0, targets=("q_proj", "v_proj")) -> Dict[str, nn.Parameter]:
+        """Put the encoder into the LoRA fine-tuning regime: every encoder parameter is frozen, and per transformer layer and target projection
+        (`targets`: any of q_proj, k_proj, v_proj, out_proj) a pair lora_A [rank][in] (kaiming_uniform_, a = sqrt(5)) / lora_B [out][rank] (zeros) is
+        created on this module, so that `state_dict()` and the module's `configure_optimizers` see them.  Returns them, {name: parameter}, named as in
+        `state_dict()` (`lora.layers.{i}.{target}.lora_A` / `.lora_B`); hand them and the CTC head (the module's `decoder`) to the optimizer.
+        Train mode then runs huggingface/train.py with LoRALinear in place of the target products (train_precision="bf16" only); with any base
+        parameter trainable it refuses by name.  wav2vec2-conformer, sew and MMS (adapter_attn_dim) checkpoints are refused by name."""
+        from .train import LORA_RANKS, LORA_TARGETS, refuse_lora
+        if getattr(self, "lora", None) is not None:
+            raise RuntimeError("lora_finetuning: this encoder already carries LoRA parameters (merge_lora() folds them into the base)")
+        if isinstance(rank, bool) or not isinstance(rank, int) or rank not in LORA_RANKS:
+            raise ValueError(f"lora_finetuning: rank must be one of {LORA_RANKS} (the low-rank kernels' widths), got {rank!r}")
+        targets = (targets,) if isinstance(targets, str) else tuple(targets)
+        bad = [t for t in targets if t not in LORA_TARGETS]
+        if bad or not targets or len(set(targets)) != len(targets):
+            raise ValueError(f"lora_finetuning: targets must be distinct names out of {LORA_TARGETS}, got {targets!r}")
+        if not float(alpha) > 0.0:
+            raise ValueError(f"lora_finetuning: alpha must be positive, got {alpha!r}")
+        enc = self.original_encoder
+        refuse_lora(enc.config)
+        for p in enc.parameters():
+            p.requires_grad_(False)
+        layers = nn.ModuleList()
+        for layer in enc.encoder.layers:
+            pairs = nn.ModuleDict()
+            for target in (t for t in LORA_TARGETS if t in targets):                 # a fixed order, whatever the caller's
+                w = getattr(layer.attention, target).weight
+                a = torch.empty(rank, w.shape[1], dtype=torch.float32, device=w.device)
+                nn.init.kaiming_uniform_(a, a=math.sqrt(5))
+                pairs[target] = nn.ParameterDict({"lora_A": nn.Parameter(a),
+                                                  "lora_B": nn.Parameter(torch.zeros(w.shape[0], rank, dtype=torch.float32, device=w.device))})
+            layers.append(pairs)
+        self.lora = nn.ModuleDict({"layers": layers})
+        self.lora_rank, self.lora_alpha, self.lora_scale = int(rank), float(alpha), float(alpha) / int(rank)
+        self._param_epoch = getattr(self, "_param_epoch", 0) + 1       # BaseCTCModule._weights_stamp: the set of parameters changed
+        return {"lora." + n: p for n, p in self.lora.named_parameters()}
+
+    def merge_lora(self) -> None:
+        """Fold W += s B A into the base weights (f32) and remove the LoRA parameters; the base stays frozen as it is.  Eval-mode outputs before
+        and after are bit-equal: the unmerged plan is packed from the same f32 sums."""
+        if getattr(self, "lora", None) is None:
+            raise RuntimeError("merge_lora: this encoder carries no LoRA parameters (lora_finetuning() creates them)")
+        with torch.no_grad():
+            for i, target, _ in self._lora_items():
+                w = getattr(self.original_encoder.encoder.layers[i].attention, target).weight
+                w.copy_(self._lora_effective(i, target).to(w.dtype))
+        del self.lora
+        del self.lora_rank, self.lora_alpha, self.lora_scale
+        self._param_epoch = getattr(self, "_param_epoch", 0) + 1
+
+    def lora_state_dict(self) -> Dict[str, torch.Tensor]:
+        """The LoRA tensors alone ({`lora.layers.{i}.{target}.lora_A` / `.lora_B`: tensor}, detached copies): an adaptation ships without the base."""
+        if getattr(self, "lora", None) is None:
+            raise RuntimeError("lora_state_dict: this encoder carries no LoRA parameters (lora_finetuning() creates them)")
+        return {"lora." + n: p.detach().clone() for n, p in self.lora.named_parameters()}
+
+    def load_lora_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
+        """Load what lora_state_dict() returned into the parameters lora_finetuning() created (same rank and targets: the keys and shapes must match)."""
+        if getattr(self, "lora", None) is None:
+            raise RuntimeError("load_lora_state_dict: call lora_finetuning() with the adaptation's rank, alpha and targets first")
+        mine = {"lora." + n: p for n, p in self.lora.named_parameters()}
+        if set(sd) != set(mine):
+            raise KeyError(f"load_lora_state_dict: keys differ (missing {sorted(set(mine) - set(sd))[:3]}, unexpected {sorted(set(sd) - set(mine))[:3]})")
+        for n, p in mine.items():
+            if tuple(sd[n].shape) != tuple(p.shape):
+                raise ValueError(f"load_lora_state_dict: {n} has shape {tuple(sd[n].shape)}, expected {tuple(p.shape)}")
+        with torch.no_grad():
+            for n, p in mine.items():
+                p.copy_(sd[n])
 
     def _plan_frozen(self, device) -> Wav2Vec2Plan:
         """The plan the training path runs the frozen conv feature extractor on: built from and keyed on the feature extractor's parameters
@@ -632,6 +730,9 @@ class HuggingFaceEncoderAdapt(nn.Module):
 
     def forward(self, audio: torch.Tensor, audio_lengths: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         conformer = getattr(self.original_encoder.config, "model_type", "wav2vec2") == "wav2vec2-conformer"
+        if self.training and getattr(self, "lora", None) is not None:
+            from .train import refuse_untrainable_lora
+            refuse_untrainable_lora(self)               # LoRA: f32 training, a trainable base parameter: by name, before any device work
         if self.training and conformer:
             # the conformer trains on a chain of its own, in mixed precision only (huggingface/conformer_train.py, csrc/conformer_train.hip):
             # train_precision="fp32", an adapter, mask_feature_prob, an unfrozen feature extractor are refused by name, before any device work

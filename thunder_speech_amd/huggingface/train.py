@@ -5,6 +5,8 @@ WavLMAttentionFused).  In mixed precision the attention core is fused at head_di
 (AttentionFused80, ts_mms_attention_train_* of csrc/mms_train.hip on the head_dim 80 kernels of csrc/w2v_attn_train.hip: the XLS-R 1B geometry); every other head dimension, and f32 training, take the materialised Attention node.
 MMS checkpoints (config.adapter_attn_dim) train adapter-only: the base frozen (HuggingFaceEncoderAdapt.adapter_finetuning), the attention adapter
 behind every layer one fused node (AttnAdapter, csrc/mms_adapter_train.hip).
+Every other checkpoint on this chain also trains by low-rank adaptation of its attention projections on a frozen base
+(HuggingFaceEncoderAdapt.lora_finetuning; mixed precision only): LoRALinear, the frozen product plus the low-rank launches of csrc/lora_train.hip.
 `HubertModel`, `UniSpeechModel` and `UniSpeechSatModel` train on the wav2vec2 chain as it is (HuBERT's feature-projection LayerNorm is optional);
 `Data2VecAudioModel` trains on it with its stacked positional convs as one node per layer (PosConvStackLayer, csrc/posconv_stack_train.hip).
 
@@ -178,6 +180,62 @@ class LinearMixed(torch.autograd.Function):
         if want_db and not fused_db:
             db = _colsum(dy, rows, n)
         return dx, dw, db
+
+
+class LoRALinear(torch.autograd.Function):
+    """nn.Linear with a FROZEN weight and bias plus low-rank (LoRA) terms on column slices of its output, in mixed precision (csrc/lora_train.hip,
+    thunder_speech_amd/lora/lora_train.h):  y = x W^T + b, then y[:, c0 : c0 + n_t] += s (x A_t^T) B_t^T per target t = (c0, A_t [r][k], B_t [n_t][r]).
+    The fused q | k | v product passes up to three targets (each its own slice of [rows][3 c]), out_proj one (c0 = 0).
+    The base product is LinearMixed's, call for call (same casts, same GEMM, same split-K rule), without its weight gradient; the low-rank path is a
+    path of its own (ts_lora_fwd behind the GEMM, ts_lora_bwd behind the data-gradient GEMM), never folded into the bf16 copy of W.
+    Saved for the backward: x16 (bf16, half the f32 input), wT16, and per target u16 = bf16(x A^T) ([rows][r]: kept, not recomputed) and the bf16
+    transposes of A and B.  Arguments: x, w, b, scale, offsets (c0 per target), then A_0, B_0, A_1, B_1, ..."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, scale, offsets, *ab):
+        x, w = _f32c(x), _f32c(w)
+        n, k = w.shape
+        rows = x.numel() // k
+        L = _lib.lib()
+        x16, _ = _cast(x.view(rows, k), rows, k, True, False)
+        w16, wt16 = _cast(w, n, k, True, ctx.needs_input_grad[0])
+        y = torch.empty(*x.shape[:-1], n, dtype=torch.float32, device=x.device)
+        _gemm_nt_splitk(x16, k, w16, k, y, rows, n, k, bias=_f32c(b) if b is not None else None, min_k=2048)
+        saved = [x16, wt16]
+        for t, c0 in enumerate(offsets):
+            a, bb = ab[2 * t].detach(), ab[2 * t + 1].detach()
+            r, nt = a.shape[0], bb.shape[0]
+            a16, b16 = a.to(torch.bfloat16).contiguous(), bb.to(torch.bfloat16).contiguous()
+            u16 = torch.empty(rows, r, dtype=torch.bfloat16, device=x.device)
+            _lib.check(L.ts_lora_fwd(x16.data_ptr(), rows, k, a16.data_ptr(), b16.data_ptr(), nt, r, float(scale), y.data_ptr() + 4 * c0, n,
+                                     u16.data_ptr(), _s(x)), "ts_lora_fwd")
+            saved += [u16, a16.t().contiguous(), b16.t().contiguous()]
+        ctx.save_for_backward(*saved)
+        ctx.geom = (rows, n, k, x.shape, float(scale), tuple(offsets))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x16, wt16, *per = ctx.saved_tensors
+        rows, n, k, xshape, scale, offsets = ctx.geom
+        dy = _f32c(dy)
+        L = _lib.lib()
+        dy16, _ = _cast(dy.view(rows, n), rows, n, True, False)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty(xshape, dtype=torch.float32, device=dy.device)
+            _gemm_nt_splitk(dy16, n, wt16, _pad32(n), dx, rows, k, n)
+        grads = []
+        for t, c0 in enumerate(offsets):
+            u16, at16, bt16 = per[3 * t: 3 * t + 3]
+            r, nt = at16.shape[1], bt16.shape[1]
+            da = torch.empty(r, k, dtype=torch.float32, device=dy.device)
+            db = torch.empty(nt, r, dtype=torch.float32, device=dy.device)
+            ws = torch.empty(L.ts_lora_bwd_workspace(rows, k, nt, r), dtype=torch.uint8, device=dy.device)
+            _lib.check(L.ts_lora_bwd(dy16.data_ptr() + 2 * c0, n, x16.data_ptr(), u16.data_ptr(), rows, k, nt, r, scale, at16.data_ptr(), bt16.data_ptr(),
+                                     dx.data_ptr() if dx is not None else None, da.data_ptr(), db.data_ptr(), ws.data_ptr(), _s(dy)), "ts_lora_bwd")
+            grads += [da if ctx.needs_input_grad[5 + 2 * t] else None, db if ctx.needs_input_grad[6 + 2 * t] else None]
+        return (dx, None, None, None, None) + tuple(grads)
 
 
 class FFNActLinear(torch.autograd.Function):
@@ -935,9 +993,43 @@ def refuse_untrainable(adapt, mixed: bool) -> None:
                                   f"{len(unfrozen)} of its parameters have requires_grad=True (first: feature_extractor.{unfrozen[0]})")
 
 
+LORA_TARGETS = ("q_proj", "k_proj", "v_proj", "out_proj")
+LORA_RANKS = (8, 16, 32, 64)                      # ts_lora_fwd / ts_lora_bwd
+
+
+def refuse_lora(cfg) -> None:
+    """Raise NotImplementedError, by name, for a model LoRA has no path for (no device work; HuggingFaceEncoderAdapt.lora_finetuning() calls it)."""
+    from .encoder import has_attn_adapters
+    model_type = getattr(cfg, "model_type", "wav2vec2")
+    if model_type in ("wav2vec2-conformer", "sew"):
+        raise NotImplementedError(f"HIP fine-tuning path: LoRA on model_type={model_type!r} is not implemented (it trains on a chain of its own; LoRA "
+                                  f"covers the wav2vec2 chain: {', '.join(TRAINABLE_MODEL_TYPES)})")
+    if has_attn_adapters(cfg):
+        raise NotImplementedError(f"HIP fine-tuning path: LoRA together with adapter_attn_dim={cfg.adapter_attn_dim} is not implemented (MMS checkpoints "
+                                  "train their attention adapters: HuggingFaceEncoderAdapt.adapter_finetuning())")
+    if int(cfg.hidden_size) % 32:
+        raise NotImplementedError(f"HIP fine-tuning path: LoRA needs hidden_size a multiple of 32 (the mixed-precision products), got {cfg.hidden_size}")
+
+
+def refuse_untrainable_lora(adapt) -> None:
+    """The LoRA regime's refusals, by name, before any device work: nothing if `adapt` carries no LoRA parameters."""
+    if getattr(adapt, "lora", None) is None:
+        return
+    refuse_lora(adapt.original_encoder.config)
+    if getattr(adapt, "train_precision", "fp32") != "bf16":
+        raise NotImplementedError(f"HIP fine-tuning path: LoRA with train_precision={adapt.train_precision!r} is not implemented (the low-rank launches "
+                                  'are mixed precision only); use train_precision="bf16"')
+    base = [n for n, p in adapt.original_encoder.named_parameters() if p.requires_grad]
+    if base:
+        raise NotImplementedError(f"HIP fine-tuning path: LoRA trains on a frozen base; {len(base)} base parameters have requires_grad=True "
+                                  f"(first: {base[0]}). HuggingFaceEncoderAdapt.lora_finetuning() freezes them; leave them frozen, or merge_lora() first")
+
+
 def _train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
     from .encoder import feat_extract_output_lengths
+    refuse_untrainable_lora(adapt)
     refuse_untrainable(adapt, _MIXED)
+    lora = getattr(adapt, "lora", None)
     enc = adapt.original_encoder
     cfg = enc.config
     dev = audio.device
@@ -1007,14 +1099,24 @@ def _train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
         wqkv = torch.cat([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight], 0)
         bqkv = torch.cat([att.q_proj.bias, att.k_proj.bias, att.v_proj.bias], 0)
 
+        lo = lora.layers[i] if lora is not None else {}            # this layer's LoRA targets: {projection name: {lora_A, lora_B}}
+
+        def project(x, w, b, names):
+            """`linear`, or LoRALinear where one of the projections `names` (stacked along w's rows, c rows each) carries LoRA parameters."""
+            hit = [(j * c, lo[nm]) for j, nm in enumerate(names) if nm in lo]
+            if not hit:
+                return linear(x, w, b)
+            return LoRALinear.apply(x, w, b, adapt.lora_scale, tuple(c0 for c0, _ in hit), *[t for _, m in hit for t in (m["lora_A"], m["lora_B"])])
+
         def attend(x):
             seed = next_seed() if p_att > 0 else 0
+            qkv = project(x, wqkv, bqkv, ("q_proj", "k_proj", "v_proj"))
             if wavlm:                                               # the gate reads the same rows the QKV projection multiplies
                 g = WavLMGate.apply(x, att.gru_rel_pos_linear.weight, att.gru_rel_pos_linear.bias, att.gru_rel_pos_const.view(-1))
-                ctxt = WavLMAttentionFused.apply(linear(x, wqkv, bqkv), key_len, g, rb, heads, p_att, seed)
+                ctxt = WavLMAttentionFused.apply(qkv, key_len, g, rb, heads, p_att, seed)
             else:
-                ctxt = attention(linear(x, wqkv, bqkv), key_len, heads, p_att, seed)
-            return dropout(linear(ctxt, att.out_proj.weight, att.out_proj.bias), p_hid)
+                ctxt = attention(qkv, key_len, heads, p_att, seed)
+            return dropout(project(ctxt, att.out_proj.weight, att.out_proj.bias, ("out_proj",)), p_hid)
 
         def ffn(x):
             z = linear(x, ff.intermediate_dense.weight, None)

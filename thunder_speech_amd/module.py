@@ -94,12 +94,16 @@ class BaseCTCModule(_Base):
     def _weights_stamp(self):
         """Changes whenever a parameter / buffer of the model is written in place (optimizer step, load_state_dict, manual edits): the sum
         of the tensors' version counters.  The tensor list is rebuilt on train() / _apply() (.to, .half ...) / load_state_dict; code that
-        REPLACES a Parameter object calls reset_inference_graphs()."""
+        REPLACES a Parameter object calls reset_inference_graphs().  An encoder that adds or removes Parameters of its own (LoRA:
+        HuggingFaceEncoderAdapt.lora_finetuning / merge_lora) counts that in `_param_epoch`: the list is rebuilt when it moves, and it is part
+        of the stamp."""
         ts = getattr(self, "_stamp_tensors", None)
-        if ts is None:
+        epoch = getattr(self.encoder, "_param_epoch", 0)
+        if ts is None or self.__dict__.get("_stamp_epoch", 0) != epoch:
             ts = self._stamp_tensors = [t for m in (self.audio_transform, self.encoder, self.decoder)
                                         for t in list(m.parameters()) + list(m.buffers())]
-        return sum(t._version for t in ts)
+            self.__dict__["_stamp_epoch"] = epoch
+        return sum(t._version for t in ts) + (epoch << 48)
 
     def reset_inference_graphs(self) -> None:
         self.__dict__.pop("_stamp_tensors", None)
