@@ -1,5 +1,5 @@
 /*
- * thunder_speech_amd_conformer.h -- companion C ABI of thunder_speech_amd.h: the conformer block of wav2vec2-conformer checkpoints with
+ * thunder_speech_amd/conformer.h -- companion C ABI of thunder_speech_amd.h: the conformer block of wav2vec2-conformer checkpoints with
  * rotary position embeddings.  The same shared library exports these entry points; the conventions are the core header's (DEVICE pointers
  * into caller-owned buffers, `stream` a hipStream_t passed as void*, 0 / TS_E* / positive hipError_t returns, nothing allocates, frees or
  * synchronises, so every call can be captured into a hipGraph).  The core ABI (TS_ABI_VERSION) and the WavLM companions are unchanged by

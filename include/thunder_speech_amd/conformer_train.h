@@ -1,12 +1,12 @@
 /*
- * thunder_speech_amd/abi/conformer_train.h -- companion C ABI of include/thunder_speech_amd.h: what mixed-precision FINE-TUNING of a rotary
+ * thunder_speech_amd/conformer_train.h -- companion C ABI of include/thunder_speech_amd.h: what mixed-precision FINE-TUNING of a rotary
  * wav2vec2-conformer needs beyond the wav2vec2 training kernels (csrc/conformer_train.hip; the Python chain is huggingface/conformer_train.py):
  * the convolution module between its two pointwise products with BatchNorm on batch statistics, forward and backward, the transpose of the
  * rotary rotation, and the feed-forward activation pair with an activation code.  The same shared library exports these entry points; the
  * conventions are the core header's (DEVICE pointers into caller-owned buffers, `stream` a hipStream_t passed as void*, 0 / TS_EINVAL /
  * TS_EUNSUPPORTED / positive hipError_t returns, workspace sizes from the *_workspace queries, nothing allocates, frees or synchronises,
  * argument checks before any launch).  The core ABI (TS_ABI_VERSION) and the other companions are unchanged by this header; it is versioned on
- * its own by TS_CONFORMER_TRAIN_ABI_VERSION.  (Like sew.h, ctc_align.h and ctc_beam.h it lives inside the package: INTEGRATION.md says why.)
+ * its own by TS_CONFORMER_TRAIN_ABI_VERSION.
  *
  * transformers call sites (modeling_wav2vec2_conformer.py, train mode): Wav2Vec2ConformerConvolutionModule.forward (glu, depthwise_conv,
  * batch_norm, activation), Wav2Vec2ConformerSelfAttention._apply_rotary_embedding, Wav2Vec2ConformerFeedForward.forward (intermediate_act_fn,

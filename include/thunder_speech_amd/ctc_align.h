@@ -1,10 +1,10 @@
 /*
- * thunder_speech_amd/abi/ctc_align.h -- companion C ABI of include/thunder_speech_amd.h: "when was it said".  CTC forced alignment of a known
+ * thunder_speech_amd/ctc_align.h -- companion C ABI of include/thunder_speech_amd.h: "when was it said".  CTC forced alignment of a known
  * transcript (a Viterbi recursion over the blank-extended target) and the frame spans of the greedy transcript (csrc/ctc_align.hip).  The same
  * shared library exports these entry points; the conventions are the core header's (DEVICE pointers into caller-owned buffers, `stream` a
  * hipStream_t passed as void*, 0 / TS_EINVAL / TS_EUNSUPPORTED / positive hipError_t returns, nothing allocates, frees or synchronises, so every
  * call can be captured into a hipGraph).  The core ABI (TS_ABI_VERSION) and the other companions are unchanged by this header; it is versioned on
- * its own by TS_CTC_ALIGN_ABI_VERSION.  (Like sew.h this companion lives inside the package, not under include/: INTEGRATION.md says why.)
+ * its own by TS_CTC_ALIGN_ABI_VERSION.
  *
  * No reference call site: the reference answers "what was said" only (module.py:98-101 returns bare strings).  The inputs are the ones
  * ts_ctc_loss takes: logits [B][V][pitch] f32 BEFORE softmax, time contiguous, and the int32 targets / lengths ts_ctc_prepare writes.

@@ -1,11 +1,10 @@
 /*
- * thunder_speech_amd/abi/ctc_beam.h -- companion C ABI of include/thunder_speech_amd.h: CTC prefix beam search with n-best output
+ * thunder_speech_amd/ctc_beam.h -- companion C ABI of include/thunder_speech_amd.h: CTC prefix beam search with n-best output
  * (csrc/ctc_beam.hip).  Where ts_greedy_decode follows one path, this decoder sums the probability of all alignments of a transcript and returns
  * the n best transcripts with their CTC scores.  The same shared library exports these entry points; the conventions are the core header's
  * (DEVICE pointers into caller-owned buffers, `stream` a hipStream_t passed as void*, 0 / TS_EINVAL / TS_EUNSUPPORTED / positive hipError_t
  * returns, nothing allocates, frees or synchronises, so every call can be captured into a hipGraph).  The core ABI (TS_ABI_VERSION) and the other
- * companions are unchanged by this header; it is versioned on its own by TS_CTC_BEAM_ABI_VERSION.  (Like sew.h and ctc_align.h this companion
- * lives inside the package, not under include/: INTEGRATION.md says why.)
+ * companions are unchanged by this header; it is versioned on its own by TS_CTC_BEAM_ABI_VERSION.
  *
  * No reference call site: the reference decodes greedily only (module.py:98-101).  Input: logits [B][V][pitch] f32 BEFORE softmax, time contiguous.
  *

@@ -1,11 +1,11 @@
 /*
- * thunder_speech_amd/capi/ctc_beam_lm.h -- companion C ABI of include/thunder_speech_amd.h: CTC prefix beam search with shallow fusion of a
+ * thunder_speech_amd/ctc_beam_lm.h -- companion C ABI of include/thunder_speech_amd.h: CTC prefix beam search with shallow fusion of a
  * token-level n-gram language model (csrc/ctc_beam_lm.hip).  The LM's words are the acoustic model's CTC classes (characters, or sentencepiece
  * pieces); thunder_speech_amd/ctc_lm.py reads an ARPA file and compiles the tables this header takes.  The same shared library exports these
  * entry points; the conventions are the core header's (DEVICE pointers into caller-owned buffers, `stream` a hipStream_t passed as void*,
  * 0 / TS_EINVAL / TS_EUNSUPPORTED / positive hipError_t returns, nothing allocates, frees or synchronises, so every call can be captured into a
  * hipGraph).  The core ABI (TS_ABI_VERSION), ctc_beam.h and the other companions are unchanged by this header; it is versioned on its own by
- * TS_CTC_BEAM_LM_ABI_VERSION.  (It lives in capi/, not in abi/ or under include/: INTEGRATION.md says why.)
+ * TS_CTC_BEAM_LM_ABI_VERSION.
  *
  * No reference call site: the reference decodes greedily only.  Input: logits [B][V][pitch] f32 BEFORE softmax, time contiguous.
  *

@@ -1,5 +1,5 @@
 /*
- * lora_train.h -- companion C ABI of thunder_speech_amd.h: the low-rank (LoRA) term of a frozen linear projection as a trainable node
+ * thunder_speech_amd/lora_train.h -- companion C ABI of thunder_speech_amd.h: the low-rank (LoRA) term of a frozen linear projection as a trainable node
  * (csrc/lora_train.hip).  It is what LoRA fine-tuning of the attention projections needs next to the launches of the core header: the base
  * product y = x W^T + b and its data gradient dx = dy W stay the core header's bf16 GEMM (ts_gemm_nt_bf16*), these entry points add the low-rank
  * term on top of them.  The same shared library exports these entry points; the conventions are the core header's (DEVICE pointers into

@@ -1,5 +1,5 @@
 /*
- * thunder_speech_amd_mms.h -- companion C ABI of thunder_speech_amd.h: what the MMS checkpoints (facebook/mms-1b-all, -fl102, -l1107) and
+ * thunder_speech_amd/mms.h -- companion C ABI of thunder_speech_amd.h: what the MMS checkpoints (facebook/mms-1b-all, -fl102, -l1107) and
  * XLS-R 1B need beyond the wav2vec2 launches -- the attention core at head_dim 80 and the per-layer attention adapter.  The same shared
  * library exports these entry points; the conventions are the core header's (DEVICE pointers into caller-owned buffers, `stream` a
  * hipStream_t passed as void*, 0 / TS_E* / positive hipError_t returns, nothing allocates, frees or synchronises, so every call can be

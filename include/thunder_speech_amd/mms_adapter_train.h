@@ -1,7 +1,7 @@
 /*
- * thunder_speech_amd_mms_adapter_train.h -- companion C ABI of thunder_speech_amd.h: the MMS attention adapter as a trainable node, an
+ * thunder_speech_amd/mms_adapter_train.h -- companion C ABI of thunder_speech_amd.h: the MMS attention adapter as a trainable node, an
  * out-of-place forward and a fused backward (csrc/mms_adapter_train.hip).  It is what adapter-only fine-tuning of an MMS checkpoint needs next
- * to the launches of the core header and of thunder_speech_amd_mms_train.h: the base is frozen, the adapters (and the CTC head) train.  The same
+ * to the launches of the core header and of thunder_speech_amd/mms_train.h: the base is frozen, the adapters (and the CTC head) train.  The same
  * shared library exports these entry points; the conventions are the core header's (DEVICE pointers into caller-owned buffers, `stream` a
  * hipStream_t passed as void*, 0 / TS_E* / positive hipError_t returns, nothing allocates, frees or synchronises, so every call can be captured
  * into a hipGraph).  The core ABI (TS_ABI_VERSION) and the other companions are unchanged by this header; it is versioned on its own by
@@ -28,7 +28,7 @@ extern "C" {
 int ts_mms_adapter_train_abi_version(void);
 
 /* Forward: y [rows][c] f32 = the adapter applied to h, which is left untouched (autograd keeps it).  The kernel and the arithmetic are those of
- * ts_mms_attn_adapter_fwd (thunder_speech_amd_mms.h) without a fused LayerNorm behind it: for equal inputs and precision, y equals bit for bit
+ * ts_mms_attn_adapter_fwd (thunder_speech_amd/mms.h) without a fused LayerNorm behind it: for equal inputs and precision, y equals bit for bit
  * what that call leaves in a copy of h.
  * precision 0: w1 / w2 f32, every product on the f32 matrix-core instruction.  precision 1: w1 / w2 bf16, u and r rounded to bf16 for the two
  * products (f32 accumulation); LayerNorm and the sum into y f32.

@@ -1,5 +1,5 @@
 /*
- * thunder_speech_amd_mms_train.h -- companion C ABI of thunder_speech_amd.h: the fused attention core for mixed-precision FINE-TUNING at
+ * thunder_speech_amd/mms_train.h -- companion C ABI of thunder_speech_amd.h: the fused attention core for mixed-precision FINE-TUNING at
  * head_dim 80 (XLS-R 1B / MMS geometry: hidden 1280, 16 heads), forward and backward (entry points in csrc/mms_train.hip, kernels in csrc/w2v_attn_train.hip).  The same shared library exports
  * these entry points; the conventions are the core header's (DEVICE pointers into caller-owned buffers, `stream` a hipStream_t passed as
  * void*, 0 / TS_E* / positive hipError_t returns, nothing allocates, frees or synchronises, so every call can be captured into a hipGraph).

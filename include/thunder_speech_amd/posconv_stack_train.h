@@ -5,8 +5,7 @@
  * shared library exports these entry points; the conventions are the core header's (DEVICE pointers into caller-owned buffers, `stream` a
  * hipStream_t passed as void*, 0 / TS_E* / positive hipError_t returns, nothing allocates, frees or synchronises, so every call can be captured
  * into a hipGraph).  The core ABI (TS_ABI_VERSION) and the other companions are unchanged by this header; it is versioned on its own by
- * TS_POSCONV_STACK_TRAIN_ABI_VERSION.  (Companion headers live in this directory from this one on: include/ itself holds the core header and the
- * first six companions.)
+ * TS_POSCONV_STACK_TRAIN_ABI_VERSION.
  *
  * Reference call site: transformers' Data2VecAudioPositionalConvEmbedding (num_conv_pos_embeddings layers of Data2VecAudioPositionalConvLayer)
  * under the reference's training_step (src/thunder/module.py:102-127).  Per layer, on time-major f32 rows x [B][T][C]:

@@ -1,10 +1,10 @@
 /*
- * thunder_speech_amd/abi/sew.h -- companion C ABI of include/thunder_speech_amd.h: the two launches a SEW encoder (transformers' SEWModel, the
+ * thunder_speech_amd/sew.h -- companion C ABI of include/thunder_speech_amd.h: the two launches a SEW encoder (transformers' SEWModel, the
  * "squeezed and efficient" wav2vec2) needs next to the wav2vec2 launches of the core header (csrc/sew.hip).  The same shared library exports these
  * entry points; the conventions are the core header's (DEVICE pointers into caller-owned buffers, `stream` a hipStream_t passed as void*,
  * 0 / TS_EINVAL / TS_EUNSUPPORTED / positive hipError_t returns, nothing allocates, frees or synchronises, so every call can be captured into a
  * hipGraph).  The core ABI (TS_ABI_VERSION) and the other companions are unchanged by this header; it is versioned on its own by
- * TS_SEW_ABI_VERSION.  (This companion lives inside the package, not under include/: INTEGRATION.md says why.)
+ * TS_SEW_ABI_VERSION.
  *
  * Reference call site: SEWEncoder.forward (transformers/models/sew/modeling_sew.py), reached from the reference's
  * `_HuggingFaceEncoderAdapt.forward` (src/thunder/huggingface/compatibility.py:31-42) for a SEW checkpoint:

@@ -1,11 +1,11 @@
 /*
- * thunder_speech_amd/abi/train/sew_train.h -- companion C ABI of include/thunder_speech_amd.h: what fine-tuning a SEW encoder (transformers' SEWModel) in
- * mixed precision needs next to abi/sew.h and the wav2vec2 training launches of the core header (csrc/sew_train.hip): the squeeze's forward that
+ * thunder_speech_amd/sew_train.h -- companion C ABI of include/thunder_speech_amd.h: what fine-tuning a SEW encoder (transformers' SEWModel) in
+ * mixed precision needs next to sew.h and the wav2vec2 training launches of the core header (csrc/sew_train.hip): the squeeze's forward that
  * keeps its pre-activation, its data gradient and its weight gradient, all on the matrix cores.  The same shared library exports these entry
  * points; the conventions are the core header's (DEVICE pointers into caller-owned buffers, `stream` a hipStream_t passed as void*,
  * 0 / TS_EINVAL / TS_EUNSUPPORTED / positive hipError_t returns, nothing allocates, frees or synchronises).  No atomics: equal arguments give equal
- * bits.  The core ABI, abi/sew.h (TS_SEW_ABI_VERSION) and the other companions are unchanged by this header; it is versioned on its own by
- * TS_SEW_TRAIN_ABI_VERSION.  (This companion lives in abi/train/ inside the package, neither under include/ nor next to abi/sew.h: INTEGRATION.md says why.)
+ * bits.  The core ABI, sew.h (TS_SEW_ABI_VERSION) and the other companions are unchanged by this header; it is versioned on its own by
+ * TS_SEW_TRAIN_ABI_VERSION.
  *
  * Reference call site: the training-mode SEWEncoder.forward (transformers/models/sew/modeling_sew.py) under autograd, reached from the reference's
  * `BaseCTCModule.training_step` (src/thunder/module.py:102-127) through `_HuggingFaceEncoderAdapt.forward`.

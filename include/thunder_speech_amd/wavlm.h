@@ -1,5 +1,5 @@
 /*
- * thunder_speech_amd_wavlm.h -- companion C ABI of thunder_speech_amd.h: the WavLM encoder's gated relative-position
+ * thunder_speech_amd/wavlm.h -- companion C ABI of thunder_speech_amd.h: the WavLM encoder's gated relative-position
  * attention.  The same shared library exports these entry points; the conventions are the core header's (DEVICE pointers
  * into caller-owned buffers, `stream` a hipStream_t passed as void*, 0 / TS_E* / positive hipError_t returns, nothing
  * allocates, frees or synchronises, so every call can be captured into a hipGraph).  The core ABI (TS_ABI_VERSION) is

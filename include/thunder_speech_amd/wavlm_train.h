@@ -1,5 +1,5 @@
 /*
- * thunder_speech_amd_wavlm_train.h -- second companion C ABI of thunder_speech_amd.h: mixed-precision FINE-TUNING of the WavLM
+ * thunder_speech_amd/wavlm_train.h -- second companion C ABI of thunder_speech_amd.h: mixed-precision FINE-TUNING of the WavLM
  * encoder's gated relative-position attention (forward and backward without a [t][t] buffer, the gate and the position-bias
  * embedding with their gradients).  The same shared library exports these entry points; the conventions are the core header's
  * (DEVICE pointers into caller-owned buffers, `stream` a hipStream_t passed as void*, 0 / TS_E* / positive hipError_t returns,

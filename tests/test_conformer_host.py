@@ -1,15 +1,9 @@
 """wav2vec2-conformer on the CPU: the host rotary table against transformers, which configurations are accepted or refused (each refusal by
-name), the refusal of fine-tuning, and the companion C header (include/thunder_speech_amd_conformer.h) next to the unchanged core ABI."""
-import ctypes
-import os
-import re
-
+name), and the refusal of fine-tuning.  (The companion C header: tests/test_abi_headers_host.py.)"""
 import pytest
 import torch
 
 transformers = pytest.importorskip("transformers")
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 CFG = dict(hidden_size=128, num_hidden_layers=2, num_attention_heads=2, intermediate_size=256, vocab_size=32, conv_dim=(32,) * 7,
            conv_kernel=(10, 3, 3, 3, 3, 2, 2), conv_stride=(5, 2, 2, 2, 2, 2, 2), num_conv_pos_embeddings=16, num_conv_pos_embedding_groups=4,
@@ -81,28 +75,3 @@ def test_conformer_training_mode_is_refused_by_name_before_any_device_work():
     enc.eval()
     with pytest.raises(RuntimeError):                                  # eval mode reaches the GPU check (no CPU path)
         enc(torch.zeros(1, 4000), torch.tensor([4000]))
-
-
-def _declared(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ts_[a-z0-9_]+)\s*\(", src)))
-
-
-def test_companion_header_parses_and_no_name_is_declared_twice():
-    from thunder_speech_amd import _lib
-    path = os.path.join(ROOT, "include", "thunder_speech_amd_conformer.h")
-    sigs, structs, defines = _lib.read_header(open(path).read())
-    assert defines["TS_CONFORMER_ABI_VERSION"] == 1 and _lib.CONFORMER_ABI_VERSION == 1 and not structs
-    conformer = _declared(path)
-    assert sorted(sigs) == conformer == sorted(_lib.CONFORMER_SIGNATURES)
-    assert conformer == sorted(["ts_conformer_abi_version", "ts_conformer_glu_dwconv_fwd", "ts_conformer_layernorm_rotary_fwd",
-                                "ts_conformer_linear_fwd"])
-    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-    assert sigs["ts_conformer_glu_dwconv_fwd"][1] == [vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, vp, vp]
-    assert sigs["ts_conformer_layernorm_rotary_fwd"][1] == [vp, vp, vp, f32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp]
-    assert sigs["ts_conformer_linear_fwd"][1] == [vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, i64, i32, i32, i32, i32, vp]
-    core = _declared(os.path.join(ROOT, "include", "thunder_speech_amd.h"))
-    assert len(core) == 123
-    headers = [core, conformer] + [_declared(os.path.join(ROOT, "include", h)) for h in ("thunder_speech_amd_wavlm.h", "thunder_speech_amd_wavlm_train.h")]
-    names = [n for h in headers for n in h]
-    assert len(names) == len(set(names))

@@ -1,22 +1,19 @@
 """N-gram shallow fusion on the CPU: the ARPA reader, the back-off automaton of thunder_speech_amd/ctc_lm.py against the textbook dictionary
-back-off, the companion C header (thunder_speech_amd/capi/ctc_beam_lm.h) next to the unchanged other headers, the argument checks of the
-launcher (made-up pointers: none of these calls reaches a launch), the launch-config and workspace formulas, and the refusal of CPU tensors."""
+back-off, the pre-pass shared with the search without an LM, the argument checks of the launcher (made-up pointers: none of these calls
+reaches a launch), the launch-config and workspace formulas, and the refusal of CPU tensors.  (The companion C header:
+tests/test_abi_headers_host.py.)"""
 import ctypes
-import glob
 import itertools
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "thunder_speech_amd", "capi", "ctc_beam_lm.h")
 ARPA = os.path.join(ROOT, "tests", "golden", "lm_tiny.arpa")
-NAMES = sorted(["ts_ctc_beam_lm_abi_version", "ts_ctc_beam_lm_launch_config", "ts_ctc_beam_lm_workspace_bytes", "ts_ctc_beam_lm_search"])
 ITOS = ["<blank>", "a", "c", "o", "t", "x"]                                  # "x" has no unigram in the fixture: an OOV class
 
 
@@ -160,61 +157,7 @@ def test_weights_tables_are_formed_on_the_host_per_setting():
     assert (z["arc_factor"] == 1.0).all() and (z["bo_factor"] == 1.0).all() and (z["eos_factor"] == 1.0).all()
 
 
-# ---- header and ABI ------------------------------------------------------------------------------------------------------------------------------
-def _declared(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ts_[a-z0-9_]+)\s*\(", src)))
-
-
-def test_companion_header_parses_and_declares_exactly_the_four_names():
-    from thunder_speech_amd import _lib
-    assert _lib.CTC_BEAM_LM_HEADER == HEADER
-    text = open(HEADER).read()
-    sigs, structs, defines = _lib.read_header(text)
-    assert defines["TS_CTC_BEAM_LM_ABI_VERSION"] == 1 and _lib.CTC_BEAM_LM_ABI_VERSION == 1
-    assert sorted(sigs) == _declared(HEADER) == NAMES
-    assert sorted(_lib.CTC_BEAM_LM_SIGNATURES) == NAMES
-    assert all(_lib.CTC_BEAM_LM_SIGNATURES[n] == sigs[n] for n in NAMES if n != "ts_ctc_beam_lm_search")     # (each parse makes its own struct class)
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    assert not re.search(r"\b(size_t|double)\b", code)                       # only the types read_header maps
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    assert list(structs) == ["ts_ctc_lm"]
-    assert [(n, t) for n, t in structs["ts_ctc_lm"]._fields_] == [(n, i32) for n in ("n_states", "n_arcs", "start_state", "has_eos")] + [
-        (n, vp) for n in ("arc_begin", "arc_class", "arc_next", "arc_factor", "arc_log10", "bo_next", "bo_factor", "bo_log10", "eos_factor", "eos_log10")]
-    assert [(n, t) for n, t in _lib.CtcLm._fields_] == [(n, t) for n, t in structs["ts_ctc_lm"]._fields_]
-    lmp = ctypes.POINTER(_lib.CtcLm)
-    S = _lib.CTC_BEAM_LM_SIGNATURES
-    assert S["ts_ctc_beam_lm_abi_version"] == (ctypes.c_int, [])
-    assert S["ts_ctc_beam_lm_launch_config"] == (ctypes.c_int, [i32, i32, i32, vp, vp, vp])
-    assert S["ts_ctc_beam_lm_workspace_bytes"] == (i64, [i32, i32, i32, i32])
-    assert S["ts_ctc_beam_lm_search"] == (ctypes.c_int, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, lmp, vp, vp, vp, vp, vp, vp, vp, vp])
-    for step in ("word-level LMs", "lexicon constraints", "hot-word boosting", "neural LMs"):
-        assert step in text                                                   # the header names what is out of scope
-
-
-def test_no_other_header_or_table_holds_the_names():
-    from thunder_speech_amd import _lib
-    for table in (_lib.SIGNATURES, _lib.WAVLM_SIGNATURES, _lib.WAVLM_TRAIN_SIGNATURES, _lib.CONFORMER_SIGNATURES, _lib.MMS_SIGNATURES,
-                  _lib.MMS_TRAIN_SIGNATURES, _lib.MMS_ADAPTER_TRAIN_SIGNATURES, _lib.POSCONV_STACK_TRAIN_SIGNATURES, _lib.SEW_SIGNATURES,
-                  _lib.CTC_ALIGN_SIGNATURES, _lib.CTC_BEAM_SIGNATURES, _lib.CONFORMER_TRAIN_SIGNATURES, _lib.SEW_TRAIN_SIGNATURES):
-        assert not set(table) & set(NAMES)
-    assert not set(_lib.EXPORTED_SYMBOLS) & set(NAMES)
-    others = glob.glob(os.path.join(ROOT, "include", "**", "*.h"), recursive=True) + glob.glob(os.path.join(ROOT, "thunder_speech_amd", "abi", "**", "*.h"), recursive=True)
-    assert len(others) == 13
-    for path in others:
-        assert not set(_declared(path)) & set(NAMES), path
-    assert glob.glob(os.path.join(ROOT, "thunder_speech_amd", "capi", "*")) == [HEADER]
-    assert sorted(_lib.CTC_BEAM_SIGNATURES) == [n.replace("_lm", "") for n in NAMES]               # the search without an LM keeps its four
-
-
-def test_built_library_defines_the_four_symbols():
-    from thunder_speech_amd import build as b
-    path = b.build(verbose=False)
-    nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    defined = {line.split()[-1] for line in nm.splitlines() if line.strip()}
-    assert set(NAMES) <= defined
-
-
+# ---- the sources ---------------------------------------------------------------------------------------------------------------------------------
 def test_the_candidate_pre_pass_is_shared_through_a_header():
     csrc = os.path.join(ROOT, "thunder_speech_amd", "csrc")
     beam, fused, shared = (open(os.path.join(csrc, n)).read() for n in ("ctc_beam.hip", "ctc_beam_lm.hip", "ctc_beam_cand.hpp"))
@@ -222,7 +165,7 @@ def test_the_candidate_pre_pass_is_shared_through_a_header():
     for src in (beam, fused):
         assert '#include "ctc_beam_cand.hpp"' in src and "void ctc_beam_cand_kernel(" not in src and not re.search(r'#include\s+"[^"]*\.hip"', src)
         assert src.index("#pragma clang fp contract(off) reassociate(off)") < src.index('#include "ctc_beam_cand.hpp"')
-    assert '#include "ctc_beam_lm.h"' in fused and "ts_ctc_beam_lm" not in beam
+    assert '#include "thunder_speech_amd/ctc_beam_lm.h"' in fused and "ts_ctc_beam_lm" not in beam
     assert "atomic" not in re.sub(r"//[^\n]*", "", fused)                     # equal arguments give equal bits
 
 

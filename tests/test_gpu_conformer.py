@@ -1,4 +1,4 @@
-"""GPU parity of the wav2vec2-conformer path (csrc/conformer.hip through include/thunder_speech_amd_conformer.h, then the whole encoder through
+"""GPU parity of the wav2vec2-conformer path (csrc/conformer.hip through include/thunder_speech_amd/conformer.h, then the whole encoder through
 the loader) against float64 restatements of the kernels and against transformers' own Wav2Vec2Conformer modules in f32 on the CPU."""
 import json
 import os

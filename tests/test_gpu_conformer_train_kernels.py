@@ -1,4 +1,4 @@
-"""The launches of wav2vec2-conformer fine-tuning (csrc/conformer_train.hip through thunder_speech_amd/abi/conformer_train.h) on the raw C ABI against
+"""The launches of wav2vec2-conformer fine-tuning (csrc/conformer_train.hip through include/thunder_speech_amd/conformer_train.h) on the raw C ABI against
 float64 on the CPU: torch autograd in float64 through GLU -> depthwise conv -> BatchNorm -> activation for the convolution module, the written
 formulas for the rotary transpose and the feed-forward activation pair.  Every output starts as NaN, every workspace as 0xFF bytes, every return
 code is asserted, every launch runs twice and must give the same bits.

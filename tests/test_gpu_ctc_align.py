@@ -1,4 +1,4 @@
-"""ts_ctc_align and ts_ctc_greedy_spans (csrc/ctc_align.hip, thunder_speech_amd/abi/ctc_align.h) against float64 on the CPU, through the raw
+"""ts_ctc_align and ts_ctc_greedy_spans (csrc/ctc_align.hip, include/thunder_speech_amd/ctc_align.h) against float64 on the CPU, through the raw
 ABI, and BaseCTCModule.align / predict_spans through two model families.
 
 The reference is `_viterbi64` below: the Viterbi recursion over the blank-extended target on log_softmax in float64, a Python loop over the frames

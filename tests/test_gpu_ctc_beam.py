@@ -1,4 +1,4 @@
-"""CTC prefix beam search on the GPU (thunder_speech_amd/abi/ctc_beam.h, csrc/ctc_beam.hip) through the raw C ABI and through two model families.
+"""CTC prefix beam search on the GPU (include/thunder_speech_amd/ctc_beam.h, csrc/ctc_beam.hip) through the raw C ABI and through two model families.
 
 The reference is `_search` below: the header's algorithm restated with prefixes as tuples (no hashes, no trie, no pruning of candidates) over an
 arithmetic chosen by the caller -- float64 in the LOG domain (`_Log`) for the comparisons, `fractions.Fraction` (`_Exact`) for the tie rule.

@@ -1,4 +1,4 @@
-"""CTC prefix beam search with n-gram shallow fusion on the GPU (thunder_speech_amd/capi/ctc_beam_lm.h, csrc/ctc_beam_lm.hip) through the raw C
+"""CTC prefix beam search with n-gram shallow fusion on the GPU (include/thunder_speech_amd/ctc_beam_lm.h, csrc/ctc_beam_lm.hip) through the raw C
 ABI and through the module.
 
 The reference is `_search_lm` below: the header's algorithm restated in float64 in the LOG domain, in the style of `_search` of

@@ -1,4 +1,4 @@
-"""GPU checks of the LoRA launches (csrc/lora_train.hip through thunder_speech_amd/lora/lora_train.h, raw C ABI): the forward into the middle slice
+"""GPU checks of the LoRA launches (csrc/lora_train.hip through include/thunder_speech_amd/lora_train.h, raw C ABI): the forward into the middle slice
 of a [rows][3 n] buffer and the backward against a float64 restatement that reads the same bf16 operands and rounds u and g to bf16 where the kernels
 do, so what remains is accumulation order.  Bounds: those of tests/test_gpu_mms_adapter_train.py for bf16 operands (the same operand widths and the
 same kind of sums over rows), scaled by the reference's max magnitude as there."""

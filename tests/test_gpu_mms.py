@@ -1,4 +1,4 @@
-"""GPU parity of the MMS path (csrc/mms.hip and the head_dim 80 kernel of csrc/w2v_attn.hip through include/thunder_speech_amd_mms.h, then the whole encoder through the loader): the head_dim-80
+"""GPU parity of the MMS path (csrc/mms.hip and the head_dim 80 kernel of csrc/w2v_attn.hip through include/thunder_speech_amd/mms.h, then the whole encoder through the loader): the head_dim-80
 attention core and the attention adapter against float64 restatements, the encoder against transformers' own Wav2Vec2 modules in f32 on the
 CPU, and a two-language checkpoint directory end to end."""
 import copy

@@ -1,4 +1,4 @@
-"""GPU parity of adapter-only MMS fine-tuning (csrc/mms_adapter_train.hip through include/thunder_speech_amd_mms_adapter_train.h, then
+"""GPU parity of adapter-only MMS fine-tuning (csrc/mms_adapter_train.hip through include/thunder_speech_amd/mms_adapter_train.h, then
 huggingface/train.py's AttnAdapter node): the out-of-place forward and the fused backward against float64 autograd, the whole model against
 transformers' autograd with the base frozen, and one optimizer step through BaseCTCModule.training_step."""
 import math

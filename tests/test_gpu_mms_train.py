@@ -1,4 +1,4 @@
-"""GPU parity of head_dim 80 fine-tuning (csrc/mms_train.hip and the head_dim 80 kernels of csrc/w2v_attn_train.hip through include/thunder_speech_amd_mms_train.h, then huggingface/train.py's
+"""GPU parity of head_dim 80 fine-tuning (csrc/mms_train.hip and the head_dim 80 kernels of csrc/w2v_attn_train.hip through include/thunder_speech_amd/mms_train.h, then huggingface/train.py's
 AttentionFused80): the fused training attention against float64 (forward, row statistic, and float64 autograd for dq / dk / dv under the oracle's
 Philox keep mask), against the materialised f32 `Attention` node, and a whole head_dim 80 Wav2Vec2Model against transformers' autograd on the CPU.
 

@@ -1,4 +1,4 @@
-"""GPU parity of the SEW path: the two launches of csrc/sew.hip (through thunder_speech_amd/abi/sew.h) against float64 on the CPU, element by
+"""GPU parity of the SEW path: the two launches of csrc/sew.hip (through include/thunder_speech_amd/sew.h) against float64 on the CPU, element by
 element, then the whole encoder against transformers' own SEWModel in f32 on the CPU, bare and through the loader.  Every output starts as NaN,
 every workspace as 0xFF bytes, every return code is asserted.  Bounds of the kernel tests:
   precision 0, and precision 1 at a width without a matrix-core kernel (f32 operands)    1e-5 x max |reference| (the f32 row kernels' figure)

@@ -1,4 +1,4 @@
-"""GPU parity of the three launches of csrc/sew_train.hip (through thunder_speech_amd/abi/train/sew_train.h) against float64 on the CPU, element by
+"""GPU parity of the three launches of csrc/sew_train.hip (through include/thunder_speech_amd/sew_train.h) against float64 on the CPU, element by
 element: the training forward of SEW's squeeze (y bit-equal to the inference call's, z the conv result), its data gradient and its weight gradient.
 Every output starts as NaN, every workspace as 0xFF bytes, every return code is asserted.  The references read what the kernels read: bf16-rounded
 conv operands (x, dz, w) and the f32 pool operand; the bound is the matrix-core bound of tests/test_gpu_sew.py, max 0.03 and rms 0.006 of

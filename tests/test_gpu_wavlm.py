@@ -1,4 +1,4 @@
-"""GPU parity of the WavLM path (csrc/wavlm.hip through include/thunder_speech_amd_wavlm.h, then the whole encoder through the loader) against
+"""GPU parity of the WavLM path (csrc/wavlm.hip through include/thunder_speech_amd/wavlm.h, then the whole encoder through the loader) against
 transformers' own WavLM modules in f32 on the CPU and against a float64 restatement of the gated relative-position attention."""
 import json
 import os

@@ -1,4 +1,4 @@
-"""GPU parity of WavLM FINE-TUNING in mixed precision (csrc/wavlm_train.hip through include/thunder_speech_amd_wavlm_train.h, then the training path
+"""GPU parity of WavLM FINE-TUNING in mixed precision (csrc/wavlm_train.hip through include/thunder_speech_amd/wavlm_train.h, then the training path
 of huggingface/train.py): the kernels against a float64 restatement of transformers' WavLMAttention, the gate and the embedding gradient against
 float64 autograd of transformers' own modules, and whole encoders against transformers' f32 autograd on the CPU."""
 import json

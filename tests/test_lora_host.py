@@ -1,53 +1,18 @@
-"""LoRA fine-tuning of the attention projections on the CPU: the fourteenth companion header (thunder_speech_amd/lora/lora_train.h) next to the
-unchanged other headers, its binding in _lib, the symbols of the built library, and the regime -- what HuggingFaceEncoderAdapt.lora_finetuning()
-sets up, merge_lora(), the LoRA-only state dict, and which configurations are refused by name."""
-import ctypes
+"""LoRA fine-tuning of the attention projections on the CPU (the companion C header: tests/test_abi_headers_host.py): that the entry points fail
+loudly without a library, and the regime -- what HuggingFaceEncoderAdapt.lora_finetuning() sets up, merge_lora(), the LoRA-only state dict, and
+which configurations are refused by name."""
 import math
-import os
-import re
-import subprocess
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "thunder_speech_amd", "lora", "lora_train.h")
 NAMES = sorted(["ts_lora_abi_version", "ts_lora_fwd", "ts_lora_bwd_workspace", "ts_lora_bwd"])
 # a tiny wav2vec2: hidden 128, 2 layers, 2 heads
 CFG = dict(hidden_size=128, num_hidden_layers=2, num_attention_heads=2, intermediate_size=256, vocab_size=32, conv_dim=(32, 32, 32),
            conv_kernel=(10, 3, 2), conv_stride=(5, 2, 2), num_conv_pos_embeddings=16, num_conv_pos_embedding_groups=2, pad_token_id=0)
 
 
-def _declared(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ts_[a-z0-9_]+)\s*\(", src)))
-
-
-# ---- header and ABI ----------------------------------------------------------------------------------------------------------------------------
-def test_companion_header_parses_and_declares_exactly_the_four_names():
-    from thunder_speech_amd import _lib
-    assert _lib.LORA_HEADER == HEADER
-    sigs, structs, defines = _lib.read_header(open(HEADER).read())
-    assert defines["TS_LORA_ABI_VERSION"] == 1 and _lib.LORA_ABI_VERSION == 1 and not structs
-    assert sorted(sigs) == _declared(HEADER) == NAMES
-    assert _lib.LORA_SIGNATURES == sigs
-    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-    assert sigs["ts_lora_abi_version"] == (ctypes.c_int, [])
-    assert sigs["ts_lora_fwd"] == (ctypes.c_int, [vp, i64, i32, vp, vp, i32, i32, f32, vp, i64, vp, vp])
-    assert sigs["ts_lora_bwd_workspace"] == (i64, [i64, i32, i32, i32])
-    assert sigs["ts_lora_bwd"] == (ctypes.c_int, [vp, i64, vp, vp, i64, i32, i32, i32, f32] + [vp] * 7)
-    for table in (_lib.SIGNATURES, _lib.MMS_ADAPTER_TRAIN_SIGNATURES, _lib.SEW_TRAIN_SIGNATURES, _lib.CTC_BEAM_LM_SIGNATURES):
-        assert not set(table) & set(NAMES)
-
-
-def test_built_library_defines_the_four_symbols():
-    from thunder_speech_amd import build as b
-    path = b.build(verbose=False)
-    nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    defined = {line.split()[-1] for line in nm.splitlines() if line.strip()}
-    assert set(NAMES) <= defined
-
-
+# ---- no library, no entry points ----------------------------------------------------------------------------------------------------------------
 def test_without_a_library_the_entry_points_fail_loudly(monkeypatch, tmp_path):
     """The same path as every other entry point: lib() raises by name when the shared library is missing (no CPU fallback), and a library
     without the four symbols is refused at load."""
@@ -57,7 +22,7 @@ def test_without_a_library_the_entry_points_fail_loudly(monkeypatch, tmp_path):
     for name in NAMES:
         with pytest.raises(RuntimeError, match="is missing"):
             getattr(_lib.lib(), name)
-    assert set(NAMES) <= set(_lib.LORA_SIGNATURES)
+    assert set(NAMES) <= set(_lib.COMPANIONS["lora_train"].signatures)
 
 
 # ---- the regime --------------------------------------------------------------------------------------------------------------------------------

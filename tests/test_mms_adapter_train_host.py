@@ -1,65 +1,12 @@
-"""Adapter-only fine-tuning of MMS checkpoints on the CPU: the sixth companion header (include/thunder_speech_amd_mms_adapter_train.h) next to the
-unchanged other headers, its binding in _lib, the symbols of the built library, and the regime -- which models train mode refuses by name and
-what HuggingFaceEncoderAdapt.adapter_finetuning() sets up."""
-import ctypes
-import glob
-import os
-import re
-import subprocess
-
+"""Adapter-only fine-tuning of MMS checkpoints on the CPU (the companion C header: tests/test_abi_headers_host.py): the regime -- which models
+train mode refuses by name and what HuggingFaceEncoderAdapt.adapter_finetuning() sets up."""
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "thunder_speech_amd_mms_adapter_train.h")
-NAMES = sorted(["ts_mms_adapter_train_abi_version", "ts_mms_attn_adapter_train_fwd", "ts_mms_attn_adapter_train_bwd_workspace",
-                "ts_mms_attn_adapter_train_bwd"])
 # tests/test_mms_host.py's model: hidden 160, 2 heads (head_dim 80), adapter 16
 CFG = dict(hidden_size=160, num_hidden_layers=2, num_attention_heads=2, intermediate_size=320, feat_extract_norm="layer", conv_bias=True,
            do_stable_layer_norm=True, vocab_size=32, conv_dim=(32,) * 7, conv_kernel=(10, 3, 3, 3, 3, 2, 2),
            conv_stride=(5, 2, 2, 2, 2, 2, 2), num_conv_pos_embeddings=16, num_conv_pos_embedding_groups=4, pad_token_id=0, adapter_attn_dim=16)
-
-
-def _declared(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ts_[a-z0-9_]+)\s*\(", src)))
-
-
-# ---- header and ABI ----------------------------------------------------------------------------------------------------------------------------
-def test_companion_header_parses_and_declares_exactly_the_four_names():
-    from thunder_speech_amd import _lib
-    assert _lib.MMS_ADAPTER_TRAIN_HEADER == HEADER
-    sigs, structs, defines = _lib.read_header(open(HEADER).read())
-    assert defines["TS_MMS_ADAPTER_TRAIN_ABI_VERSION"] == 1 and _lib.MMS_ADAPTER_TRAIN_ABI_VERSION == 1 and not structs
-    assert sorted(sigs) == _declared(HEADER) == NAMES
-    assert _lib.MMS_ADAPTER_TRAIN_SIGNATURES == sigs
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    assert sigs["ts_mms_adapter_train_abi_version"] == (ctypes.c_int, [])
-    assert sigs["ts_mms_attn_adapter_train_fwd"] == (ctypes.c_int, [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp])
-    assert sigs["ts_mms_attn_adapter_train_bwd_workspace"] == (i64, [i64, i32, i32])
-    assert sigs["ts_mms_attn_adapter_train_bwd"] == (ctypes.c_int, [vp, vp, i64, i32, i32] + [vp] * 13 + [i32, vp])
-
-
-def test_no_name_is_declared_twice_and_the_older_headers_are_at_their_versions():
-    from thunder_speech_amd import _lib
-    headers = sorted(glob.glob(os.path.join(ROOT, "include", "*.h")))
-    assert len(headers) == 7
-    names = [n for h in headers for n in _declared(h)]
-    assert len(names) == len(set(names))
-    assert len(_declared(os.path.join(ROOT, "include", "thunder_speech_amd.h"))) == 123 and _lib.ABI_VERSION == 15
-    assert (_lib.WAVLM_ABI_VERSION, _lib.WAVLM_TRAIN_ABI_VERSION, _lib.CONFORMER_ABI_VERSION, _lib.MMS_ABI_VERSION,
-            _lib.MMS_TRAIN_ABI_VERSION) == (1, 1, 1, 1, 1)
-    for table in (_lib.SIGNATURES, _lib.WAVLM_SIGNATURES, _lib.WAVLM_TRAIN_SIGNATURES, _lib.CONFORMER_SIGNATURES, _lib.MMS_SIGNATURES,
-                  _lib.MMS_TRAIN_SIGNATURES):
-        assert not set(table) & set(NAMES)
-
-
-def test_built_library_defines_the_four_symbols():
-    from thunder_speech_amd import build as b
-    path = b.build(verbose=False)
-    nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    defined = {line.split()[-1] for line in nm.splitlines() if line.strip()}
-    assert set(NAMES) <= defined
 
 
 # ---- the regime --------------------------------------------------------------------------------------------------------------------------------

@@ -1,17 +1,12 @@
-"""MMS on the CPU: the companion C header (include/thunder_speech_amd_mms.h) next to the unchanged core ABI, which adapter configurations are
-accepted or refused (by name), the refusal of fine-tuning, and load_huggingface_checkpoint(dir, target_lang=...) on a two-language directory."""
-import ctypes
+"""MMS on the CPU (the companion C header: tests/test_abi_headers_host.py): which adapter configurations are accepted or refused (by name),
+the refusal of fine-tuning, and load_huggingface_checkpoint(dir, target_lang=...) on a two-language directory."""
 import json
 import os
-import re
-import subprocess
 
 import pytest
 import torch
 
 transformers = pytest.importorskip("transformers")
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 BASE = ["<pad>", "<s>", "</s>", "<unk>", "|"]
 VOCABS = {"aaa": BASE + list("abcdefghijklmnopqrstuvwxyz'"), "bbb": BASE + list("zyxwvutsrq")}
@@ -22,42 +17,6 @@ CFG = dict(hidden_size=160, num_hidden_layers=2, num_attention_heads=2, intermed
 
 def _model(**kw):
     return transformers.Wav2Vec2Model(transformers.Wav2Vec2Config(**{**CFG, **kw}))
-
-
-# ---- the companion header ----------------------------------------------------------------------------------------------------------------
-def _declared(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ts_[a-z0-9_]+)\s*\(", src)))
-
-
-def test_companion_header_parses_and_no_name_is_declared_twice():
-    from thunder_speech_amd import _lib
-    path = os.path.join(ROOT, "include", "thunder_speech_amd_mms.h")
-    assert _lib.MMS_HEADER == path
-    sigs, structs, defines = _lib.read_header(open(path).read())
-    assert defines["TS_MMS_ABI_VERSION"] == 1 and _lib.MMS_ABI_VERSION == 1 and not structs
-    mms = _declared(path)
-    assert sorted(sigs) == mms == sorted(_lib.MMS_SIGNATURES)
-    assert mms == sorted(["ts_mms_abi_version", "ts_mms_attention_fwd", "ts_mms_attn_adapter_fwd"])
-    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-    assert sigs["ts_mms_abi_version"] == (ctypes.c_int, [])
-    assert sigs["ts_mms_attention_fwd"] == (ctypes.c_int, [vp, i32, i32, i32, i32, vp, vp, vp])
-    assert sigs["ts_mms_attn_adapter_fwd"] == (ctypes.c_int, [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp])
-    core = _declared(os.path.join(ROOT, "include", "thunder_speech_amd.h"))
-    assert len(core) == 123 and _lib.ABI_VERSION == 15
-    others = [_declared(os.path.join(ROOT, "include", h)) for h in ("thunder_speech_amd_wavlm.h", "thunder_speech_amd_wavlm_train.h",
-                                                                    "thunder_speech_amd_conformer.h")]
-    names = [n for h in [core, mms] + others for n in h]
-    assert len(names) == len(set(names))
-    assert not set(_lib.MMS_SIGNATURES) & set(_lib.EXPORTED_SYMBOLS)
-
-
-def test_built_library_defines_the_companion_symbols():
-    from thunder_speech_amd import _lib, build as b
-    path = b.build(verbose=False)
-    nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    defined = {line.split()[-1] for line in nm.splitlines() if line.strip()}
-    assert set(_lib.MMS_SIGNATURES) <= defined
 
 
 # ---- configurations ------------------------------------------------------------------------------------------------------------------------

@@ -1,62 +1,7 @@
-"""Head_dim 80 fine-tuning on the CPU: the companion C header include/thunder_speech_amd_mms_train.h next to the unchanged other headers, its
-binding in _lib, the symbols of the built library, which geometries the two fused attention nodes take, and that a head_dim 80 model in mixed
-precision is no longer refused before the GPU check."""
-import ctypes
-import glob
-import os
-import re
-import subprocess
-
+"""Head_dim 80 fine-tuning on the CPU (the companion C header: tests/test_abi_headers_host.py): which geometries the two fused attention
+nodes take, and that a head_dim 80 model in mixed precision is no longer refused before the GPU check."""
 import pytest
 import torch
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "thunder_speech_amd_mms_train.h")
-NAMES = sorted(["ts_mms_train_abi_version", "ts_mms_attention_train_fwd_workspace", "ts_mms_attention_train_fwd",
-                "ts_mms_attention_train_bwd_workspace", "ts_mms_attention_train_bwd"])
-
-
-def _declared(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ts_[a-z0-9_]+)\s*\(", src)))
-
-
-def test_companion_header_parses_and_is_version_1():
-    from thunder_speech_amd import _lib
-    assert _lib.MMS_TRAIN_HEADER == HEADER
-    sigs, structs, defines = _lib.read_header(open(HEADER).read())
-    assert defines["TS_MMS_TRAIN_ABI_VERSION"] == 1 and _lib.MMS_TRAIN_ABI_VERSION == 1 and not structs
-    assert sorted(sigs) == _declared(HEADER) == NAMES
-
-
-def test_its_five_names_are_declared_nowhere_else():
-    from thunder_speech_amd import _lib
-    others = [h for h in glob.glob(os.path.join(ROOT, "include", "*.h")) if h != HEADER]
-    assert len(others) >= 5
-    for h in others:
-        assert not set(_declared(h)) & set(NAMES), h
-    for table in (_lib.SIGNATURES, _lib.WAVLM_SIGNATURES, _lib.WAVLM_TRAIN_SIGNATURES, _lib.CONFORMER_SIGNATURES, _lib.MMS_SIGNATURES):
-        assert not set(table) & set(NAMES)
-
-
-def test_lib_signatures_match_the_header_exactly():
-    from thunder_speech_amd import _lib
-    sigs, _, _ = _lib.read_header(open(HEADER).read())
-    assert _lib.MMS_TRAIN_SIGNATURES == sigs and sorted(_lib.MMS_TRAIN_SIGNATURES) == NAMES
-    vp, i32, i64, u64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
-    assert sigs["ts_mms_train_abi_version"] == (ctypes.c_int, [])
-    assert sigs["ts_mms_attention_train_fwd_workspace"] == (i64, [i32, i32, i32, i32])
-    assert sigs["ts_mms_attention_train_bwd_workspace"] == (i64, [i32, i32, i32, i32])
-    assert sigs["ts_mms_attention_train_fwd"] == (ctypes.c_int, [vp, i32, i32, i32, i32, vp, f32, u64, vp, vp, vp, vp])
-    assert sigs["ts_mms_attention_train_bwd"] == (ctypes.c_int, [vp, i32, i32, i32, i32, vp, f32, u64, vp, vp, vp, vp, vp, vp, vp])
-
-
-def test_built_library_defines_the_five_symbols():
-    from thunder_speech_amd import _lib, build as b
-    path = b.build(verbose=False)
-    nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    defined = {line.split()[-1] for line in nm.splitlines() if line.strip()}
-    assert set(NAMES) <= defined and set(_lib.MMS_TRAIN_SIGNATURES) <= defined
 
 
 def test_which_geometries_the_fused_nodes_take():

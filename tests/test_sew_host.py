@@ -1,19 +1,11 @@
 """SEW on the CPU: which configurations are accepted or refused (each refusal by name, sew-d included), the refusal of fine-tuning, the pooled key
-lengths against max_pool1d of transformers' mask, the tap packing, the companion C header inside the package (thunder_speech_amd/abi/sew.h) next to
-the unchanged core ABI, and the argument checks of the two launchers (made-up pointers: none of these calls reaches a launch)."""
-import ctypes
-import os
-import re
-import subprocess
-
+lengths against max_pool1d of transformers' mask, the tap packing, and the argument checks of the two launchers (made-up pointers: none of
+these calls reaches a launch).  (The companion C header: tests/test_abi_headers_host.py.)"""
 import pytest
 import torch
 
 transformers = pytest.importorskip("transformers")
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "thunder_speech_amd", "abi", "sew.h")
-NAMES = sorted(["ts_sew_abi_version", "ts_sew_squeeze_workspace_bytes", "ts_sew_squeeze_fwd", "ts_sew_unsqueeze_rows"])
 CFG = dict(hidden_size=128, num_hidden_layers=2, num_attention_heads=2, intermediate_size=256, vocab_size=32, conv_dim=(32, 32, 32, 32, 64),
            conv_kernel=(10, 3, 1, 3, 1), conv_stride=(5, 2, 1, 2, 1), num_conv_pos_embeddings=16, num_conv_pos_embedding_groups=4, squeeze_factor=2)
 
@@ -136,59 +128,6 @@ def test_tap_packing_pads_24_channel_groups_with_zeros():
     assert packed.shape == (5, 2, 32, 32) and packed.dtype == torch.bfloat16 and packed.is_contiguous()
     assert torch.equal(packed[:, :, :24, :24], f32.to(torch.bfloat16))
     assert not bool(packed[:, :, 24:, :].any()) and not bool(packed[:, :, :, 24:].any())
-
-
-# ---- header and ABI ----------------------------------------------------------------------------------------------------------------------------
-def _declared(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ts_[a-z0-9_]+)\s*\(", src)))
-
-
-def test_companion_header_parses_and_declares_exactly_the_four_names():
-    from thunder_speech_amd import _lib
-    assert _lib.SEW_HEADER == HEADER
-    sigs, structs, defines = _lib.read_header(open(HEADER).read())
-    assert defines["TS_SEW_ABI_VERSION"] == 1 and _lib.SEW_ABI_VERSION == 1 and not structs
-    assert sorted(sigs) == _declared(HEADER) == NAMES
-    assert _lib.SEW_SIGNATURES == sigs
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    assert sigs["ts_sew_abi_version"] == (ctypes.c_int, [])
-    assert sigs["ts_sew_squeeze_workspace_bytes"] == (i64, [i32, i32, i32, i32, i32, i32])
-    assert sigs["ts_sew_squeeze_fwd"] == (ctypes.c_int, [vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp])
-    assert sigs["ts_sew_unsqueeze_rows"] == (ctypes.c_int, [vp, i32, i32, i32, i32, i32, vp, vp])
-
-
-def test_no_other_table_holds_the_names_and_the_core_abi_is_unchanged():
-    from thunder_speech_amd import _lib
-    for table in (_lib.SIGNATURES, _lib.WAVLM_SIGNATURES, _lib.WAVLM_TRAIN_SIGNATURES, _lib.CONFORMER_SIGNATURES, _lib.MMS_SIGNATURES,
-                  _lib.MMS_TRAIN_SIGNATURES, _lib.MMS_ADAPTER_TRAIN_SIGNATURES, _lib.POSCONV_STACK_TRAIN_SIGNATURES):
-        assert not set(table) & set(NAMES)
-    assert len(_declared(os.path.join(ROOT, "include", "thunder_speech_amd.h"))) == 123 and _lib.ABI_VERSION == 15
-
-
-def test_built_library_defines_the_four_symbols():
-    from thunder_speech_amd import build as b
-    path = b.build(verbose=False)
-    nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    defined = {line.split()[-1] for line in nm.splitlines() if line.strip()}
-    assert set(NAMES) <= defined
-
-
-def test_editing_the_header_makes_the_library_stale(tmp_path, monkeypatch):
-    """build.needs_build() looks at thunder_speech_amd/abi/*.h too: a header newer than the library asks for a rebuild."""
-    import glob
-    from thunder_speech_amd import build as b
-    lib = tmp_path / "lib.so"
-    lib.write_bytes(b"")
-    monkeypatch.setattr(b, "lib_path", lambda: str(lib))
-    real = glob.glob
-    monkeypatch.setattr(b, "sources", lambda: [])
-    monkeypatch.setattr(b.glob, "glob", lambda pat, **kw: real(pat, **kw) if os.path.dirname(pat) == os.path.dirname(HEADER) else [])
-    mtime = os.path.getmtime(HEADER)
-    os.utime(lib, (mtime + 10, mtime + 10))
-    assert not b.needs_build()
-    os.utime(lib, (mtime - 10, mtime - 10))
-    assert b.needs_build()
 
 
 # ---- argument checks ---------------------------------------------------------------------------------------------------------------------------

@@ -1,23 +1,12 @@
-"""SEW fine-tuning on the CPU: the companion C header inside the package (thunder_speech_amd/abi/train/sew_train.h) next to the unchanged abi/sew.h, the
+"""SEW fine-tuning on the CPU (the companion C header: tests/test_abi_headers_host.py): the
 argument checks of its launchers (made-up pointers: none of these calls reaches a launch), the Python mirror of the support matrix against the
 launchers' own geometry check, the refusals by name of huggingface/sew_train.py (CPU tensors reach them), and the data gradient's tap packing against
 a float64 loop."""
-import ctypes
-import glob
-import os
-import re
-
 import pytest
 import torch
 
 transformers = pytest.importorskip("transformers")
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "thunder_speech_amd", "abi", "train", "sew_train.h")
-SEW_HEADER = os.path.join(ROOT, "thunder_speech_amd", "abi", "sew.h")
-NAMES = sorted(["ts_sew_train_abi_version", "ts_sew_squeeze_train_supported", "ts_sew_squeeze_train_fwd", "ts_sew_squeeze_dgrad_workspace_bytes",
-                "ts_sew_squeeze_dgrad", "ts_sew_squeeze_wgrad_workspace_bytes", "ts_sew_squeeze_wgrad"])
-SEW_NAMES = sorted(["ts_sew_abi_version", "ts_sew_squeeze_workspace_bytes", "ts_sew_squeeze_fwd", "ts_sew_unsqueeze_rows"])
 CFG = dict(hidden_size=128, num_hidden_layers=2, num_attention_heads=2, intermediate_size=256, vocab_size=32, conv_dim=(32, 32, 64),
            conv_kernel=(10, 3, 2), conv_stride=(5, 2, 2), num_conv_pos_embeddings=16, num_conv_pos_embedding_groups=4, squeeze_factor=2)
 
@@ -26,40 +15,6 @@ def _adapter(train_precision="bf16", **kw):
     from thunder_speech_amd.huggingface.encoder import HuggingFaceEncoderAdapt
     enc = HuggingFaceEncoderAdapt(transformers.SEWModel(transformers.SEWConfig(**{**CFG, **kw})), train_precision=train_precision)
     return enc.train()
-
-
-def _declared(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ts_[a-z0-9_]+)\s*\(", src)))
-
-
-# ---- header and ABI ----------------------------------------------------------------------------------------------------------------------------
-def test_companion_header_parses_and_declares_exactly_the_new_names():
-    from thunder_speech_amd import _lib
-    assert _lib.SEW_TRAIN_HEADER == HEADER
-    sigs, structs, defines = _lib.read_header(open(HEADER).read())
-    assert defines["TS_SEW_TRAIN_ABI_VERSION"] == _lib.SEW_TRAIN_ABI_VERSION == _lib.lib().ts_sew_train_abi_version() and not structs
-    assert sorted(sigs) == _declared(HEADER) == NAMES
-    assert _lib.SEW_TRAIN_SIGNATURES == sigs
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    assert sigs["ts_sew_squeeze_train_supported"] == (ctypes.c_int, [i32] * 6)
-    assert sigs["ts_sew_squeeze_train_fwd"] == (ctypes.c_int, [vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp])
-    assert sigs["ts_sew_squeeze_dgrad"] == (ctypes.c_int, [vp, vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp])
-    assert sigs["ts_sew_squeeze_wgrad"] == (ctypes.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp])
-    assert sigs["ts_sew_squeeze_dgrad_workspace_bytes"] == sigs["ts_sew_squeeze_wgrad_workspace_bytes"] == (i64, [i32] * 5)
-
-
-def test_sew_h_keeps_its_four_names_and_no_other_header_mentions_the_new_ones():
-    from thunder_speech_amd import _lib
-    assert _declared(SEW_HEADER) == SEW_NAMES and _lib.SEW_ABI_VERSION == 1
-    headers = glob.glob(os.path.join(ROOT, "include", "**", "*.h"), recursive=True) + glob.glob(os.path.join(ROOT, "thunder_speech_amd", "abi", "**", "*.h"), recursive=True)
-    assert HEADER in headers and SEW_HEADER in headers and len(headers) == 13                       # the core header and twelve companions
-    for path in headers:
-        if path != HEADER:
-            assert not set(_declared(path)) & set(NAMES), path
-    for name in dir(_lib):
-        if name.endswith("SIGNATURES") and name != "SEW_TRAIN_SIGNATURES":
-            assert not set(getattr(_lib, name)) & set(NAMES), name
 
 
 # ---- argument checks ---------------------------------------------------------------------------------------------------------------------------

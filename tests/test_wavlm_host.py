@@ -1,16 +1,9 @@
 """WavLM on the CPU: the host bucket table of the gated relative-position bias against transformers, which configurations are accepted or
-refused, the refusal of fine-tuning, and the companion C header (include/thunder_speech_amd_wavlm.h) next to the unchanged core ABI."""
-import ctypes
-import os
-import re
-import subprocess
-
+refused, and the refusal of fine-tuning.  (The companion C header: tests/test_abi_headers_host.py.)"""
 import pytest
 import torch
 
 transformers = pytest.importorskip("transformers")
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 CFG = dict(hidden_size=128, num_hidden_layers=2, num_attention_heads=2, intermediate_size=256, vocab_size=32, conv_dim=(32,) * 7,
            conv_kernel=(10, 3, 3, 3, 3, 2, 2), conv_stride=(5, 2, 2, 2, 2, 2, 2), num_conv_pos_embeddings=16, num_conv_pos_embedding_groups=4)
@@ -58,24 +51,3 @@ def test_wavlm_training_mode_is_refused_by_name_before_any_device_work():
     enc.eval()
     with pytest.raises(RuntimeError):                              # eval mode reaches the GPU check (no CPU path)
         enc(torch.zeros(1, 4000), torch.tensor([4000]))
-
-
-def _declared(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ts_[a-z0-9_]+)\s*\(", src)))
-
-
-def test_companion_header_is_bound_and_exported_and_the_core_abi_is_unchanged():
-    from thunder_speech_amd import _lib, build as b
-    wavlm = _declared(os.path.join(ROOT, "include", "thunder_speech_amd_wavlm.h"))
-    assert wavlm == sorted(["ts_wavlm_abi_version", "ts_wavlm_rel_bias", "ts_wavlm_attention_workspace_bytes", "ts_wavlm_attention_fwd"])
-    assert sorted(_lib.WAVLM_SIGNATURES) == wavlm and _lib.WAVLM_ABI_VERSION == 1
-    core = _declared(os.path.join(ROOT, "include", "thunder_speech_amd.h"))
-    assert sorted(_lib.SIGNATURES) == core and _lib.EXPORTED_SYMBOLS == list(_lib.SIGNATURES) and len(core) == 123
-    assert not set(wavlm) & set(core)
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    assert _lib.WAVLM_SIGNATURES["ts_wavlm_attention_fwd"][1] == [vp, i32, i32, i32, i32, vp, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp]
-    path = b.build(verbose=False)
-    nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    defined = {line.split()[-1] for line in nm.splitlines() if line.strip()}
-    assert not [s for s in wavlm if s not in defined]

@@ -30,13 +30,21 @@ def sources():
     return sorted(glob.glob(os.path.join(PKG, "csrc", "*.hip")))
 
 
+def header_deps():
+    """Every header of the C ABI: the core header in include/ and its companions in include/thunder_speech_amd/."""
+    return glob.glob(os.path.join(ROOT, "include", "*.h")) + glob.glob(os.path.join(ROOT, "include", "thunder_speech_amd", "*.h"))
+
+
+def common_flags():
+    """What the product build and the sanitizer build share: language, include path, target name."""
+    return ["-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc"), f'-DTS_BUILD_TARGET="{ARCH}"']
+
+
 def needs_build() -> bool:
     out = lib_path()
     if not os.path.exists(out):
         return True
-    deps = sources() + glob.glob(os.path.join(PKG, "csrc", "*.hpp")) + glob.glob(os.path.join(ROOT, "include", "*.h")) + \
-        glob.glob(os.path.join(ROOT, "include", "thunder_speech_amd", "*.h")) + glob.glob(os.path.join(PKG, "abi", "*.h")) + \
-        glob.glob(os.path.join(PKG, "abi", "train", "*.h")) + glob.glob(os.path.join(PKG, "capi", "*.h")) + glob.glob(os.path.join(PKG, "lora", "*.h"))
+    deps = sources() + glob.glob(os.path.join(PKG, "csrc", "*.hpp")) + header_deps()
     return any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps)
 
 
@@ -66,9 +74,7 @@ def build(force: bool = False, verbose: bool = True, only=None) -> str:
         objs.append(obj)
         if not own and os.path.exists(obj):
             continue
-        cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffast-math", "-fno-finite-math-only",
-               "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc"), "-I" + os.path.join(PKG, "abi"),
-               "-I" + os.path.join(PKG, "capi"), "-I" + os.path.join(PKG, "lora"), f'-DTS_BUILD_TARGET="{ARCH}"', "-c", src, "-o", obj]
+        cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-ffast-math", "-fno-finite-math-only"] + common_flags() + ["-c", src, "-o", obj]
         cmd[1:1] = os.environ.get("TS_CXXFLAGS", "").split()        # diagnostic builds (tools/variants.py), e.g. TS_CXXFLAGS=-DTS_STAMP
         if verbose:
             print(" ".join(cmd), flush=True)
@@ -98,15 +104,10 @@ def build_asan(verbose: bool = True) -> str:
     for src in sources():
         obj = os.path.join(bdir, os.path.basename(src) + ".o")
         objs.append(obj)
-        if os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(d) for d in [src] + glob.glob(os.path.join(PKG, "csrc", "*.hpp")) +
-                                                                 glob.glob(os.path.join(ROOT, "include", "*.h")) +
-                                                                 glob.glob(os.path.join(ROOT, "include", "thunder_speech_amd", "*.h")) +
-                                                                 glob.glob(os.path.join(PKG, "abi", "*.h")) + glob.glob(os.path.join(PKG, "abi", "train", "*.h")) +
-                                                                 glob.glob(os.path.join(PKG, "capi", "*.h")) + glob.glob(os.path.join(PKG, "lora", "*.h"))):
+        if os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(d) for d in [src] + glob.glob(os.path.join(PKG, "csrc", "*.hpp")) + header_deps()):
             continue
-        cmd = [hipcc, f"--offload-arch={ARCH}", "-O2", "-g", "-std=c++17", "-fPIC", "-fsanitize=address,undefined", "-Wno-option-ignored",
-               "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc"), "-I" + os.path.join(PKG, "abi"),
-               "-I" + os.path.join(PKG, "capi"), "-I" + os.path.join(PKG, "lora"), f'-DTS_BUILD_TARGET="{ARCH}"', "-c", src, "-o", obj]
+        cmd = [hipcc, f"--offload-arch={ARCH}", "-O2", "-g", "-fsanitize=address,undefined", "-Wno-option-ignored", "-fno-omit-frame-pointer",
+               "-fno-sanitize-recover=undefined"] + common_flags() + ["-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         procs.append((src, subprocess.Popen(cmd)))

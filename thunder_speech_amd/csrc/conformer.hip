@@ -1,5 +1,5 @@
 // The conformer block of wav2vec2-conformer with rotary position embeddings (transformers modeling_wav2vec2_conformer.py, reached from
-// huggingface/compatibility.py:31-42 for a wav2vec2-conformer checkpoint).  Declared in include/thunder_speech_amd_conformer.h.
+// huggingface/compatibility.py:31-42 for a wav2vec2-conformer checkpoint).  Declared in include/thunder_speech_amd/conformer.h.
 //
 //   ts_conformer_glu_dwconv_fwd        act(BN(dwconv(GLU(u)))): a tile of GLU'd frames and its (KT - 1)-frame halo staged in LDS as f32,
 //                                      each lane one channel and a run of 32 output frames, taps and weights in registers
@@ -7,7 +7,7 @@
 //   ts_conformer_linear_fwd            the bf16 GEMM of csrc/gemm_nt.hip with its GELU / SiLU epilogue, column slices of a wider output;
 //                                      f32: the f32 GEMM and one epilogue pass
 #include "w2v_rows.hpp"
-#include "thunder_speech_amd_conformer.h"
+#include "thunder_speech_amd/conformer.h"
 
 namespace ts {
 

@@ -1,5 +1,5 @@
 // Fine-tuning of the rotary wav2vec2-conformer (transformers modeling_wav2vec2_conformer.py in train mode): what the wav2vec2 training kernels
-// (csrc/w2v_train.hip, w2v_attn_train.hip, gemm_nt.hip) do not cover.  Declared in thunder_speech_amd/abi/conformer_train.h.
+// (csrc/w2v_train.hip, w2v_attn_train.hip, gemm_nt.hip) do not cover.  Declared in include/thunder_speech_amd/conformer_train.h.
 //
 //   ts_conformer_glu_dwconv_train_fwd   z = dwconv(GLU(u)), unnormalised, + per-workgroup (count, mean, M2) of z per channel (float64): the
 //                                       staging and tap loop of conformer_glu_dwconv_kernel (csrc/conformer.hip)
@@ -13,7 +13,7 @@
 // No atomics; every sum has a fixed order.
 #include "w2v_rows.hpp"
 #include "ts_philox.hpp"
-#include "conformer_train.h"
+#include "thunder_speech_amd/conformer_train.h"
 
 namespace ts {
 

@@ -1,5 +1,5 @@
 // CTC forced alignment (Viterbi over the blank-extended target) and the frame spans of the greedy transcript, for gfx950.
-// No reference counterpart: the reference returns bare strings (module.py:98-101).  ABI: thunder_speech_amd/abi/ctc_align.h.
+// No reference counterpart: the reference returns bare strings (module.py:98-101).  ABI: include/thunder_speech_amd/ctc_align.h.
 //
 // ts_ctc_align keeps the skeleton of csrc/ctc.hip's alpha recursion -- one workgroup per utterance, the L = 2S+1 states spread over the lanes
 // (1, 2 or 4 per thread), two LDS rows with -inf guard cells, the emissions requested a chunk of frames ahead, a barrier per step that orders
@@ -14,7 +14,7 @@
 //     16 frames x 2 words x 2 ballots at once).
 #include "ts_common.hpp"
 
-#include "ctc_align.h"
+#include "thunder_speech_amd/ctc_align.h"
 
 namespace ts {
 

@@ -1,5 +1,5 @@
 // CTC prefix beam search with n-best output, for gfx950.  No reference counterpart: the reference decodes greedily (module.py:98-101).
-// ABI and the specification of the algorithm: thunder_speech_amd/abi/ctc_beam.h.
+// ABI and the specification of the algorithm: include/thunder_speech_amd/ctc_beam.h.
 //
 // Three launches.
 //   1. ctc_beam_cand_kernel, a wave per frame: the f64 normaliser and the token_cap largest non-blank logits.  The classes are spread over the
@@ -30,7 +30,7 @@
 //      order), the other lanes zero the tail.
 #include "ts_common.hpp"
 
-#include "ctc_beam.h"
+#include "thunder_speech_amd/ctc_beam.h"
 
 // the f64 products and sums below are the specification's, one rounding each: no contraction into fma, no reassociation.  (The quotient of
 // beam_prob keeps the build's reciprocal-and-refine form; both kernels form every probability through that one function.)

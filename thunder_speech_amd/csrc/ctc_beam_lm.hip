@@ -1,5 +1,5 @@
 // CTC prefix beam search with n-gram shallow fusion, for gfx950.  No reference counterpart.  ABI and the specification of the algorithm:
-// thunder_speech_amd/capi/ctc_beam_lm.h; the search without an LM, whose structure this one keeps, is csrc/ctc_beam.hip.
+// include/thunder_speech_amd/ctc_beam_lm.h; the search without an LM, whose structure this one keeps, is csrc/ctc_beam.hip.
 //
 // Three launches.
 //   1. ctc_beam_cand_kernel (csrc/ctc_beam_cand.hpp), the pre-pass of csrc/ctc_beam.hip, unchanged.
@@ -19,7 +19,7 @@
 //      the row forward: the frame of each node and the f64 sum of the tokens' log10 LM scores in forward order.
 #include "ts_common.hpp"
 
-#include "ctc_beam_lm.h"
+#include "thunder_speech_amd/ctc_beam_lm.h"
 
 // the f64 products and sums below are the specification's, one rounding each: no contraction into fma, no reassociation
 #pragma clang fp contract(off) reassociate(off)
@@ -48,7 +48,7 @@ struct BeamLmArgs {
   int* lengths;             // [B][n_best]
   float* scores;            // [B][n_best]
   int* counts;              // [B]
-  // the LM (capi/ctc_beam_lm.h)
+  // the LM (thunder_speech_amd/ctc_beam_lm.h)
   const int* arc_begin; const int* arc_class; const int* arc_next; const double* arc_factor; const double* arc_log10;
   const int* bo_next; const double* bo_factor; const double* bo_log10; const double* eos_factor; const double* eos_log10;
   int n_states, n_arcs, start_state, eos;

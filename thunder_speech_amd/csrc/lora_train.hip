@@ -1,4 +1,4 @@
-// The low-rank (LoRA) term of a frozen linear projection as a trainable node (thunder_speech_amd/lora/lora_train.h), mixed precision:
+// The low-rank (LoRA) term of a frozen linear projection as a trainable node (include/thunder_speech_amd/lora_train.h), mixed precision:
 //   ts_lora_fwd   u = x A^T, y += s u B^T into the target's column slice of the node's f32 result                  one launch
 //   ts_lora_bwd   g = s dy B, dx += g A, dA = g^T x, dB = s dy^T u                                                   three launches
 // The base product y = x W^T + b and dx = dy W stay the bf16 GEMM of csrc/gemm_nt.hip; these launches run behind it on the same buffers.
@@ -33,7 +33,7 @@
 // Measured on an MI355X at that shape (profiles/lora_finetune.md, tools/bench_lora.py): forward 12.9 us against 6.4 us for its floor at 8 TB/s;
 // backward 37.3 us against 7.7 us, 28.6 us of it without dx -- the sums over rows are bound by the latency of their 2-byte loads, not by bytes.
 #include "ts_common.hpp"
-#include "lora_train.h"
+#include "thunder_speech_amd/lora_train.h"
 
 namespace ts {
 

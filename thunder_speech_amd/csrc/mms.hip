@@ -1,11 +1,11 @@
-// What MMS (facebook/mms-1b-*) and XLS-R 1B need beyond the wav2vec2 launches (include/thunder_speech_amd_mms.h):
+// What MMS (facebook/mms-1b-*) and XLS-R 1B need beyond the wav2vec2 launches (include/thunder_speech_amd/mms.h):
 //   ts_mms_attention_fwd     the fused attention core at head_dim 80 (hidden 1280, 16 heads): w2v_flash_attn_kernel<80>, launched by attn_flash_launch
 //                            (csrc/w2v_attn.hip; the head_dim 80 geometry and its LDS pitches are AttnGeom<80> of csrc/attn_tile.hpp)
 //   ts_mms_attn_adapter_fwd  h += W2 relu(W1 LN(h) + b1) + b2 in place on the residual stream, with the LayerNorm that follows it: mms_adapter_kernel
 // adapter_launch (declared in mms_adapter_rows.hpp) is that kernel's launcher, also used by ts_mms_attn_adapter_train_fwd (csrc/mms_adapter_train.hip).
 #include "attn_tile.hpp"
 #include "mms_adapter_rows.hpp"
-#include "thunder_speech_amd_mms.h"
+#include "thunder_speech_amd/mms.h"
 
 namespace ts {
 

@@ -1,4 +1,4 @@
-// The MMS attention adapter as a trainable node (include/thunder_speech_amd_mms_adapter_train.h):
+// The MMS attention adapter as a trainable node (include/thunder_speech_amd/mms_adapter_train.h):
 //   ts_mms_attn_adapter_train_fwd   y = h + W2 relu(W1 LN(h) + b1) + b2 out of place: mms_adapter_kernel (csrc/mms.hip) reading h, writing y
 //   ts_mms_attn_adapter_train_bwd   dh and the six parameter gradients from h and dy alone, in three launches:
 //     1. mms_adapter_bwd_rows_kernel   16 rows per workgroup in the forward's tile layout (csrc/mms_adapter_rows.hpp).  It recomputes the row
@@ -22,7 +22,7 @@
 #include <type_traits>
 
 #include "mms_adapter_rows.hpp"
-#include "thunder_speech_amd_mms_adapter_train.h"
+#include "thunder_speech_amd/mms_adapter_train.h"
 
 namespace ts {
 

@@ -1,10 +1,10 @@
 // Fused self-attention for mixed-precision FINE-TUNING at head_dim 80 (XLS-R 1B / MMS: hidden 1280, 16 heads): the entry points of
-// include/thunder_speech_amd_mms_train.h.  The contract is ts_w2v_attention_train_fwd / _bwd's with scale = 1 / sqrt(80), and so is the code: the
+// include/thunder_speech_amd/mms_train.h.  The contract is ts_w2v_attention_train_fwd / _bwd's with scale = 1 / sqrt(80), and so is the code: the
 // head_dim 80 instantiations of attn_fwd_train_kernel / attn_bwd_dq_kernel / attn_bwd_dkv_kernel with attn_rowdot80_kernel, launched by
 // attn_train_fwd_launch / attn_train_bwd_launch (csrc/w2v_attn_train.hip; the geometry is AttnGeom<80> of csrc/attn_tile.hpp).  What is this file's own
 // are the argument checks, which differ from the head_dim 64 entry points' in what they refuse and with which code.
 #include "attn_tile.hpp"
-#include "thunder_speech_amd_mms_train.h"
+#include "thunder_speech_amd/mms_train.h"
 
 using namespace ts;
 
@@ -16,7 +16,7 @@ static int mms_train_check(const void* qkv, int32_t batch, int32_t t, int32_t c,
 
 extern "C" int ts_mms_train_abi_version(void) { return TS_MMS_TRAIN_ABI_VERSION; }
 
-/* see include/thunder_speech_amd_mms_train.h */
+/* see include/thunder_speech_amd/mms_train.h */
 extern "C" int64_t ts_mms_attention_train_fwd_workspace(int32_t batch, int32_t t, int32_t c, int32_t heads) {
   return attn_train_fwd_workspace(batch, t, c, heads);
 }

@@ -1,5 +1,5 @@
 // SEW (transformers' SEWModel, the squeezed wav2vec2): the two launches its encoder needs next to the wav2vec2 ones, time-major fp32 [B][T][C];
-// ABI in thunder_speech_amd/abi/sew.h.
+// ABI in include/thunder_speech_amd/sew.h.
 //   ts_sew_squeeze_fwd      y[r] = mean_{i < s} x[s r + i] + gelu(conv_stride_s(x)[r] + b), T / s output frames: precision 1 with 24 or 32 channels per
 //                           group on sew_squeeze_mfma_kernel; otherwise the f32 GEMM (csrc/gemm_f32.hip, one launch: the taps are its outer
 //                           contraction loop, the stride its row pitch) over a padded f32 copy and sew_squeeze_finish_kernel
@@ -8,7 +8,7 @@
 
 #include "w2v_rows.hpp"
 
-#include "sew.h"
+#include "thunder_speech_amd/sew.h"
 #include "sew_squeeze.hpp"
 
 namespace ts {

@@ -1,5 +1,5 @@
 // SEW fine-tuning in mixed precision: the squeeze (average pool + stride-s weight-normed grouped conv + GELU) of csrc/sew.hip with what its backward
-// needs, time-major fp32 [B][T][C]; ABI in thunder_speech_amd/abi/train/sew_train.h.  s = stride, k = kernel, p = k / 2, T2 = T / s.
+// needs, time-major fp32 [B][T][C]; ABI in include/thunder_speech_amd/sew_train.h.  s = stride, k = kernel, p = k / 2, T2 = T / s.
 //   ts_sew_squeeze_train_fwd   ts_sew_squeeze_fwd(precision = 1) on the same kernel (sew_squeeze_mfma_kernel<true>), which also stores the conv result z
 //   ts_sew_squeeze_dgrad       dx = pool^T(dy) + conv^T(dz): per phase f = (q + p) % s a stride-1 conv of dz, sew_squeeze_dgrad_kernel
 //   ts_sew_squeeze_wgrad       dw[j][g] = dz^T x(shifted by s r + j - p) over all B T2 rows, sew_squeeze_wgrad_kernel
@@ -8,7 +8,7 @@
 
 #include "w2v_rows.hpp"
 
-#include "train/sew_train.h"
+#include "thunder_speech_amd/sew_train.h"
 #include "sew_squeeze.hpp"
 
 namespace ts {

@@ -1,6 +1,6 @@
 // WavLM's gated relative-position attention (transformers modeling_wavlm.py WavLMAttention.forward / compute_bias /
 // _relative_positions_bucket, reached from huggingface/compatibility.py:31-42 for a WavLM checkpoint).  Declared in
-// include/thunder_speech_amd_wavlm.h; everything around the attention core is the wav2vec2 sequence of csrc/w2v_attn.hip.
+// include/thunder_speech_amd/wavlm.h; everything around the attention core is the wav2vec2 sequence of csrc/w2v_attn.hip.
 //
 //   ts_wavlm_rel_bias        rb[h][d + t - 1] = E[bucket(d)][h] for d in [-(t - 1), t - 1]: the [H][2t - 1] diagonals of the
 //                            position bias, never the [T][T] matrix; the bucket table is built on the host (float32 log there)
@@ -11,7 +11,7 @@
 //     precision 0:          scores from the f32 GEMM, one row kernel (gate, bias, mask, softmax), P V on the f32 GEMM
 #include "attn_tile.hpp"
 #include "w2v_rows.hpp"
-#include "thunder_speech_amd_wavlm.h"
+#include "thunder_speech_amd/wavlm.h"
 
 namespace ts {
 

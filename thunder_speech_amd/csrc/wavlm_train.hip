@@ -1,7 +1,7 @@
 // Mixed-precision WavLM FINE-TUNING: the gated relative-position attention of transformers' WavLMAttention (modeling_wavlm.py forward /
 // compute_bias, reached through huggingface/compatibility.py:31-42 under the reference's training_step, module.py:102-127) forward and backward
 // without the [T][T] matrices, plus the gate and the position-bias embedding with their gradients.  Declared in
-// include/thunder_speech_amd_wavlm_train.h.  The attention kernels are the sequences of csrc/attn_tile.hpp with the bias pieces of its WavLM
+// include/thunder_speech_amd/wavlm_train.h.  The attention kernels are the sequences of csrc/attn_tile.hpp with the bias pieces of its WavLM
 // section; the mask kernel, the row-dot kernel and the argument check are those of csrc/w2v_attn_train.hip (the wav2vec2 path):
 //
 //   ts_wavlm_gate_fwd       g[b][h][i] = ga (gb c_h - 1) + 2, ga = sigmoid(p0..3), gb = sigmoid(p4..7), p = x_h W^T + beta   (ga, gb kept)
@@ -17,7 +17,7 @@
 //   ts_wavlm_rel_bias_bwd   dE[k][h] = sum over the diagonals d with bucket(d) = k of drb[h][d + t - 1]: one wave per (bucket, head), a gather
 // No float atomics anywhere: two calls give the same bits.
 #include "attn_tile.hpp"
-#include "thunder_speech_amd_wavlm_train.h"
+#include "thunder_speech_amd/wavlm_train.h"
 
 namespace ts {
 

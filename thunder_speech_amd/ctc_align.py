@@ -21,7 +21,7 @@ WORD_SEPARATORS = (" ", "|", "▁")       # what BatchTextTransformer.decode_pre
 
 @dataclass
 class Alignment:
-    """Device tensors of `forced_align` (abi/ctc_align.h: ts_ctc_align)."""
+    """Device tensors of `forced_align` (thunder_speech_amd/ctc_align.h: ts_ctc_align)."""
     path: Tensor          # int32 [B, T']     token id per frame, -1 beyond the clip's length and for infeasible clips
     spans: Tensor         # int32 [B, S, 2]   first and end frame (exclusive) of each target position, (0, 0) beyond the target's length
     span_logp: Tensor     # f32 [B, S]        sum of the span's log-probabilities
@@ -32,7 +32,7 @@ class Alignment:
 
 @dataclass
 class GreedySpans:
-    """Device tensors of `greedy_spans` (abi/ctc_align.h: ts_ctc_greedy_spans); entries at or beyond counts[b] are zero."""
+    """Device tensors of `greedy_spans` (thunder_speech_amd/ctc_align.h: ts_ctc_greedy_spans); entries at or beyond counts[b] are zero."""
     tokens: Tensor        # int32 [B, T']
     spans: Tensor         # int32 [B, T', 2]
     span_logp: Tensor     # f32 [B, T']

@@ -4,7 +4,7 @@ src/thunder/module.py:98-101).
 `beam_search` runs the three launches of csrc/ctc_beam.hip (frame candidates, the search with one workgroup per utterance, the
 backtrace) on the logits `calculate_ctc` takes ([B, V, T'] BEFORE softmax) and returns a dataclass of DEVICE tensors; the host side
 (`BeamToken`, `Hypothesis`, `hypotheses_from_tables`) is what `BaseCTCModule.predict_nbest` hands to users.  The algorithm is
-specified in abi/ctc_beam.h.  There is no CPU path."""
+specified in thunder_speech_amd/ctc_beam.h.  There is no CPU path."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
@@ -19,7 +19,7 @@ from .ctc_align import _logits_f32
 
 @dataclass
 class BeamResult:
-    """Device tensors of `beam_search` (abi/ctc_beam.h: ts_ctc_beam_search); entries beyond a length or a count are zero, scores beyond
+    """Device tensors of `beam_search` (thunder_speech_amd/ctc_beam.h: ts_ctc_beam_search); entries beyond a length or a count are zero, scores beyond
     the count are -inf."""
     tokens: Tensor        # int32 [B, n_best, T']   class ids, forward order
     frames: Tensor        # int32 [B, n_best, T']   frame at which each token entered its hypothesis

@@ -3,7 +3,7 @@
 The LM's words are the acoustic model's CTC classes: characters for QuartzNet and wav2vec2, sentencepiece pieces for Citrinet.  The host side
 (this module, numpy only) reads an ARPA file (`read_arpa`), matches its words to the classes and compiles the table to a back-off automaton
 (`NGramLM`); `NGramLM.weights(alpha, beta)` forms the f64 factors of one setting on the host, so that the device takes no exp and no log of the
-LM, and `beam_search_lm` runs the three launches of csrc/ctc_beam_lm.hip on them.  The algorithm is specified in capi/ctc_beam_lm.h.  There is
+LM, and `beam_search_lm` runs the three launches of csrc/ctc_beam_lm.hip on them.  The algorithm is specified in thunder_speech_amd/ctc_beam_lm.h.  There is
 no CPU path for the search."""
 from __future__ import annotations
 
@@ -100,13 +100,13 @@ def read_arpa(path_or_text: str) -> Tuple[int, List[Dict[Tuple[str, ...], Tuple[
 
 @dataclass
 class BeamLMResult(BeamResult):
-    """`BeamResult` of the fused search (capi/ctc_beam_lm.h: ts_ctc_beam_lm_search); `scores` are the logs of the fused masses."""
+    """`BeamResult` of the fused search (thunder_speech_amd/ctc_beam_lm.h: ts_ctc_beam_lm_search); `scores` are the logs of the fused masses."""
     lm_scores: Any = None     # f32 [B, n_best]         unweighted log10 LM score of the hypothesis, </s> included where it was applied
 
 
 @dataclass
 class LMWeights:
-    """Device tables of one (alpha, beta) setting (capi/ctc_beam_lm.h: ts_ctc_lm); `struct` holds their addresses."""
+    """Device tables of one (alpha, beta) setting (thunder_speech_amd/ctc_beam_lm.h: ts_ctc_lm); `struct` holds their addresses."""
     alpha: float
     beta: float
     tensors: dict

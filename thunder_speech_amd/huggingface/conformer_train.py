@@ -1,7 +1,7 @@
 """wav2vec2-conformer (rotary) fine-tuning on the HIP kernels: the training-mode forward of `transformers.Wav2Vec2ConformerModel` as a chain of
 autograd nodes whose forward and backward are C-ABI launches, in MIXED PRECISION only (`train_precision="bf16"`).  Everything a conformer layer
 shares with wav2vec2 is huggingface/train.py's (LinearMixed, AttentionFused, FFNActLinear, LayerNorm, Dropout, MaskEmbed, MaskRows, Add, the frozen
-feature-extractor plan); this module adds what is the conformer's own, on csrc/conformer_train.hip (thunder_speech_amd/abi/conformer_train.h):
+feature-extractor plan); this module adds what is the conformer's own, on csrc/conformer_train.hip (include/thunder_speech_amd/conformer_train.h):
 
     LayerNormRotary    LN(h) and its rotated copy (the inference launch ts_conformer_layernorm_rotary_fwd at f32); backward: ts_conformer_rotary_bwd,
                        then the LayerNorm backward

@@ -6,11 +6,11 @@ src/thunder/huggingface/compatibility.py:31-42: `self.original_encoder(audio, at
 weights (same attribute name `original_encoder`, same state-dict keys, so checkpoints and fine-tuning code see no
 difference); the arithmetic runs in `Wav2Vec2Plan`, which keeps packed fp32 device copies of the weights and issues one C-ABI
 call per stage.  Both published families (group-norm / post-LN: wav2vec2-base-960h, -large-960h; layer-norm / pre-LN: -large-lv60, xlsr);
-WavLM runs the same sequence with its gated relative-position attention (csrc/wavlm.hip, include/thunder_speech_amd_wavlm.h) in place of
+WavLM runs the same sequence with its gated relative-position attention (csrc/wavlm.hip, include/thunder_speech_amd/wavlm.h) in place of
 the wav2vec2 one (fine-tuning in mixed precision only: csrc/wavlm_train.hip); wav2vec2-conformer (rotary) runs conformer blocks behind the same
 front end (huggingface/conformer.py; fine-tuning in mixed precision only: huggingface/conformer_train.py, csrc/conformer_train.hip); SEW runs the post-LN layers at 1 / squeeze_factor of the frame rate between csrc/sew.hip's
-squeeze and an upsampling GEMM (huggingface/sew.py, thunder_speech_amd/abi/sew.h; fine-tuning in mixed precision only: huggingface/sew_train.py, csrc/sew_train.hip); MMS (config.adapter_attn_dim: an attention adapter behind every pre-LN layer) and the head_dim 80
-of MMS-1B / XLS-R 1B run on csrc/mms.hip and the head_dim 80 kernel of csrc/w2v_attn.hip (include/thunder_speech_amd_mms.h, inference only); training mode (fine-tuning with the conv feature extractor frozen) runs
+squeeze and an upsampling GEMM (huggingface/sew.py, include/thunder_speech_amd/sew.h; fine-tuning in mixed precision only: huggingface/sew_train.py, csrc/sew_train.hip); MMS (config.adapter_attn_dim: an attention adapter behind every pre-LN layer) and the head_dim 80
+of MMS-1B / XLS-R 1B run on csrc/mms.hip and the head_dim 80 kernel of csrc/w2v_attn.hip (include/thunder_speech_amd/mms.h, inference only); training mode (fine-tuning with the conv feature extractor frozen) runs
 through huggingface/train.py; no CPU fallback."""
 from __future__ import annotations
 
@@ -48,8 +48,8 @@ def feat_extract_output_lengths(conv_kernel, conv_stride, lengths: torch.Tensor,
 # norm, pre-LN): the wav2vec2 layers with WavLMAttention's gated relative-position bias in the attention core (csrc/wavlm.hip, head_dim 64 -- every
 # published WavLM -- fine-tuned with train_precision="bf16" only, csrc/wavlm_train.hip); wav2vec2-conformer with rotary position embeddings
 # (fine-tuned with train_precision="bf16" only, huggingface/conformer_train.py): the wav2vec2 front end and adapter around conformer blocks (huggingface/conformer.py, csrc/conformer.hip,
-# include/thunder_speech_amd_conformer.h); sew (fine-tuned with train_precision="bf16" only, huggingface/sew_train.py): wav2vec2's post-LN layers at 1 / squeeze_factor of the frame rate between a
-# strided positional conv added to an average pool and an upsampling projection (huggingface/sew.py, csrc/sew.hip, thunder_speech_amd/abi/sew.h).
+# include/thunder_speech_amd/conformer.h); sew (fine-tuned with train_precision="bf16" only, huggingface/sew_train.py): wav2vec2's post-LN layers at 1 / squeeze_factor of the frame rate between a
+# strided positional conv added to an average pool and an upsampling projection (huggingface/sew.py, csrc/sew.hip, include/thunder_speech_amd/sew.h).
 # Others (sew-d's disentangled attention, the conformer's relative-position variant ...) have layers this library holds no kernels for and raise.
 # Fine-tuning (huggingface/train.py, TRAINABLE_MODEL_TYPES): every family above but the conformer, which trains on the chain of
 # huggingface/conformer_train.py, and sew, which trains on the chain of huggingface/sew_train.py (both in mixed precision only).  hubert, unispeech and unispeech-sat train on the

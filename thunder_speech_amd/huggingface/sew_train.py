@@ -2,7 +2,7 @@
 whose forward and backward are C-ABI launches, in MIXED PRECISION only (`train_precision="bf16"`).  SEW's layers are wav2vec2's post-LN layers at
 1 / squeeze_factor of the frame rate, so everything but the two ends of the encoder is huggingface/train.py's (LinearMixed, LayerNorm, AttentionFused at
 head_dim 64, FFNActLinear, BiasGelu, Dropout, MaskEmbed, MaskRows, the frozen feature-extractor plan); this module adds what is SEW's own, on
-csrc/sew_train.hip (thunder_speech_amd/abi/train/sew_train.h):
+csrc/sew_train.hip (include/thunder_speech_amd/sew_train.h):
 
     SqueezeGelu       y[r] = mean_{i < s} x[s r + i] + gelu(conv_stride_s(x)[r] + b): the inference kernel with the conv result kept
                       (ts_sew_squeeze_train_fwd); backward: GELU backward, bias column sum, ts_sew_squeeze_dgrad (pool^T + conv^T on the matrix
@@ -35,7 +35,7 @@ __all__ = ["train_forward", "refuse_untrainable", "squeeze_trains", "pack_squeez
 
 
 def squeeze_trains(channels_per_group: int, kernel: int, stride: int) -> bool:
-    """Whether the three launches of abi/train/sew_train.h take this geometry (ts_sew_squeeze_train_supported): the geometries the inference call runs on
+    """Whether the three launches of thunder_speech_amd/sew_train.h take this geometry (ts_sew_squeeze_train_supported): the geometries the inference call runs on
     its matrix-core kernel -- 24 or 32 channels per group, the staged window within 64 KiB of LDS.  Python mirror of the launchers' check."""
     return stride >= 1 and kernel >= 1 and squeeze_on_matrix_cores(channels_per_group, kernel, stride)
 

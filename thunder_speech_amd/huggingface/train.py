@@ -184,7 +184,7 @@ class LinearMixed(torch.autograd.Function):
 
 class LoRALinear(torch.autograd.Function):
     """nn.Linear with a FROZEN weight and bias plus low-rank (LoRA) terms on column slices of its output, in mixed precision (csrc/lora_train.hip,
-    thunder_speech_amd/lora/lora_train.h):  y = x W^T + b, then y[:, c0 : c0 + n_t] += s (x A_t^T) B_t^T per target t = (c0, A_t [r][k], B_t [n_t][r]).
+    include/thunder_speech_amd/lora_train.h):  y = x W^T + b, then y[:, c0 : c0 + n_t] += s (x A_t^T) B_t^T per target t = (c0, A_t [r][k], B_t [n_t][r]).
     The fused q | k | v product passes up to three targets (each its own slice of [rows][3 c]), out_proj one (c0 = 0).
     The base product is LinearMixed's, call for call (same casts, same GEMM, same split-K rule), without its weight gradient; the low-rank path is a
     path of its own (ts_lora_fwd behind the GEMM, ts_lora_bwd behind the data-gradient GEMM), never folded into the bf16 copy of W.
@@ -353,7 +353,7 @@ class LayerNorm(torch.autograd.Function):
 class AttnAdapter(torch.autograd.Function):
     """MMS attention adapter with its residual: y = h + W2 relu(W1 LN(h; norm_w, norm_b, eps 1e-5) + b1) + b2 (transformers'
     Wav2Vec2AttnAdapterLayer at the end of a pre-LN layer), one launch forward and a fused backward (csrc/mms_adapter_train.hip,
-    include/thunder_speech_amd_mms_adapter_train.h).  Only h and the weights are saved: the backward recomputes LN(h), z and the ReLU mask.
+    include/thunder_speech_amd/mms_adapter_train.h).  Only h and the weights are saved: the backward recomputes LN(h), z and the ReLU mask.
     Mixed mode: the two small weights are cast to bf16 here and multiply bf16 operands (f32 accumulation); LayerNorm and every gradient are f32."""
 
     @staticmethod
@@ -601,7 +601,7 @@ class AttentionFused(torch.autograd.Function):
 
 
 class AttentionFused80(torch.autograd.Function):
-    """AttentionFused at head_dim 80 (XLS-R 1B / MMS geometry: hidden 1280, 16 heads; csrc/mms_train.hip on the kernels of csrc/w2v_attn_train.hip, include/thunder_speech_amd_mms_train.h):
+    """AttentionFused at head_dim 80 (XLS-R 1B / MMS geometry: hidden 1280, 16 heads; csrc/mms_train.hip on the kernels of csrc/w2v_attn_train.hip, include/thunder_speech_amd/mms_train.h):
     the same contract, node shape and saved tensors on the ts_mms_attention_train_* entry points."""
     ENTRY = "ts_mms_attention_train"
 

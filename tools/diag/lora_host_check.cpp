@@ -1,12 +1,12 @@
 // Stand-alone driver of the LoRA entry points' HOST side (argument checks, workspace arithmetic) for the sanitizer build of the library
 // (python -m thunder_speech_amd.build --asan): every call below returns before a launch, so it runs without a GPU.
-//   clang++ -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan -I include -I thunder_speech_amd/lora \
+//   clang++ -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan -I include \
 //       tools/diag/lora_host_check.cpp thunder_speech_amd/libthunder_speech_hip.asan.so -Wl,-rpath,thunder_speech_amd -o tools/diag/lora_host_check
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 
-#include "lora_train.h"
+#include "thunder_speech_amd/lora_train.h"
 
 static int failures = 0;
 #define EXPECT(expr, want)                                                                \
