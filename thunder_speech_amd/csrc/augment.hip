@@ -16,8 +16,14 @@ namespace ts {
 
 // torchaudio.functional.mask_along_axis (0.12) / spec_augment._create_mask: value = rand * mask_param;
 // min_value = rand * (size - value); [start, end) = [long(min_value), long(min_value) + long(value))
+// Every step is rounded to f32 like the reference's tensor ops.  Under -ffast-math size - u * mask_param contracts into one fma, whose single
+// rounding moves min_value across an integer for about one span in 10^5 (profiles/data_text_optim_kernel_checks.md); the contraction happens in
+// the back end, out of a pragma's reach, so the product is made opaque to it.
 __host__ __device__ inline void draw_span(float u_value, float u_min, int mask_param, int size, int& start, int& end) {
-  const float value = u_value * (float)mask_param;
+  float value = u_value * (float)mask_param;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(value));
+#endif
   const float min_value = u_min * ((float)size - value);
   start = (int)min_value;
   end = (int)min_value + (int)value;

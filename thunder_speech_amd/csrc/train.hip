@@ -67,6 +67,9 @@ __global__ __launch_bounds__(256) void decoder_wgrad_kernel(const float* __restr
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, long long n, float lr, float beta1, float beta2,
                                                     float eps, float weight_decay, float bias_c1, float bias_c2) {
+  // the moments are formed as written: left to -ffast-math's reassociation they become g + beta (m - g), whose difference is rounded at the size of
+  // the gradient -- beta2 / (1 - beta2) = 1000 roundings' worth of relative error in exp_avg_sq wherever it is small against g^2 (the first steps)
+#pragma clang fp reassociate(off)
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float gi = g[i];
@@ -84,6 +87,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
 // receives the updated parameter rounded to bf16: the GEMM operand copy of the mixed-precision training path, refreshed for free.
 __global__ __launch_bounds__(256) void adamw_multi_kernel(const unsigned long long* __restrict__ table, float lr, float beta1, float beta2,
                                                           float eps, float weight_decay, float bias_c1, float bias_c2) {
+#pragma clang fp reassociate(off)            // as in adamw_kernel
   const unsigned long long* e = table + (size_t)blockIdx.y * 6;
   const long long n = (long long)e[4];
   const long long i0 = (long long)blockIdx.x * 1024 + threadIdx.x;
