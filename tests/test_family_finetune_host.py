@@ -57,6 +57,42 @@ def test_data2vec_audio_still_refuses_what_the_other_families_refuse_with_the_sa
             T.refuse_untrainable(enc, mixed)
 
 
+def test_mixed_precision_restores_the_mode_it_found_on_return_on_exception_and_when_nested():
+    from thunder_speech_amd.huggingface import train as T
+    assert T._MIXED is False
+    with T.mixed_precision(True):
+        assert T._MIXED is True
+        with T.mixed_precision(False):
+            assert T._MIXED is False
+            with T.mixed_precision(True):
+                assert T._MIXED is True
+            assert T._MIXED is False
+        assert T._MIXED is True                                # the inner block did not clear the outer one's mode
+        with pytest.raises(KeyError):
+            with T.mixed_precision(False):
+                assert T._MIXED is False
+                raise KeyError("out by exception")
+        assert T._MIXED is True
+    assert T._MIXED is False
+    with pytest.raises(KeyError):
+        with T.mixed_precision(True):
+            raise KeyError("out by exception")
+    assert T._MIXED is False
+
+
+def test_every_supported_model_type_resolves_to_a_chain_module_with_the_two_entry_points():
+    import inspect
+    from thunder_speech_amd.huggingface import conformer_train, encoder, sew_train, train
+    assert set(encoder.TRAIN_CHAINS) == set(encoder.SUPPORTED_MODEL_TYPES)
+    for model_type in encoder.SUPPORTED_MODEL_TYPES:
+        chain = encoder.train_chain(model_type)
+        assert chain is {"wav2vec2-conformer": conformer_train, "sew": sew_train}.get(model_type, train), model_type
+        params = list(inspect.signature(chain.train_forward).parameters)
+        assert params == ["adapt", "audio", "lengths"], (model_type, params)
+        required = [p for p in inspect.signature(chain.refuse_untrainable).parameters.values() if p.default is p.empty]
+        assert [p.name for p in required] == ["adapt"], (model_type, required)           # callable with the adapter alone
+
+
 def test_the_conformer_is_still_refused_by_name_in_both_places():
     from thunder_speech_amd.huggingface import train as T
     assert "wav2vec2-conformer" not in T.TRAINABLE_MODEL_TYPES

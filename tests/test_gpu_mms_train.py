@@ -220,15 +220,11 @@ def _against_the_materialised_node(b, t, heads, p, key_len):
     ref.backward(dout)
     dref = qkv.grad.clone()
     qkv.grad = None
-    old = T._MIXED
-    T._MIXED = True
-    try:
+    with T.mixed_precision(True):
         out = T.attention(qkv, key_len, heads, p, seed)
         assert isinstance(out.grad_fn, T.AttentionFused80._backward_cls) and type(out.grad_fn).__name__ == "AttentionFused80Backward"
         out.backward(dout)
         other = T.attention(qkv.detach(), key_len, heads, p, seed + 1) if p > 0 else None
-    finally:
-        T._MIXED = old
     torch.cuda.synchronize()
     assert _rel(out.detach(), ref.detach()) <= 2e-2
     for sl in (slice(0, c), slice(c, 2 * c), slice(2 * c, 3 * c)):
@@ -248,14 +244,16 @@ def test_attention_node_matches_the_materialised_path(p, ragged):
 def test_the_switch_still_selects_the_materialised_node():
     from thunder_speech_amd.huggingface import train as T
     qkv = torch.randn(1, 40, 3 * 160, device="cuda", requires_grad=True)
-    old, old_f = T._MIXED, T.FUSED_ATTENTION
+    old_f = T.FUSED_ATTENTION
     try:
-        T._MIXED, T.FUSED_ATTENTION = True, False
-        assert isinstance(T.attention(qkv, None, 2, 0.0, 0).grad_fn, T.Attention._backward_cls)
-        T._MIXED, T.FUSED_ATTENTION = False, True                         # f32 training is unchanged
-        assert isinstance(T.attention(qkv, None, 2, 0.0, 0).grad_fn, T.Attention._backward_cls)
+        T.FUSED_ATTENTION = False
+        with T.mixed_precision(True):
+            assert isinstance(T.attention(qkv, None, 2, 0.0, 0).grad_fn, T.Attention._backward_cls)
+        T.FUSED_ATTENTION = True                                          # f32 training is unchanged
+        with T.mixed_precision(False):
+            assert isinstance(T.attention(qkv, None, 2, 0.0, 0).grad_fn, T.Attention._backward_cls)
     finally:
-        T._MIXED, T.FUSED_ATTENTION = old, old_f
+        T.FUSED_ATTENTION = old_f
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -297,14 +297,10 @@ def test_fused_training_attention_matches_the_materialised_path_forward_and_back
     ref.backward(dout)
     dref = qkv.grad.clone()
     qkv.grad = None
-    old = T._MIXED
-    T._MIXED = True
-    try:
+    with T.mixed_precision(True):
         out = T.attention(qkv, key_len, heads, p, seed)
         assert isinstance(out.grad_fn, T.AttentionFused._backward_cls)
         out.backward(dout)
-    finally:
-        T._MIXED = old
     torch.cuda.synchronize()
     rel = lambda a_, r_: float((a_ - r_).norm() / r_.norm())
     assert rel(out.detach(), ref.detach()) <= 2e-2
@@ -312,11 +308,8 @@ def test_fused_training_attention_matches_the_materialised_path_forward_and_back
         assert bool(torch.isfinite(qkv.grad[..., sl]).all())
         assert rel(qkv.grad[..., sl], dref[..., sl]) <= 2e-2
     if p > 0:                                            # the mask matters: another seed gives another result
-        T._MIXED = True
-        try:
+        with T.mixed_precision(True):
             other = T.attention(qkv.detach(), key_len, heads, p, seed + 1)
-        finally:
-            T._MIXED = old
         assert rel(other, ref.detach()) > 5e-2
 
 
@@ -327,16 +320,12 @@ def test_fused_training_attention_is_reproducible_bit_for_bit():
     qkv = torch.randn(2, 300, 3 * 128, device="cuda")
     dout = torch.randn(2, 300, 128, device="cuda")
     res = []
-    old = T._MIXED
-    T._MIXED = True
-    try:
+    with T.mixed_precision(True):
         for _ in range(2):
             x = qkv.clone().requires_grad_(True)
             y = T.attention(x, None, 2, 0.1, 42)
             y.backward(dout)
             res.append((y.detach().clone(), x.grad.clone()))
-    finally:
-        T._MIXED = old
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
 
 
@@ -354,16 +343,12 @@ def test_mixed_precision_positional_conv_matches_the_f32_path_forward_and_backwa
     bias = torch.randn(c, device="cuda") * 0.1
     dy = torch.randn(b, t, c, device="cuda")
     res = {}
-    old = T._MIXED
-    try:
-        for mode in (False, True):
-            T._MIXED = mode
+    for mode in (False, True):
+        with T.mixed_precision(mode):
             xi, wi, bi = x.clone().requires_grad_(True), wk.clone().requires_grad_(True), bias.clone().requires_grad_(True)
             y = T.PosConvGelu.apply(xi, wi, bi)
             y.backward(dy)
             res[mode] = (y.detach(), xi.grad, wi.grad, bi.grad)
-    finally:
-        T._MIXED = old
     torch.cuda.synchronize()
     for a_, r_, what in zip(res[True], res[False], ("y", "dx", "dw", "db")):
         assert bool(torch.isfinite(a_).all()), what
@@ -419,9 +404,7 @@ def test_fused_feed_forward_activation_node_equals_the_three_separate_nodes(rows
     dy = torch.randn(*rows_shape, n, device="cuda")
     seed = 424242
     res = []
-    old = T._MIXED
-    T._MIXED = True
-    try:
+    with T.mixed_precision(True):
         for fused in (True, False):
             zi, b1i, w2i, b2i = (t_.clone().requires_grad_(True) for t_ in (z, b1, w2, b2))
             if fused:
@@ -432,8 +415,6 @@ def test_fused_feed_forward_activation_node_equals_the_three_separate_nodes(rows
                 y = T.LinearMixed.apply(a, w2i, b2i)
             y.backward(dy)
             res.append((y.detach(), zi.grad, w2i.grad, b1i.grad, b2i.grad))
-    finally:
-        T._MIXED = old
     torch.cuda.synchronize()
     for i in (0, 1, 2):
         assert torch.equal(res[0][i], res[1][i]), i

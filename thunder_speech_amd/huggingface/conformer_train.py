@@ -1,7 +1,7 @@
 """wav2vec2-conformer (rotary) fine-tuning on the HIP kernels: the training-mode forward of `transformers.Wav2Vec2ConformerModel` as a chain of
 autograd nodes whose forward and backward are C-ABI launches, in MIXED PRECISION only (`train_precision="bf16"`).  Everything a conformer layer
-shares with wav2vec2 is huggingface/train.py's (LinearMixed, AttentionFused, FFNActLinear, LayerNorm, Dropout, MaskEmbed, MaskRows, Add, the frozen
-feature-extractor plan); this module adds what is the conformer's own, on csrc/conformer_train.hip (include/thunder_speech_amd/conformer_train.h):
+shares with wav2vec2 is huggingface/train.py's (LinearMixed, AttentionFused, FFNActLinear, LayerNorm, Dropout, mask_time, MaskRows, Add,
+frozen_features); this module adds what is the conformer's own, on csrc/conformer_train.hip (include/thunder_speech_amd/conformer_train.h):
 
     LayerNormRotary    LN(h) and its rotated copy (the inference launch ts_conformer_layernorm_rotary_fwd at f32); backward: ts_conformer_rotary_bwd,
                        then the LayerNorm backward
@@ -26,7 +26,6 @@ from __future__ import annotations
 
 from typing import Optional
 
-import numpy as np
 import torch
 from torch import Tensor
 
@@ -42,6 +41,7 @@ __all__ = ["train_forward", "refuse_untrainable", "LayerNormRotary", "RotaryQKV"
 def refuse_untrainable(adapt) -> None:
     """Raise NotImplementedError, by name, for a wav2vec2-conformer configuration the chain below has no backward for.  No device work: the adapter
     calls it before its GPU check."""
+    T.refuse_untrainable_lora(adapt)                  # (lora_finetuning() refuses the conformer: only a hand-attached `lora` gets here)
     enc = adapt.original_encoder
     cfg = enc.config
     precision = getattr(adapt, "train_precision", "fp32")
@@ -52,12 +52,7 @@ def refuse_untrainable(adapt) -> None:
         raise NotImplementedError("wav2vec2-conformer: fine-tuning runs on the fused attention only (train.FUSED_ATTENTION is False)")
     if getattr(cfg, "add_adapter", False):
         raise NotImplementedError("wav2vec2-conformer fine-tuning: add_adapter=True is inference-only (the adapter layers have no backward here)")
-    if float(getattr(cfg, "mask_feature_prob", 0.0)) > 0.0 and getattr(cfg, "apply_spec_augment", True):
-        raise NotImplementedError("wav2vec2-conformer fine-tuning: mask_feature_prob > 0 is not supported")
-    unfrozen = [n for n, p in enc.feature_extractor.named_parameters() if p.requires_grad]
-    if unfrozen:
-        raise NotImplementedError("wav2vec2-conformer fine-tuning: the conv feature extractor is frozen (freeze_feature_encoder); "
-                                  f"{len(unfrozen)} of its parameters have requires_grad=True (first: feature_extractor.{unfrozen[0]})")
+    T.refuse_masking_and_unfrozen(enc, "wav2vec2-conformer fine-tuning")
     if int(cfg.intermediate_size) % 32:
         raise NotImplementedError(f"wav2vec2-conformer fine-tuning: intermediate_size={cfg.intermediate_size} (the fused feed-forward activation "
                                   "takes multiples of 32)")
@@ -241,11 +236,8 @@ def train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
     """Training-mode Wav2Vec2ConformerModel.forward -> last_hidden_state [B, T', C] (f32, time-major).  `adapt`: the HuggingFaceEncoderAdapt module
     (its `original_encoder` owns the parameters), with train_precision == "bf16"."""
     refuse_untrainable(adapt)
-    T._MIXED = True                                   # train.linear / train.attention: LinearMixed and the fused attention
-    try:
+    with T.mixed_precision(True):                     # train.linear / train.attention: LinearMixed and the fused attention
         return _train_forward(adapt, audio, lengths)
-    finally:
-        T._MIXED = False
 
 
 def _train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
@@ -258,9 +250,7 @@ def _train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
     if audio.shape[0] * frames < 2 and any(layer.conv_module.batch_norm.training for layer in enc.encoder.layers):
         # one frame in the whole batch: BatchNorm has no variance to normalise with; torch's own check and message, before any launch
         raise ValueError(f"Expected more than 1 value per channel when training, got input size {torch.Size([audio.shape[0], c, frames])}")
-    plan = adapt._plan_frozen(dev)
-    with torch.no_grad():                                   # frozen conv feature extractor: the inference kernels
-        feats = plan.feature_extractor(audio)
+    feats = T.frozen_features(adapt, audio)
     b, t, _ = feats.shape
     eps = float(cfg.layer_norm_eps)
     fp, en = enc.feature_projection, enc.encoder
@@ -270,11 +260,7 @@ def _train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
     key_len = None
     if lengths is not None:
         key_len = feat_extract_output_lengths(cfg.conv_kernel, cfg.conv_stride, lengths.to(dev).long()).to(torch.int32).contiguous()
-    if getattr(cfg, "apply_spec_augment", True) and float(cfg.mask_time_prob) > 0.0:
-        m = T.compute_mask_indices(b, t, float(cfg.mask_time_prob), int(cfg.mask_time_length), None if key_len is None else key_len.tolist(),
-                                   int(getattr(cfg, "mask_time_min_masks", 2)))
-        if m.any():
-            h = T.MaskEmbed.apply(h, torch.from_numpy(m.astype(np.uint8)).to(dev), enc.masked_spec_embed)
+    h = T.mask_time(enc, h, key_len)
     if key_len is not None:
         h = T.MaskRows.apply(h, key_len)
     p_hid, p_act, p_att = float(cfg.hidden_dropout), float(cfg.activation_dropout), float(cfg.attention_dropout)

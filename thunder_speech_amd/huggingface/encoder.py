@@ -11,9 +11,10 @@ the wav2vec2 one (fine-tuning in mixed precision only: csrc/wavlm_train.hip); wa
 front end (huggingface/conformer.py; fine-tuning in mixed precision only: huggingface/conformer_train.py, csrc/conformer_train.hip); SEW runs the post-LN layers at 1 / squeeze_factor of the frame rate between csrc/sew.hip's
 squeeze and an upsampling GEMM (huggingface/sew.py, include/thunder_speech_amd/sew.h; fine-tuning in mixed precision only: huggingface/sew_train.py, csrc/sew_train.hip); MMS (config.adapter_attn_dim: an attention adapter behind every pre-LN layer) and the head_dim 80
 of MMS-1B / XLS-R 1B run on csrc/mms.hip and the head_dim 80 kernel of csrc/w2v_attn.hip (include/thunder_speech_amd/mms.h, inference only); training mode (fine-tuning with the conv feature extractor frozen) runs
-through huggingface/train.py; no CPU fallback."""
+through the chain module TRAIN_CHAINS names for the model type (huggingface/train.py, conformer_train.py, sew_train.py); no CPU fallback."""
 from __future__ import annotations
 
+import importlib
 import math
 import os
 
@@ -57,6 +58,15 @@ def feat_extract_output_lengths(conv_kernel, conv_stride, lengths: torch.Tensor,
 # csrc/posconv_stack_train.hip, include/thunder_speech_amd/posconv_stack_train.h); wavlm in mixed precision only.
 SUPPORTED_MODEL_TYPES = ("wav2vec2", "hubert", "data2vec-audio", "unispeech", "unispeech-sat", "wavlm", "wav2vec2-conformer", "sew")
 CONFORMER_ACTIVATIONS = ("swish", "silu", "gelu")
+# model_type -> the module of this package that holds its fine-tuning chain: `refuse_untrainable(adapt)` (by name, no device work) and
+# `train_forward(adapt, audio, lengths)`.  A new family with a chain of its own is one more entry here
+TRAIN_CHAINS = {**{model_type: "train" for model_type in SUPPORTED_MODEL_TYPES}, "wav2vec2-conformer": "conformer_train", "sew": "sew_train"}
+
+
+def train_chain(model_type: str):
+    """The module that fine-tunes `model_type` (imported on first use: the chains import this module).  A type outside the table goes to
+    huggingface/train.py, whose `refuse_untrainable` names it."""
+    return importlib.import_module("." + TRAIN_CHAINS.get(model_type, "train"), __package__)
 
 
 def relative_position_bucket(relative_positions: torch.Tensor, num_buckets: int, max_distance: int) -> torch.Tensor:
@@ -729,45 +739,17 @@ class HuggingFaceEncoderAdapt(nn.Module):
         return out
 
     def forward(self, audio: torch.Tensor, audio_lengths: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        conformer = getattr(self.original_encoder.config, "model_type", "wav2vec2") == "wav2vec2-conformer"
-        if self.training and getattr(self, "lora", None) is not None:
-            from .train import refuse_untrainable_lora
-            refuse_untrainable_lora(self)               # LoRA: f32 training, a trainable base parameter: by name, before any device work
-        if self.training and conformer:
-            # the conformer trains on a chain of its own, in mixed precision only (huggingface/conformer_train.py, csrc/conformer_train.hip):
-            # train_precision="fp32", an adapter, mask_feature_prob, an unfrozen feature extractor are refused by name, before any device work
-            from .conformer_train import refuse_untrainable as refuse_untrainable_conformer
-            refuse_untrainable_conformer(self)
-        sew = getattr(self.original_encoder.config, "model_type", "wav2vec2") == "sew"
-        if self.training and sew:
-            # sew trains on a chain of its own, in mixed precision only (huggingface/sew_train.py, csrc/sew_train.hip: the squeeze's backward runs on the
-            # matrix-core kernels): train_precision="fp32", a group width other than 24 / 32, mask_feature_prob, an unfrozen feature extractor are
-            # refused by name, before any device work
-            from .sew_train import refuse_untrainable as refuse_untrainable_sew
-            refuse_untrainable_sew(self)
-        if self.training and getattr(self.original_encoder.config, "model_type", "wav2vec2") == "wavlm" and self.train_precision != "bf16":
-            # the gated relative-position attention trains on the fused mixed-precision kernels only (csrc/wavlm_train.hip); f32 fine-tuning would
-            # need a materialised-probability path of its own
-            raise NotImplementedError(f"wavlm: fine-tuning with train_precision={self.train_precision!r} is not implemented (the gated relative-position "
-                                      'attention trains in mixed precision only); use train_precision="bf16", or the module in eval mode')
-        if self.training and getattr(self.original_encoder.config, "model_type", "wav2vec2") == "wavlm":
-            from .train import refuse_untrainable
-            refuse_untrainable(self, True)              # adapter, mask_feature_prob, unfrozen feature extractor: by name, before any device work
-        if self.training and has_attn_adapters(self.original_encoder.config):
-            from .train import refuse_untrainable
-            refuse_untrainable(self, self.train_precision == "bf16")       # adapter_attn_dim: by name, before any device work
+        if self.training:
+            # fine-tuning (module.py:102-127 through this adapter): transformers' training-mode forward -- frozen conv feature extractor, time
+            # masking, dropouts, LayerDrop -- as a chain of autograd nodes on the HIP kernels.  What the family's chain has no backward for
+            # (a train_precision, LoRA outside its regime, an adapter, mask_feature_prob, an unfrozen feature extractor ...) is refused by
+            # name, before any device work
+            chain = train_chain(getattr(self.original_encoder.config, "model_type", "wav2vec2"))
+            chain.refuse_untrainable(self)
         _t.require_gpu(audio, "wav2vec2 encoder")
         x = audio.to(torch.float32).contiguous()
         if self.training:
-            # fine-tuning (module.py:102-127 through this adapter): transformers' training-mode forward -- frozen conv feature extractor, time
-            # masking, dropouts, LayerDrop -- as a chain of autograd nodes on the HIP kernels (huggingface/train.py), f32 arithmetic
-            if conformer:
-                from .conformer_train import train_forward
-            elif sew:
-                from .sew_train import train_forward
-            else:
-                from .train import train_forward
-            h = train_forward(self, x, audio_lengths if self.mask_input else None)
+            h = chain.train_forward(self, x, audio_lengths if self.mask_input else None)
         else:
             h = self._plan(x.device).forward(x, audio_lengths if self.mask_input else None)
         cfg = self.original_encoder.config

@@ -1,7 +1,7 @@
 """SEW fine-tuning on the HIP kernels: the training-mode forward of `transformers.SEWModel` (models/sew/modeling_sew.py) as a chain of autograd nodes
 whose forward and backward are C-ABI launches, in MIXED PRECISION only (`train_precision="bf16"`).  SEW's layers are wav2vec2's post-LN layers at
-1 / squeeze_factor of the frame rate, so everything but the two ends of the encoder is huggingface/train.py's (LinearMixed, LayerNorm, AttentionFused at
-head_dim 64, FFNActLinear, BiasGelu, Dropout, MaskEmbed, MaskRows, the frozen feature-extractor plan); this module adds what is SEW's own, on
+1 / squeeze_factor of the frame rate, so everything but the two ends of the encoder is huggingface/train.py's (post_ln_layer with LinearMixed, LayerNorm,
+AttentionFused at head_dim 64 and FFNActLinear; BiasGelu, Dropout, mask_time, MaskRows, frozen_features); this module adds what is SEW's own, on
 csrc/sew_train.hip (include/thunder_speech_amd/sew_train.h):
 
     SqueezeGelu       y[r] = mean_{i < s} x[s r + i] + gelu(conv_stride_s(x)[r] + b): the inference kernel with the conv result kept
@@ -21,12 +21,10 @@ from __future__ import annotations
 
 from typing import Optional
 
-import numpy as np
 import torch
 from torch import Tensor
 
 from .. import _lib
-from ..rng import next_seed
 from . import train as T
 from .sew import SQUEEZE_SLOT, pooled_key_lengths, squeeze_on_matrix_cores
 from .train import _f32c, _s
@@ -58,6 +56,7 @@ def pack_squeeze_dgrad_taps(wk: Tensor, stride: int) -> Tensor:
 def refuse_untrainable(adapt) -> None:
     """Raise NotImplementedError, by name, for a SEW configuration the chain below has no backward for.  No device work: the adapter calls it before
     its GPU check."""
+    T.refuse_untrainable_lora(adapt)                  # (lora_finetuning() refuses sew: only a hand-attached `lora` gets here)
     enc = adapt.original_encoder
     cfg = enc.config
     precision = getattr(adapt, "train_precision", "fp32")
@@ -72,12 +71,7 @@ def refuse_untrainable(adapt) -> None:
         raise NotImplementedError(f"sew fine-tuning: {c // g} channels per group with num_conv_pos_embeddings={k} and squeeze_factor={s} has no backward "
                                   "(24 or 32 channels per group train, with the staged window of 127 squeeze_factor + num_conv_pos_embeddings rows "
                                   "within 64 KiB of LDS); use the module in eval mode")
-    if float(getattr(cfg, "mask_feature_prob", 0.0)) > 0.0 and getattr(cfg, "apply_spec_augment", True):
-        raise NotImplementedError("sew fine-tuning: mask_feature_prob > 0 is not supported")
-    unfrozen = [n for n, p in enc.feature_extractor.named_parameters() if p.requires_grad]
-    if unfrozen:
-        raise NotImplementedError("sew fine-tuning: the conv feature extractor is frozen (freeze_feature_encoder); "
-                                  f"{len(unfrozen)} of its parameters have requires_grad=True (first: feature_extractor.{unfrozen[0]})")
+    T.refuse_masking_and_unfrozen(enc, "sew fine-tuning")
 
 
 class SqueezeGelu(torch.autograd.Function):
@@ -156,11 +150,8 @@ def train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
     """Training-mode SEWModel.forward -> last_hidden_state [B, T, C] (f32, time-major).  `adapt`: the HuggingFaceEncoderAdapt module (its
     `original_encoder` owns the parameters), with train_precision == "bf16"."""
     refuse_untrainable(adapt)
-    T._MIXED = True                                   # train.linear: LinearMixed
-    try:
+    with T.mixed_precision(True):                     # train.linear: LinearMixed; train.attention: AttentionFused
         return _train_forward(adapt, audio, lengths)
-    finally:
-        T._MIXED = False
 
 
 def _train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
@@ -171,9 +162,7 @@ def _train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
     c, heads, s = int(cfg.hidden_size), int(cfg.num_attention_heads), int(cfg.squeeze_factor)
     if not T.AttentionFused.supported(c, heads):
         raise NotImplementedError(f"sew fine-tuning: head_dim={c // heads} (the fused attention takes 64)")
-    plan = adapt._plan_frozen(dev)
-    with torch.no_grad():                                   # frozen conv feature extractor: the inference kernels
-        feats = plan.feature_extractor(audio)
+    feats = T.frozen_features(adapt, audio)
     b, t, _ = feats.shape
     if t < s:
         raise RuntimeError(f"sew: input too short: {t} frames behind the conv feature extractor, squeeze_factor {s}")
@@ -184,47 +173,25 @@ def _train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
     if getattr(enc, "project_features", int(cfg.conv_dim[-1]) != c):
         h = T.linear(h, enc.feature_projection.weight, enc.feature_projection.bias)
     h = T.dropout(h, float(cfg.feat_proj_dropout))
-    if getattr(cfg, "apply_spec_augment", True) and float(cfg.mask_time_prob) > 0.0:
-        # SEWModel._mask_hidden_states gets no attention mask: spans over all t frames of every clip
-        m = T.compute_mask_indices(b, t, float(cfg.mask_time_prob), int(cfg.mask_time_length), None, int(getattr(cfg, "mask_time_min_masks", 2)))
-        if m.any():
-            h = T.MaskEmbed.apply(h, torch.from_numpy(m.astype(np.uint8)).to(dev), enc.masked_spec_embed)
+    h = T.mask_time(enc, h, None)                           # SEWModel._mask_hidden_states gets no attention mask: spans over all t frames of every clip
     key_len = None
     if lengths is not None:
         frames = feat_extract_output_lengths(cfg.conv_kernel, cfg.conv_stride, lengths.to(dev).long())
         key_len = pooled_key_lengths(frames, s, t2).to(torch.int32).contiguous()
         h = T.MaskRows.apply(h, frames.to(torch.int32).contiguous())
-    # squeeze: weight norm over dim 2 on the parameters (torch ops on [C][C/g][k] only), pool + conv + GELU on the kernels
-    g = int(cfg.num_conv_pos_embedding_groups)
+    # squeeze: the weight norm on the parameters, pool + conv + GELU on the kernels
     conv = en.pos_conv_embed.conv
-    if hasattr(conv, "parametrizations"):
-        wg, wv = conv.parametrizations.weight.original0, conv.parametrizations.weight.original1
-    else:
-        wg, wv = conv.weight_g, conv.weight_v
-    kpos = int(cfg.num_conv_pos_embeddings)
-    w_eff = wg * wv / wv.pow(2).sum(dim=(0, 1), keepdim=True).sqrt()
-    wk = w_eff.view(g, c // g, c // g, kpos).permute(3, 0, 1, 2).contiguous()
-    h = SqueezeGelu.apply(h, wk, conv.bias, s)
+    h = SqueezeGelu.apply(h, T.weight_normed_taps(conv, int(cfg.num_conv_pos_embedding_groups)), conv.bias, s)
     h = T.LayerNorm.apply(h, None, en.layer_norm.weight, en.layer_norm.bias, eps)
     p_hid, p_act, p_att = float(cfg.hidden_dropout), float(cfg.activation_dropout), float(cfg.attention_dropout)
     h = T.dropout(h, p_hid)
     for layer in en.layers:
         if torch.rand([]).item() < float(cfg.layerdrop):       # LayerDrop, drawn as transformers draws it
             continue
-        att, ff = layer.attention, layer.feed_forward
-        wqkv = torch.cat([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight], 0)
-        bqkv = torch.cat([att.q_proj.bias, att.k_proj.bias, att.v_proj.bias], 0)
-        # the post-LN layer of train._train_forward: h = LN(h + attn(h)); h = LN(h + ffn(h))
-        ctxt = T.AttentionFused.apply(T.linear(h, wqkv, bqkv), key_len, heads, p_att, next_seed() if p_att > 0 else 0)
-        a = T.dropout(T.linear(ctxt, att.out_proj.weight, att.out_proj.bias), p_hid)
-        h = T.LayerNorm.apply(a, h, layer.layer_norm.weight, layer.layer_norm.bias, eps)
-        z = T.linear(h, ff.intermediate_dense.weight, None)
-        w2 = ff.output_dense.weight
-        if T.FUSED_FFN_ACT and T.FFNActLinear.supported(w2.shape[1], w2.shape[0]):
-            f = T.FFNActLinear.apply(z, ff.intermediate_dense.bias, w2, ff.output_dense.bias, p_act, next_seed() if p_act > 0 else 0)
-        else:
-            f = T.linear(T.dropout(T.BiasGelu.apply(z, ff.intermediate_dense.bias), p_act), w2, ff.output_dense.bias)
-        h = T.LayerNorm.apply(T.dropout(f, p_hid), h, layer.final_layer_norm.weight, layer.final_layer_norm.bias, eps)
+        att = layer.attention
+        wqkv, bqkv = T.stacked_qkv(att)
+        # (mixed mode, FUSED_ATTENTION and head_dim 64, all checked above: train.attention takes AttentionFused)
+        h = T.post_ln_layer(layer, h, lambda x: T.self_attention(att, x, wqkv, bqkv, key_len, heads, p_att, p_hid), p_act, p_hid, eps)
     up = en.upsample.projection
     u = T.BiasGelu.apply(T.linear(h, up.weight, None), up.bias)            # [B][T2][s C] = [B][s T2][C] row-major
     if s * t2 == t:

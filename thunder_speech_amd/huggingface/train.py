@@ -18,9 +18,15 @@ Wav2Vec2EncoderStableLayerNorm; forward restated for eval mode in oracle/w2v.py)
 time-major f32 activations [B, T, C] (the reference's arithmetic) and owns the backward: PyTorch only chains the nodes and accumulates the
 parameters' .grad; no ATen kernel touches an activation.  The parameters stay the transformers module's own (`original_encoder`, reference
 state-dict keys), so optimizers and checkpoints see no difference.
+
+The chains of the other families (huggingface/conformer_train.py, huggingface/sew_train.py; encoder.TRAIN_CHAINS says which module trains which
+model type) are built from this module's nodes and from the pieces every chain has: frozen_features, mask_time, weight_normed_taps, stacked_qkv,
+self_attention, feed_forward, post_ln_layer, refuse_masking_and_unfrozen.  The precision mode the nodes read is set by `mixed_precision` and by
+nothing else.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Optional
 
 import numpy as np
@@ -306,11 +312,24 @@ class FFNActLinear(torch.autograd.Function):
 
 
 FUSED_FFN_ACT = True        # mixed mode: FFNActLinear for gelu -> dropout -> output_dense (False: the three separate nodes, for A/B)
-_MIXED = False
+_MIXED = False              # the precision mode: read below, set by mixed_precision() only
+
+
+@contextlib.contextmanager
+def mixed_precision(on: bool):
+    """The precision mode of `linear`, `attention`, PosConvGelu, PosConvStackLayer, AttnAdapter and `feed_forward` inside the block: mixed (bf16
+    operands) or f32.  The mode found is restored on the way out, by return or by exception, so blocks nest.  The nodes record the mode in their
+    ctx at forward time: a backward outside the block runs in the mode of its forward."""
+    global _MIXED
+    old, _MIXED = _MIXED, bool(on)
+    try:
+        yield
+    finally:
+        _MIXED = old
 
 
 def linear(x: Tensor, w: Tensor, b: Optional[Tensor]) -> Tensor:
-    """nn.Linear of the training path in the current precision mode (`train_forward(..., mixed=...)`)."""
+    """nn.Linear of the training path in the current precision mode (`mixed_precision`)."""
     if _MIXED and LinearMixed.supported(w.shape[0], w.shape[1]):
         return LinearMixed.apply(x, w, b)
     return Linear.apply(x, w, b)
@@ -945,25 +964,103 @@ def train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
     (its `original_encoder` owns the parameters).  `adapt.train_precision`: "fp32" (default: the reference's arithmetic, every product on the f32
     matrix-core GEMM) or "bf16" (mixed precision: the linear layers -- 92 % of the step's FLOPs -- multiply bf16 operands with f32 accumulation,
     LinearMixed; attention, positional conv, LayerNorm, GELU, dropout, master weights and all gradients stay f32)."""
-    global _MIXED
-    _MIXED = getattr(adapt, "train_precision", "fp32") == "bf16"
-    try:
+    with mixed_precision(getattr(adapt, "train_precision", "fp32") == "bf16"):
         return _train_forward(adapt, audio, lengths)
-    finally:
-        _MIXED = False
+
+
+# ---- what the chains share (this one, huggingface/sew_train.py, huggingface/conformer_train.py) -----------------------------------------------
+def frozen_features(adapt, audio: Tensor) -> Tensor:
+    """The frozen conv feature extractor (compatibility.py:27-28) on the inference kernels, outside the graph: [B, T', conv_dim[-1]]."""
+    with torch.no_grad():
+        return adapt._plan_frozen(audio.device).feature_extractor(audio)
+
+
+def mask_time(enc, h: Tensor, lengths: Optional[Tensor]) -> Tensor:
+    """transformers' `_mask_hidden_states` along time: `masked_spec_embed` over the spans of compute_mask_indices.  `lengths`: the clips' valid
+    frames (the attention mask), or None to draw the spans over all frames of every clip."""
+    cfg = enc.config
+    if getattr(cfg, "apply_spec_augment", True) and float(cfg.mask_time_prob) > 0.0:
+        m = compute_mask_indices(h.shape[0], h.shape[1], float(cfg.mask_time_prob), int(cfg.mask_time_length),
+                                 None if lengths is None else lengths.tolist(), int(getattr(cfg, "mask_time_min_masks", 2)))
+        if m.any():
+            h = MaskEmbed.apply(h, torch.from_numpy(m.astype(np.uint8)).to(h.device), enc.masked_spec_embed)
+    return h
+
+
+def weight_normed_taps(conv, groups: int) -> Tensor:
+    """The effective weight of a weight-normalised grouped conv as taps [k][groups][out][in]: weight norm over dim 2 by torch ops on the PARAMETERS
+    ([C][C/g][k] only), so autograd carries d wk back through it."""
+    if hasattr(conv, "parametrizations"):
+        wg, wv = conv.parametrizations.weight.original0, conv.parametrizations.weight.original1
+    else:
+        wg, wv = conv.weight_g, conv.weight_v
+    w_eff = wg * wv / wv.pow(2).sum(dim=(0, 1), keepdim=True).sqrt()
+    c, cg, k = w_eff.shape
+    return w_eff.view(groups, c // groups, cg, k).permute(3, 0, 1, 2).contiguous()
+
+
+def stacked_qkv(att):
+    """(cat(Wq, Wk, Wv) [3c][c], cat(bq, bk, bv) [3c]) of one attention module: one product for the three projections."""
+    return (torch.cat([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight], 0),
+            torch.cat([att.q_proj.bias, att.k_proj.bias, att.v_proj.bias], 0))
+
+
+def self_attention(att, x: Tensor, wqkv: Tensor, bqkv: Tensor, key_len, heads: int, p_att: float, p_hid: float) -> Tensor:
+    """drop(out_proj(attention(x wqkv^T + bqkv))) of a plain wav2vec2 layer (no LoRA, no WavLM gate: those are `_train_forward`'s own)."""
+    ctxt = attention(linear(x, wqkv, bqkv), key_len, heads, p_att, next_seed() if p_att > 0 else 0)
+    return dropout(linear(ctxt, att.out_proj.weight, att.out_proj.bias), p_hid)
+
+
+def feed_forward(ff, x: Tensor, p_act: float, p_hid: float) -> Tensor:
+    """drop(output_dense(drop_act(gelu(intermediate_dense(x))))) of Wav2Vec2FeedForward; in mixed mode GELU, dropout and the operand cast are one node."""
+    z = linear(x, ff.intermediate_dense.weight, None)
+    w2 = ff.output_dense.weight
+    if _MIXED and FUSED_FFN_ACT and FFNActLinear.supported(w2.shape[1], w2.shape[0]):
+        return dropout(FFNActLinear.apply(z, ff.intermediate_dense.bias, w2, ff.output_dense.bias, p_act, next_seed() if p_act > 0 else 0), p_hid)
+    a = dropout(BiasGelu.apply(z, ff.intermediate_dense.bias), p_act)
+    return dropout(linear(a, w2, ff.output_dense.bias), p_hid)
+
+
+def post_ln_layer(layer, h: Tensor, attend, p_act: float, p_hid: float, eps: float) -> Tensor:
+    """Wav2Vec2EncoderLayer: h = LN(h + attend(h)); h = LN(h + ffn(h)) -- the adds ride in the LayerNorm launches."""
+    h = LayerNorm.apply(attend(h), h, layer.layer_norm.weight, layer.layer_norm.bias, eps)
+    return LayerNorm.apply(feed_forward(layer.feed_forward, h, p_act, p_hid), h, layer.final_layer_norm.weight, layer.final_layer_norm.bias, eps)
+
+
+def refuse_masking_and_unfrozen(enc, prefix: str) -> None:
+    """The two refusals every chain has, under the chain's own prefix: feature masking, and a conv feature extractor left trainable."""
+    cfg = enc.config
+    if float(getattr(cfg, "mask_feature_prob", 0.0)) > 0.0 and getattr(cfg, "apply_spec_augment", True):
+        raise NotImplementedError(f"{prefix}: mask_feature_prob > 0 is not supported")
+    unfrozen = [n for n, p in enc.feature_extractor.named_parameters() if p.requires_grad]
+    if unfrozen:
+        # the reference freezes the conv feature extractor in __init__ (compatibility.py:27-28) and never trains it; autograd WOULD train it
+        # if a user flipped requires_grad afterwards -- no chain has a backward for those convolutions, so say so instead of silently
+        # returning no gradient
+        raise NotImplementedError(f"{prefix}: the conv feature extractor is frozen (freeze_feature_encoder); "
+                                  f"{len(unfrozen)} of its parameters have requires_grad=True (first: feature_extractor.{unfrozen[0]})")
 
 
 TRAINABLE_MODEL_TYPES = ("wav2vec2", "wavlm", "hubert", "unispeech", "unispeech-sat", "data2vec-audio")
 
 
-def refuse_untrainable(adapt, mixed: bool) -> None:
-    """Raise NotImplementedError, by name, for a configuration this training path has no backward for (no device work: the WavLM adapter calls it
-    before its GPU check).  `mixed`: train_precision == "bf16"."""
+def refuse_untrainable(adapt, mixed: Optional[bool] = None) -> None:
+    """Raise NotImplementedError, by name, for a configuration this training path has no backward for (no device work: the adapter calls it
+    before its GPU check).  `mixed`: the precision mode to judge; left out (the adapter's call), it is `adapt.train_precision == "bf16"`, behind
+    the LoRA regime's refusals and WavLM's refusal of any other train_precision."""
     from .encoder import has_attn_adapters
     enc = adapt.original_encoder
     cfg = enc.config
     model_type = getattr(cfg, "model_type", "wav2vec2")
     wavlm = model_type == "wavlm"
+    if mixed is None:
+        refuse_untrainable_lora(adapt)
+        precision = getattr(adapt, "train_precision", "fp32")
+        if wavlm and precision != "bf16":
+            # f32 fine-tuning would need a materialised-probability path of its own
+            raise NotImplementedError(f"wavlm: fine-tuning with train_precision={precision!r} is not implemented (the gated relative-position "
+                                      'attention trains in mixed precision only); use train_precision="bf16", or the module in eval mode')
+        mixed = precision == "bf16"
     if wavlm and not (mixed and FUSED_ATTENTION):
         # the gated relative-position attention trains on the fused mixed-precision kernels only (csrc/wavlm_train.hip): there is no
         # materialised-probability WavLM path to fall back to
@@ -982,15 +1079,7 @@ def refuse_untrainable(adapt, mixed: bool) -> None:
             raise NotImplementedError(f"HIP fine-tuning path: adapter_attn_dim={cfg.adapter_attn_dim} trains adapter-only (the attention adapters and "
                                       f"the CTC head on a frozen base); {len(base)} base parameters have requires_grad=True (first: {base[0]}). "
                                       "Call HuggingFaceEncoderAdapt.adapter_finetuning() first")
-    if float(getattr(cfg, "mask_feature_prob", 0.0)) > 0.0 and getattr(cfg, "apply_spec_augment", True):
-        raise NotImplementedError("wav2vec2 HIP training path: mask_feature_prob > 0 is not supported")
-    unfrozen = [n for n, p in enc.feature_extractor.named_parameters() if p.requires_grad]
-    if unfrozen:
-        # the reference freezes the conv feature extractor in __init__ (compatibility.py:27-28) and never trains it; autograd WOULD train it
-        # if a user flipped requires_grad afterwards -- this path has no backward for those convolutions, so say so instead of silently
-        # returning no gradient
-        raise NotImplementedError("wav2vec2 HIP training path: the conv feature extractor is frozen (freeze_feature_encoder); "
-                                  f"{len(unfrozen)} of its parameters have requires_grad=True (first: feature_extractor.{unfrozen[0]})")
+    refuse_masking_and_unfrozen(enc, "wav2vec2 HIP training path")
 
 
 LORA_TARGETS = ("q_proj", "k_proj", "v_proj", "out_proj")
@@ -1034,26 +1123,19 @@ def _train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
     cfg = enc.config
     dev = audio.device
     wavlm = getattr(cfg, "model_type", "wav2vec2") == "wavlm"
-    plan = adapt._plan_frozen(dev)
-    with torch.no_grad():                                   # frozen conv feature extractor (compatibility.py:27-28): the inference kernels
-        feats = plan.feature_extractor(audio)
-    b, t, _ = feats.shape
+    h = frozen_features(adapt, audio)
+    t = h.shape[1]
     c, heads = int(cfg.hidden_size), int(cfg.num_attention_heads)
     eps = float(cfg.layer_norm_eps)
     fp, en = enc.feature_projection, enc.encoder
-    h = feats
-    if getattr(fp, "layer_norm", None) is not None:         # HubertFeatureProjection has none with feat_proj_layer_norm=False (hubert-base)
+    if getattr(fp, "layer_norm", None) is not None:        # HubertFeatureProjection has none with feat_proj_layer_norm=False (hubert-base)
         h = LayerNorm.apply(h, None, fp.layer_norm.weight, fp.layer_norm.bias, eps)
     h = linear(h, fp.projection.weight, fp.projection.bias)
     h = dropout(h, float(cfg.feat_proj_dropout))
     key_len = None
     if lengths is not None:
         key_len = feat_extract_output_lengths(cfg.conv_kernel, cfg.conv_stride, lengths.to(dev).long()).to(torch.int32).contiguous()
-    if getattr(cfg, "apply_spec_augment", True) and float(cfg.mask_time_prob) > 0.0:
-        m = compute_mask_indices(b, t, float(cfg.mask_time_prob), int(cfg.mask_time_length), None if key_len is None else key_len.tolist(),
-                                 int(getattr(cfg, "mask_time_min_masks", 2)))
-        if m.any():
-            h = MaskEmbed.apply(h, torch.from_numpy(m.astype(np.uint8)).to(dev), enc.masked_spec_embed)
+    h = mask_time(enc, h, key_len)
     if key_len is not None:
         h = MaskRows.apply(h, key_len)
     g = int(cfg.num_conv_pos_embedding_groups)
@@ -1071,16 +1153,9 @@ def _train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
             p = PosConvStackLayer.apply(p, wk, pl.conv.bias)
         h = LayerNorm.apply(p, h, en.layer_norm.weight, en.layer_norm.bias, eps)
     else:
-        # positional conv: weight norm over dim 2 on the parameters (torch ops on [C][C/g][k] only), conv + GELU + residual on the kernels
+        # positional conv: the weight norm on the parameters, conv + GELU + residual on the kernels
         conv = en.pos_conv_embed.conv
-        if hasattr(conv, "parametrizations"):
-            wg, wv = conv.parametrizations.weight.original0, conv.parametrizations.weight.original1
-        else:
-            wg, wv = conv.weight_g, conv.weight_v
-        kpos = int(cfg.num_conv_pos_embeddings)
-        w_eff = wg * wv / wv.pow(2).sum(dim=(0, 1), keepdim=True).sqrt()
-        wk = w_eff.view(g, c // g, c // g, kpos).permute(3, 0, 1, 2).contiguous()
-        h = PosConvGelu.apply(h, wk, conv.bias)
+        h = PosConvGelu.apply(h, weight_normed_taps(conv, g), conv.bias)
         if not stable:
             h = LayerNorm.apply(h, None, en.layer_norm.weight, en.layer_norm.bias, eps)
     h = dropout(h, p_hid)
@@ -1095,10 +1170,8 @@ def _train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
         # LayerDrop: transformers draws torch.rand([]) per layer in training; WavLMEncoder never skips layer 0 (it owns the position bias)
         if torch.rand([]).item() < float(cfg.layerdrop) and not (wavlm and i == 0):
             continue
-        att, ff = layer.attention, layer.feed_forward
-        wqkv = torch.cat([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight], 0)
-        bqkv = torch.cat([att.q_proj.bias, att.k_proj.bias, att.v_proj.bias], 0)
-
+        att = layer.attention
+        wqkv, bqkv = stacked_qkv(att)
         lo = lora.layers[i] if lora is not None else {}            # this layer's LoRA targets: {projection name: {lora_A, lora_B}}
 
         def project(x, w, b, names):
@@ -1118,23 +1191,15 @@ def _train_forward(adapt, audio: Tensor, lengths: Optional[Tensor]) -> Tensor:
                 ctxt = attention(qkv, key_len, heads, p_att, seed)
             return dropout(project(ctxt, att.out_proj.weight, att.out_proj.bias, ("out_proj",)), p_hid)
 
-        def ffn(x):
-            z = linear(x, ff.intermediate_dense.weight, None)
-            w2 = ff.output_dense.weight
-            if _MIXED and FUSED_FFN_ACT and FFNActLinear.supported(w2.shape[1], w2.shape[0]):
-                return dropout(FFNActLinear.apply(z, ff.intermediate_dense.bias, w2, ff.output_dense.bias, p_act, next_seed() if p_act > 0 else 0), p_hid)
-            a = dropout(BiasGelu.apply(z, ff.intermediate_dense.bias), p_act)
-            return dropout(linear(a, w2, ff.output_dense.bias), p_hid)
-
         if stable:                                                  # pre-LN: h += attn(LN(h)); h += ffn(LN(h))
             h = Add.apply(h, attend(LayerNorm.apply(h, None, layer.layer_norm.weight, layer.layer_norm.bias, eps)))
-            h = Add.apply(h, ffn(LayerNorm.apply(h, None, layer.final_layer_norm.weight, layer.final_layer_norm.bias, eps)))
+            h = Add.apply(h, feed_forward(layer.feed_forward, LayerNorm.apply(h, None, layer.final_layer_norm.weight, layer.final_layer_norm.bias, eps),
+                                          p_act, p_hid))
             ad = getattr(layer, "adapter_layer", None)
             if ad is not None:                                      # MMS: h += adapter_layer(h), skipped by LayerDrop with the rest of the layer
                 h = AttnAdapter.apply(h, ad.norm.weight, ad.norm.bias, ad.linear_1.weight, ad.linear_1.bias, ad.linear_2.weight, ad.linear_2.bias)
-        else:                                                       # post-LN: h = LN(h + attn(h)); h = LN(h + ffn(h))
-            h = LayerNorm.apply(attend(h), h, layer.layer_norm.weight, layer.layer_norm.bias, eps)
-            h = LayerNorm.apply(ffn(h), h, layer.final_layer_norm.weight, layer.final_layer_norm.bias, eps)
+        else:
+            h = post_ln_layer(layer, h, attend, p_act, p_hid, eps)
     if stable:
         h = LayerNorm.apply(h, None, en.layer_norm.weight, en.layer_norm.bias, eps)
     return h

@@ -112,9 +112,7 @@ def time_stack(a, t, c, groups=16, k=19, n=5, reps=10):
         p.backward(dy)
 
     best = float("inf")
-    old = T._MIXED
-    T._MIXED = True
-    try:
+    with T.mixed_precision(True):
         once()
         for _ in range(3):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -123,8 +121,6 @@ def time_stack(a, t, c, groups=16, k=19, n=5, reps=10):
                 once()
             e1.record(); torch.cuda.synchronize()
             best = min(best, e0.elapsed_time(e1) / reps)
-    finally:
-        T._MIXED = old
     return best
 
 
