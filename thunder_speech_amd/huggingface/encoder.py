@@ -180,18 +180,54 @@ def _check_config(cfg) -> None:
         raise NotImplementedError("wav2vec2 HIP path: unsupported configuration: " + ", ".join(bad))
 
 
+# precision="mxfp8": the families that run on Wav2Vec2Plan's own layer loops (pre-LN and post-LN, any head_dim the bf16 mode takes)
+MXFP8_MODEL_TYPES = ("wav2vec2", "hubert", "unispeech", "unispeech-sat", "data2vec-audio")
+
+
+def check_mxfp8_config(cfg) -> None:
+    """Whether precision="mxfp8" runs this configuration; NotImplementedError naming the reason otherwise.  No device work: callable without a GPU."""
+    mt = getattr(cfg, "model_type", "wav2vec2")
+    bad = []
+    if mt == "wavlm":
+        bad.append("model_type='wavlm' (its gate reads the bf16 rows of the attention's input, which the mode does not keep)")
+    elif mt not in MXFP8_MODEL_TYPES:
+        bad.append(f"model_type={mt!r} (the MX products exist for the layers of {', '.join(MXFP8_MODEL_TYPES)})")
+    if has_attn_adapters(cfg):
+        bad.append(f"adapter_attn_dim={cfg.adapter_attn_dim} (the MMS attention adapters multiply bf16 rows)")
+    for name in ("hidden_size", "intermediate_size"):
+        if int(getattr(cfg, name)) % 128:
+            bad.append(f"{name}={int(getattr(cfg, name))} (the MX product contracts in steps of 128; every published checkpoint of the families in "
+                       "scope is a multiple)")
+    if bad:
+        raise NotImplementedError("precision='mxfp8': unsupported configuration: " + ", ".join(bad))
+
+
+class MxWeight:
+    """A weight [n][k] as the packed MX operand ts_mx_gemm_nt loads (ts_mx_pack_w): element fragments and scale fragments."""
+    __slots__ = ("frag", "sfrag", "shape")
+
+    def __init__(self, frag, sfrag, n, k):
+        self.frag, self.sfrag, self.shape = frag, sfrag, (n, k)
+
+
 class Wav2Vec2Plan:
     """Packed weights + launch sequence for one set of encoder weights (HF state-dict keys, see oracle/w2v.py).
     precision "fp32": every GEMM in fp32; "bf16": GEMM operands in bf16 (fp32 accumulation, fp32 residual stream /
-    normalisations / softmax) -- each launch also writes the bf16 copy its consumer multiplies with."""
+    normalisations / softmax) -- each launch also writes the bf16 copy its consumer multiplies with; "mxfp8": "bf16" with the four products
+    of every transformer layer (q / k / v, out_proj, the two feed-forward linears) on MX operands -- e4m3 elements, one e8m0 scale per 32
+    consecutive K elements, f32 accumulation (csrc/mxfp8.hip) -- an opt-in mode with an accuracy cost (profiles/mxfp8_forward.md)."""
 
     def __init__(self, cfg, sd: Dict[str, torch.Tensor], device, precision: str = "bf16", feature_extractor_only: bool = False):
         """`feature_extractor_only`: pack the conv feature extractor's weights and nothing else -- the plan of the training path's frozen
         front (huggingface/train.py); `forward` is then unavailable, `feature_extractor` works."""
         _check_config(cfg)
-        if precision not in ("fp32", "bf16"):
-            raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r}")
-        self.prec = 1 if precision == "bf16" else 0
+        if precision not in ("fp32", "bf16", "mxfp8"):
+            raise ValueError(f"precision must be 'fp32', 'bf16' or 'mxfp8', got {precision!r}")
+        # a plan of the feature extractor alone runs "mxfp8" as "bf16"; the plans built on this class (conformer, SEW) hold layers of their own
+        if precision == "mxfp8" and (not feature_extractor_only or type(self) is not Wav2Vec2Plan):
+            check_mxfp8_config(cfg)
+        self.prec = 0 if precision == "fp32" else 1
+        self.mx = precision == "mxfp8" and not feature_extractor_only
         f = lambda k: sd[k].detach().to(device=device, dtype=torch.float32).contiguous()
         gw = (lambda t: t.to(torch.bfloat16).contiguous()) if self.prec else (lambda t: t.contiguous())     # GEMM operand
         self.device = torch.device(device)
@@ -250,7 +286,11 @@ class Wav2Vec2Plan:
         self._pack_adapter(cfg, sd, f)
         for i in range(self.n_layers):
             q = f"encoder.layers.{i}."
-            self.layers.append(self._pack_layer(f, gw, q))
+            self.layers.append(self._pack_layer(f, (lambda t: t.contiguous()) if self.mx else gw, q))
+            if self.mx:
+                # the four products' weights: quantised from f32 and packed once; no bf16 copy is kept
+                for name in ("wqkv", "wo", "w1", "w2"):
+                    self.layers[-1][name] = self._mx_pack(self.layers[-1][name])
             if q + "adapter_layer.linear_1.weight" in sd:
                 # Wav2Vec2AttnAdapterLayer (MMS): LayerNorm (eps 1e-5) -> linear_1 [a][c] -> ReLU -> linear_2 [c][a], added to the residual stream
                 self.attn_adapter_keys += [q + "adapter_layer." + k for k in ("norm.weight", "norm.bias", "linear_1.weight", "linear_1.bias",
@@ -343,6 +383,8 @@ class Wav2Vec2Plan:
     def _linear(self, L, stream, x_op, w, bias, act=0, want_op=False, res=None, into=None):
         """want_op: the consumer is another GEMM -- in bf16 mode only the bf16 copy is kept (the fp32 buffer is scratch).
         into: fp32 tensor the product is accumulated into in place (the residual stream; beta = 1 inside the GEMM)."""
+        if isinstance(w, MxWeight):
+            return self._mx_linear(L, stream, x_op, w, bias, act, want_op, into)
         b, t, k = x_op.shape
         n = w.shape[0]
         y = into if into is not None else self._buf(b, t, n)
@@ -353,8 +395,58 @@ class Wav2Vec2Plan:
         _lib.check(st, "ts_w2v_linear_fwd")
         return y, (y_op if self.prec else y)
 
-    def _ln(self, L, stream, x, wb, res=None, xbias=None, want_op=True, act=0, eps=None, want_f32=True):
-        """want_f32=False (bf16 mode only): the f32 result has no reader -- only the GEMM-operand copy is written."""
+    # ---- precision="mxfp8": an MX operand is the pair (elements uint8 [b][t][k], scales uint8 [b][t][k / 32]) ----------------------------
+    def _mx_pack(self, w: torch.Tensor) -> MxWeight:
+        """f32 weight [n][k] on the device -> its packed MX operand (quantiser, then the permutation of ts_mx_pack_w)."""
+        L = _lib.lib()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        n, k = w.shape
+        q, s = self._buf(n, k, dtype=torch.uint8), self._buf(n, k // 32, dtype=torch.uint8)
+        _lib.check(L.ts_mx_quantize_rows(w.data_ptr(), 0, k, n, k, q.data_ptr(), k, s.data_ptr(), k // 32, stream), "ts_mx_quantize_rows")
+        frag, sfrag = self._buf(n * k, dtype=torch.uint8), self._buf(int(L.ts_mx_pack_w_scale_bytes(n, k)), dtype=torch.uint8)
+        _lib.check(L.ts_mx_pack_w(q.data_ptr(), k, s.data_ptr(), k // 32, n, k, frag.data_ptr(), sfrag.data_ptr(), stream), "ts_mx_pack_w")
+        return MxWeight(frag, sfrag, n, k)
+
+    def _mx_linear(self, L, stream, x_op, w: MxWeight, bias, act, want_op, into):
+        """_linear on MX operands.  x_op: an MX operand, or bf16 rows (the attention context), which are quantised first.  into: accumulated in
+        place (f32 residual stream); act=1 with want_op: GELU, result as the next product's MX operand; else bias -> bf16 rows."""
+        n, k = w.shape
+        if isinstance(x_op, torch.Tensor):
+            b, t, _ = x_op.shape
+            xq, xs = self._buf(b, t, k, dtype=torch.uint8), self._buf(b, t, k // 32, dtype=torch.uint8)
+            _lib.check(L.ts_mx_quantize_rows(x_op.data_ptr(), 1, k, b * t, k, xq.data_ptr(), k, xs.data_ptr(), k // 32, stream), "ts_mx_quantize_rows")
+        else:
+            xq, xs = x_op
+            b, t, _ = xq.shape
+        y = y16 = yq = ys = None
+        if into is not None:
+            ep, y, out = _lib.STAGED["mxfp8"].defines["TS_MX_EP_ACCUM"], into, None
+        elif act == 1 and want_op:
+            yq, ys = self._buf(b, t, n, dtype=torch.uint8), self._buf(b, t, n // 32, dtype=torch.uint8)
+            ep, out = _lib.STAGED["mxfp8"].defines["TS_MX_EP_GELU_MX"], (yq, ys)
+        elif act == 0 and want_op:
+            y16 = self._buf(b, t, n, dtype=torch.bfloat16)
+            ep, out = _lib.STAGED["mxfp8"].defines["TS_MX_EP_BF16"], y16
+        else:
+            raise NotImplementedError("precision='mxfp8': this product has no MX epilogue")
+        _lib.check(L.ts_mx_gemm_nt(xq.data_ptr(), k, xs.data_ptr(), k // 32, w.frag.data_ptr(), w.sfrag.data_ptr(), self._ptr(bias), ep,
+                                   self._ptr(y), n, self._ptr(y16), n, self._ptr(yq), n, self._ptr(ys), n // 32, b * t, n, k, stream), "ts_mx_gemm_nt")
+        return y, out
+
+    def _mx_ln(self, L, stream, x, wb, res, xbias, want_f32):
+        """_ln with the result as an MX operand (and f32 when `want_f32`)."""
+        b, t, c = x.shape
+        q, s = self._buf(b, t, c, dtype=torch.uint8), self._buf(b, t, c // 32, dtype=torch.uint8)
+        y = torch.empty_like(x) if want_f32 else None
+        _lib.check(L.ts_mx_layernorm_fwd(x.data_ptr(), self._ptr(res), self._ptr(xbias), wb[0].data_ptr(), wb[1].data_ptr(), self.eps, b * t, c,
+                                         self._ptr(y), q.data_ptr(), c, s.data_ptr(), c // 32, stream), "ts_mx_layernorm_fwd")
+        return y, (q, s)
+
+    def _ln(self, L, stream, x, wb, res=None, xbias=None, want_op=True, act=0, eps=None, want_f32=True, mx=False):
+        """want_f32=False (bf16 mode only): the f32 result has no reader -- only the GEMM-operand copy is written.
+        mx (precision="mxfp8": the LayerNorms in front of a layer product): the operand copy is an MX operand."""
+        if mx:
+            return self._mx_ln(L, stream, x, wb, res, xbias, want_f32)
         y_op = self._op(*x.shape) if want_op else None
         y = torch.empty_like(x) if (want_f32 or y_op is None) else None
         st = L.ts_w2v_layernorm_fwd(x.data_ptr(), self._ptr(res), self._ptr(xbias), wb[0].data_ptr(), wb[1].data_ptr(),
@@ -467,9 +559,9 @@ class Wav2Vec2Plan:
             y, x_op = None, None                        # LN(h) for what comes next, when the previous layer's adapter launch computed it
             for i, lw in enumerate(self.layers):
                 if x_op is None:
-                    _, x_op = self._ln(L, stream, h, lw["ln1"], want_f32=False)
+                    _, x_op = self._ln(L, stream, h, lw["ln1"], want_f32=False, mx=self.mx)
                 self._linear(L, stream, attention(x_op, lw), lw["wo"], lw["bo"], into=h)        # h += attn W^T (+ bias in the epilogue)
-                _, x_op = self._ln(L, stream, h, lw["ln2"], want_f32=False)
+                _, x_op = self._ln(L, stream, h, lw["ln2"], want_f32=False, mx=self.mx)
                 _, f1_op = self._linear(L, stream, x_op, lw["w1"], lw["b1"], act=1, want_op=True)
                 self._linear(L, stream, f1_op, lw["w2"], lw["b2"], into=h)
                 x_op = None
@@ -522,14 +614,14 @@ class Wav2Vec2Plan:
     def _post_ln_layers(self, L, stream, hp, pos_res, attention):
         """The post-LN family's chain (wav2vec2-base, hubert, data2vec-audio, wavlm-base, SEW at its squeezed frame rate): encoder.layer_norm over
         hp (+ pos_res) before the layers, a LayerNorm after each residual add inside them.  -> (f32 result, its GEMM-operand copy)."""
-        h, h_op = self._ln(L, stream, hp, self.enc_ln, res=pos_res)
+        h, h_op = self._ln(L, stream, hp, self.enc_ln, res=pos_res, mx=self.mx)
         for lw in self.layers:
             # the projections accumulate into the residual stream inside the GEMM; their biases ride in the LayerNorm launch
             self._linear(L, stream, attention(h_op, lw), lw["wo"], None, into=h)
-            h, h_op = self._ln(L, stream, h, lw["ln1"], xbias=lw["bo"])
+            h, h_op = self._ln(L, stream, h, lw["ln1"], xbias=lw["bo"], mx=self.mx)
             _, f1_op = self._linear(L, stream, h_op, lw["w1"], lw["b1"], act=1, want_op=True)
             self._linear(L, stream, f1_op, lw["w2"], None, into=h)
-            h, h_op = self._ln(L, stream, h, lw["ln2"], xbias=lw["b2"])
+            h, h_op = self._ln(L, stream, h, lw["ln2"], xbias=lw["b2"], mx=self.mx)
         return h, h_op
 
     def _adapter(self, L, stream, h: torch.Tensor) -> torch.Tensor:
@@ -581,10 +673,30 @@ class HuggingFaceEncoderAdapt(nn.Module):
         self.mask_input = mask_input
         self._cache = _PackedCache()
         _check_config(encoder.config)
+        if precision == "mxfp8":
+            check_mxfp8_config(encoder.config)
+
+    @property
+    def precision(self) -> str:
+        """"fp32", "bf16" or "mxfp8" (Wav2Vec2Plan).  Assigning another value on a loaded module re-packs the plan on the next forward and, through
+        `_param_epoch` (BaseCTCModule._weights_stamp), retires the inference graphs captured with the old one."""
+        d = self.__dict__
+        return d["_precision"] if "_precision" in d else d["precision"]      # "precision": an adapter unpickled from before this was a property
+
+    @precision.setter
+    def precision(self, value: str) -> None:
+        if value != self.__dict__.get("_precision"):
+            self.__dict__["_precision"] = value
+            self.__dict__["_param_epoch"] = self.__dict__.get("_param_epoch", 0) + 1
 
     def _plan(self, device) -> Wav2Vec2Plan:
         params = list(self.original_encoder.parameters())
         cfg = self.original_encoder.config
+        if self.precision == "mxfp8":
+            check_mxfp8_config(cfg)                  # by name, before any plan of another family is built
+        if getattr(self, "_cache_precision", None) != self.precision:
+            # the precision is part of the cache key: flipping `encoder.precision` on a loaded module re-packs the weights
+            self._cache, self._cache_precision = _PackedCache(), self.precision
         if getattr(cfg, "model_type", "wav2vec2") == "wav2vec2-conformer":
             from .conformer import ConformerPlan
             # the plan folds running_mean / running_var into bn_scale / bn_shift: a train-mode forward changes those buffers without touching a
@@ -700,8 +812,8 @@ class HuggingFaceEncoderAdapt(nn.Module):
         only, so an optimizer step on the transformer re-packs nothing and no transformer weight gets a device copy it never uses.  It runs
         at `self.precision` -- with the default "bf16" the FROZEN convolutions multiply bf16 operands (f32 accumulation) while everything
         trainable behind them is f32; pass precision="fp32" for f32 arithmetic throughout (what the parity tests use)."""
-        if not hasattr(self, "_fe_cache"):
-            self._fe_cache = _PackedCache()
+        if not hasattr(self, "_fe_cache") or getattr(self, "_fe_cache_precision", None) != self.precision:
+            self._fe_cache, self._fe_cache_precision = _PackedCache(), self.precision        # keyed on the precision, as `_plan`'s cache
         fe = self.original_encoder.feature_extractor
         params = list(fe.parameters())
         sd = {"feature_extractor." + k: v for k, v in fe.state_dict().items()}
