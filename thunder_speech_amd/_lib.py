@@ -1,6 +1,7 @@
 """ctypes binding of the C ABI: the core header include/thunder_speech_amd.h and its companions, one header per feature in
 include/thunder_speech_amd/, each versioned on its own (COMPANIONS, keyed by the header's file name without ".h"), and the staged companions in
-include_staged/thunder_speech_amd/ (STAGED, keyed the same way): headers of the same kind that wait for their place in include/.
+include_staged/thunder_speech_amd/ (STAGED, keyed the same way): headers of the same kind that wait for their place in include/, and those one
+level further down in include_staged/thunder_speech_amd/queued/ (QUEUED), which wait behind them.
 
 The headers are the only copy of the ABI: `read_header` derives every prototype, struct and TS_* constant from them and `lib()` applies the
 result, so a new entry point needs the header and its .hip definition and nothing here -- and a new companion needs its header in that directory
@@ -22,6 +23,7 @@ from .build import ROOT, lib_path
 HEADER = os.path.join(ROOT, "include", "thunder_speech_amd.h")
 COMPANION_DIR = os.path.join(ROOT, "include", "thunder_speech_amd")
 STAGED_DIR = os.path.join(ROOT, "include_staged", "thunder_speech_amd")
+QUEUED_DIR = os.path.join(STAGED_DIR, "queued")
 
 # Parameters and struct fields: these scalars, `[const] <struct>*` as POINTER(struct), every other pointer to one of
 # _POINTEES (const or not, any depth) as c_void_p.  Return types: _RETURNS only.
@@ -105,8 +107,10 @@ SIGNATURES, STRUCTS, DEFINES = CORE.signatures, CORE.structs, CORE.defines
 COMPANIONS = {os.path.basename(p)[:-len(".h")]: _read_installed_header(p) for p in sorted(glob.glob(os.path.join(COMPANION_DIR, "*.h")))}
 # staged companions: read, applied and checked exactly as the companions are, in a table of their own
 STAGED = {os.path.basename(p)[:-len(".h")]: _read_installed_header(p) for p in sorted(glob.glob(os.path.join(STAGED_DIR, "*.h")))}
+# queued companions: the same again, for headers that arrived while the staged set was pinned too
+QUEUED = {os.path.basename(p)[:-len(".h")]: _read_installed_header(p) for p in sorted(glob.glob(os.path.join(QUEUED_DIR, "*.h")))}
 _declared_in = {}
-for _h in (CORE, *COMPANIONS.values(), *STAGED.values()):
+for _h in (CORE, *COMPANIONS.values(), *STAGED.values(), *QUEUED.values()):
     for _name in _h.signatures:
         if _name in _declared_in:
             raise RuntimeError(f"thunder_speech_amd: {_name} is declared by two headers, {_declared_in[_name]} and {_h.path}")
@@ -140,7 +144,7 @@ def lib() -> C.CDLL:
             "`python -m thunder_speech_amd.build` (needs hipcc / ROCm); there is no CPU fallback.")
     import torch  # noqa: F401  -- must initialise its bundled HIP runtime BEFORE our code object is loaded
     L = C.CDLL(path)
-    headers = (CORE, *COMPANIONS.values(), *STAGED.values())
+    headers = (CORE, *COMPANIONS.values(), *STAGED.values(), *QUEUED.values())
     missing = [name for h in headers for name in h.signatures if not hasattr(L, name)]
     if missing:
         raise RuntimeError(f"thunder_speech_amd: {path} does not export {missing}; rebuild it")

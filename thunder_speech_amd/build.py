@@ -31,10 +31,11 @@ def sources():
 
 
 def header_deps():
-    """Every header of the C ABI: the core header in include/, its companions in include/thunder_speech_amd/ and the staged companions in
-    include_staged/thunder_speech_amd/ (headers waiting for their place in include/: _lib.STAGED)."""
+    """Every header of the C ABI: the core header in include/, its companions in include/thunder_speech_amd/, the staged companions in
+    include_staged/thunder_speech_amd/ (headers waiting for their place in include/: _lib.STAGED) and the queued ones below them (_lib.QUEUED)."""
     return (glob.glob(os.path.join(ROOT, "include", "*.h")) + glob.glob(os.path.join(ROOT, "include", "thunder_speech_amd", "*.h"))
-            + glob.glob(os.path.join(ROOT, "include_staged", "thunder_speech_amd", "*.h")))
+            + glob.glob(os.path.join(ROOT, "include_staged", "thunder_speech_amd", "*.h"))
+            + glob.glob(os.path.join(ROOT, "include_staged", "thunder_speech_amd", "queued", "*.h")))
 
 
 def common_flags():

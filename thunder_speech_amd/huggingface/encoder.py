@@ -27,7 +27,7 @@ from torch import nn
 from .. import _lib, tensors as _t
 from ..blocks import _PackedCache
 
-__all__ = ["Wav2Vec2Plan", "HuggingFaceEncoderAdapt", "feat_extract_output_lengths", "relative_position_bucket", "wavlm_bucket_table"]
+__all__ = ["Wav2Vec2Plan", "HuggingFaceEncoderAdapt", "LoraBank", "feat_extract_output_lengths", "relative_position_bucket", "wavlm_bucket_table"]
 
 
 def feat_extract_output_lengths(conv_kernel, conv_stride, lengths: torch.Tensor, adapter_layers: int = 0, adapter_stride: int = 2) -> torch.Tensor:
@@ -287,6 +287,7 @@ class Wav2Vec2Plan:
         for i in range(self.n_layers):
             q = f"encoder.layers.{i}."
             self.layers.append(self._pack_layer(f, (lambda t: t.contiguous()) if self.mx else gw, q))
+            self.layers[-1]["index"] = i                 # the layer's row of a LoRA bank (self.bank)
             if self.mx:
                 # the four products' weights: quantised from f32 and packed once; no bf16 copy is kept
                 for name in ("wqkv", "wo", "w1", "w2"):
@@ -367,6 +368,29 @@ class Wav2Vec2Plan:
                     _lib.check(st, "ts_gemm_nt_pack_w")
             cache[key] = (out, w)            # holds w so that the key stays unique
         return cache[key][0]
+
+    # ---- a bank of LoRA adaptations (HuggingFaceEncoderAdapt.lora_bank): None, or the LoraBank whose terms follow the attention projections -----
+    bank = None
+
+    def _bank_term(self, L, stream, lw, x_op, y, out: bool) -> None:
+        """Behind a base product of layer `lw`: y's rows of every clip += the low-rank terms of the slot that clip's id names (one
+        ts_lora_bank_fwd; clips with id -1 keep their bits).  out=False: the banked targets among q | k | v on the stacked result y [b][t][3c]
+        (the GEMM operand: bf16 in bf16 mode), x_op what the stacked product read; out=True: out_proj on the f32 residual stream y [b][t][c],
+        x_op the attention context.  Without a bank, or without a banked target of that kind, no launch."""
+        bank = self.bank
+        if bank is None:
+            return
+        targets = tuple(n for n in bank.targets if (n == "out_proj") == out)
+        if not targets:
+            return
+        b, t, c = x_op.shape
+        a_bank, b_bank = (bank.a_out, bank.b_out) if out else (bank.a_qkv, bank.b_qkv)
+        cols = [0] if out else [c * ("q_proj", "k_proj", "v_proj").index(n) for n in targets]
+        cols += [-1] * (3 - len(cols))
+        i = lw["index"]
+        _lib.check(L.ts_lora_bank_fwd(x_op.data_ptr(), self.prec, c, b, t, c, a_bank[i].data_ptr(), b_bank[i].data_ptr(), bank.scales.data_ptr(),
+                                      bank.capacity, len(targets), c, bank.rank, bank.ids.data_ptr(), y.data_ptr(),
+                                      0 if out else self.prec, y.shape[-1], cols[0], cols[1], cols[2], stream), "ts_lora_bank_fwd")
 
     # ---- launch helpers: every helper returns (fp32 result, GEMM operand for the next stage) ------------------------
     def _buf(self, *shape, dtype=torch.float32):
@@ -560,7 +584,9 @@ class Wav2Vec2Plan:
             for i, lw in enumerate(self.layers):
                 if x_op is None:
                     _, x_op = self._ln(L, stream, h, lw["ln1"], want_f32=False, mx=self.mx)
-                self._linear(L, stream, attention(x_op, lw), lw["wo"], lw["bo"], into=h)        # h += attn W^T (+ bias in the epilogue)
+                ctx_op = attention(x_op, lw)
+                self._linear(L, stream, ctx_op, lw["wo"], lw["bo"], into=h)                     # h += attn W^T (+ bias in the epilogue)
+                self._bank_term(L, stream, lw, ctx_op, h, out=True)
                 _, x_op = self._ln(L, stream, h, lw["ln2"], want_f32=False, mx=self.mx)
                 _, f1_op = self._linear(L, stream, x_op, lw["w1"], lw["b1"], act=1, want_op=True)
                 self._linear(L, stream, f1_op, lw["w2"], lw["b2"], into=h)
@@ -594,6 +620,7 @@ class Wav2Vec2Plan:
         def attention(x_op, lw):
             # x_op: the attention's input as the QKV GEMM reads it -- WavLM's gate is computed from the same rows; lw: the layer's weights
             _, qkv_op = self._linear(L, stream, x_op, lw["wqkv"], lw["bqkv"], want_op=True)
+            self._bank_term(L, stream, lw, x_op, qkv_op, out=False)
             ctx_op = self._buf(b, t, c, dtype=torch.bfloat16 if self.prec else torch.float32)
             if self.wavlm:
                 _lib.check(L.ts_wavlm_attention_fwd(qkv_op.data_ptr(), b, t, c, self.heads, self._ptr(key_len), self.prec, x_op.data_ptr(), c,
@@ -617,7 +644,9 @@ class Wav2Vec2Plan:
         h, h_op = self._ln(L, stream, hp, self.enc_ln, res=pos_res, mx=self.mx)
         for lw in self.layers:
             # the projections accumulate into the residual stream inside the GEMM; their biases ride in the LayerNorm launch
-            self._linear(L, stream, attention(h_op, lw), lw["wo"], None, into=h)
+            ctx_op = attention(h_op, lw)
+            self._linear(L, stream, ctx_op, lw["wo"], None, into=h)
+            self._bank_term(L, stream, lw, ctx_op, h, out=True)
             h, h_op = self._ln(L, stream, h, lw["ln1"], xbias=lw["bo"], mx=self.mx)
             _, f1_op = self._linear(L, stream, h_op, lw["w1"], lw["b1"], act=1, want_op=True)
             self._linear(L, stream, f1_op, lw["w2"], None, into=h)
@@ -648,6 +677,62 @@ class Wav2Vec2Plan:
             _lib.check(L.ts_w2v_glu_fwd(y.data_ptr(), b * t_out, c, h.data_ptr(), None, stream), "ts_w2v_glu_fwd")
             t = t_out
         return h
+
+
+LORA_BANK_MAX_CLIPS = 4096         # entries of a bank's id buffer: the largest batch a forward with a bank takes
+
+
+class LoraBank:
+    """The tensors of HuggingFaceEncoderAdapt.lora_bank(): `capacity` slots of LoRA pairs for every layer and target, next to one frozen base
+    (include_staged/thunder_speech_amd/queued/lora_bank.h).  Plain tensors at fixed addresses: adding, removing and selecting write in place, so a
+    captured graph that read them keeps serving.  a_qkv [layers][capacity][targets among q, k, v][rank][c], b_qkv [...][c][rank], a_out / b_out the
+    same with one target (out_proj); `dtype` is the GEMM operands' (bf16 under precision="bf16", f32 under "fp32"); scales f32 [capacity]
+    (alpha / rank per slot); ids int32 [LORA_BANK_MAX_CLIPS]: the slot of clip b, -1 = the base alone."""
+
+    def __init__(self, n_layers: int, hidden: int, rank: int, alpha_default: float, targets, capacity: int, precision: str, device):
+        self.n_layers, self.hidden, self.rank, self.alpha_default, self.targets, self.capacity = n_layers, hidden, rank, alpha_default, targets, capacity
+        self.precision = precision
+        self.dtype = torch.float32 if precision == "fp32" else torch.bfloat16
+        self.qkv_targets = tuple(t for t in targets if t != "out_proj")
+        self.has_out = "out_proj" in targets
+        z = lambda *shape: torch.zeros(*shape, dtype=self.dtype, device=device)
+        nq = len(self.qkv_targets)
+        self.a_qkv = z(n_layers, capacity, nq, rank, hidden) if nq else None
+        self.b_qkv = z(n_layers, capacity, nq, hidden, rank) if nq else None
+        self.a_out = z(n_layers, capacity, 1, rank, hidden) if self.has_out else None
+        self.b_out = z(n_layers, capacity, 1, hidden, rank) if self.has_out else None
+        self.scales = torch.zeros(capacity, dtype=torch.float32, device=device)
+        self.ids = torch.full((LORA_BANK_MAX_CLIPS,), -1, dtype=torch.int32, device=device)
+        self.names = [None] * capacity                   # slot -> name
+        self.selection = []                              # what select_adapters() was last given: a name or None per clip
+
+    _TENSORS = ("a_qkv", "b_qkv", "a_out", "b_out", "scales", "ids")
+
+    @property
+    def device(self):
+        return self.ids.device
+
+    def to(self, device) -> None:
+        """Move the tensors (new addresses: the caller retires the graphs captured on the old ones)."""
+        for name in self._TENSORS:
+            if getattr(self, name) is not None:
+                setattr(self, name, getattr(self, name).to(device))
+
+    def pair(self, layer: int, slot: int, target: str):
+        """(A [rank][c], B [c][rank]): views into the bank's tensors."""
+        if target == "out_proj":
+            return self.a_out[layer, slot, 0], self.b_out[layer, slot, 0]
+        j = self.qkv_targets.index(target)
+        return self.a_qkv[layer, slot, j], self.b_qkv[layer, slot, j]
+
+    def write_ids(self) -> None:
+        """The id buffer from `selection`: the slots of the given clips, -1 for a None and for every entry beyond them.  One host-to-device copy at
+        a fixed address."""
+        host = torch.full((LORA_BANK_MAX_CLIPS,), -1, dtype=torch.int32)
+        for i, name in enumerate(self.selection):
+            if name is not None:
+                host[i] = self.names.index(name)
+        self.ids.copy_(host)
 
 
 class HuggingFaceEncoderAdapt(nn.Module):
@@ -747,6 +832,9 @@ class HuggingFaceEncoderAdapt(nn.Module):
         from .train import LORA_RANKS, LORA_TARGETS, refuse_lora
         if getattr(self, "lora", None) is not None:
             raise RuntimeError("lora_finetuning: this encoder already carries LoRA parameters (merge_lora() folds them into the base)")
+        if getattr(self, "_lora_bank", None) is not None:
+            raise RuntimeError("lora_finetuning: this encoder serves a LoRA bank (lora_bank); fine-tune on a copy without one and add the "
+                               "result with lora_bank_add()")
         if isinstance(rank, bool) or not isinstance(rank, int) or rank not in LORA_RANKS:
             raise ValueError(f"lora_finetuning: rank must be one of {LORA_RANKS} (the low-rank kernels' widths), got {rank!r}")
         targets = (targets,) if isinstance(targets, str) else tuple(targets)
@@ -807,6 +895,143 @@ class HuggingFaceEncoderAdapt(nn.Module):
             for n, p in mine.items():
                 p.copy_(sd[n])
 
+    # ------------------------------------------------------------------------------------------------------------------
+    # Serving many adaptations on one base (no reference counterpart): a bank of LoRA pairs next to the frozen, packed base; every clip of a batch
+    # picks its pair by name.  Eval mode then runs the base products as they are and adds each clip's low-rank term behind them
+    # (Wav2Vec2Plan._bank_term, csrc/lora_bank.hip) with the arithmetic of the training forward -- not the merged weight of `_plan` above, which
+    # serves one adaptation per packed copy of the base.  The bank's tensors are plain attributes (no Parameters, no buffers: state_dict() does
+    # not change); adding, removing and selecting write at fixed addresses, so captured graphs keep replaying.
+    def _bank(self, what: str) -> LoraBank:
+        bank = getattr(self, "_lora_bank", None)
+        if bank is None:
+            raise RuntimeError(f"{what}: this encoder has no LoRA bank (lora_bank() creates one)")
+        return bank
+
+    def lora_bank(self, rank: int = 8, alpha_default: float = 16.0, targets=("q_proj", "v_proj"), capacity: int = 8) -> None:
+        """Create an empty bank of `capacity` slots for adaptations of rank `rank` on `targets` (ordered as LORA_TARGETS, whatever the caller's
+        order); `alpha_default` is the alpha of an adaptation added without one.  The selection starts as the base alone for every clip.
+        Refused by name: what lora_finetuning() refuses (conformer, sew, attention adapters), precision="mxfp8", an encoder that carries LoRA
+        parameters, a second bank."""
+        from .train import LORA_RANKS, LORA_TARGETS, refuse_lora
+        if isinstance(rank, bool) or not isinstance(rank, int) or rank not in LORA_RANKS:
+            raise ValueError(f"lora_bank: rank must be one of {LORA_RANKS} (the low-rank kernels' widths), got {rank!r}")
+        targets = (targets,) if isinstance(targets, str) else tuple(targets)
+        bad = [t for t in targets if t not in LORA_TARGETS]
+        if bad or not targets or len(set(targets)) != len(targets):
+            raise ValueError(f"lora_bank: targets must be distinct names out of {LORA_TARGETS}, got {targets!r}")
+        if not float(alpha_default) > 0.0:
+            raise ValueError(f"lora_bank: alpha_default must be positive, got {alpha_default!r}")
+        if isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 1:
+            raise ValueError(f"lora_bank: capacity must be a positive number of slots, got {capacity!r}")
+        enc = self.original_encoder
+        refuse_lora(enc.config)
+        if self.precision == "mxfp8":
+            raise NotImplementedError("lora_bank: a LoRA bank under precision='mxfp8' is not implemented (the low-rank term multiplies the bf16 rows "
+                                      "of the LayerNorm, which the mode does not keep next to the MX operand); use precision='bf16' or 'fp32'")
+        if getattr(self, "lora", None) is not None:
+            raise RuntimeError("lora_bank: this encoder carries LoRA parameters (lora_finetuning); merge_lora() them into the base, or export them "
+                               "with lora_state_dict() and add them to the bank of an encoder without them")
+        if getattr(self, "_lora_bank", None) is not None:
+            raise RuntimeError("lora_bank: this encoder already has a LoRA bank (one bank per encoder; lora_bank_add() fills its slots)")
+        device = next(enc.parameters()).device
+        self._lora_bank = LoraBank(int(enc.config.num_hidden_layers), int(enc.config.hidden_size), rank, float(alpha_default),
+                                   tuple(t for t in LORA_TARGETS if t in targets), capacity, self.precision, device)
+        self._param_epoch = getattr(self, "_param_epoch", 0) + 1       # graphs of the bank-less launch sequence are retired
+
+    def lora_bank_names(self):
+        """The names of the adaptations in the bank, in slot order."""
+        return [n for n in self._bank("lora_bank_names").names if n is not None]
+
+    def lora_bank_add(self, name: str, lora_sd: Dict[str, torch.Tensor], alpha: Optional[float] = None) -> int:
+        """Put the adaptation `lora_sd` (what lora_state_dict() returned: the bank's rank and targets) under `name` into a free slot; `alpha`: its
+        alpha (default: the bank's alpha_default).  Returns the slot.  Written in place: captured graphs stay valid."""
+        bank = self._bank("lora_bank_add")
+        if not isinstance(name, str) or not name:
+            raise ValueError(f"lora_bank_add: the name must be a non-empty string, got {name!r}")
+        if name in bank.names:
+            raise RuntimeError(f"lora_bank_add: the bank already holds an adaptation named {name!r} (lora_bank_remove() it first)")
+        if None not in bank.names:
+            raise RuntimeError(f"lora_bank_add: the bank is full ({bank.capacity} slots: {', '.join(bank.names)}); lora_bank_remove() frees one")
+        alpha = bank.alpha_default if alpha is None else float(alpha)
+        if not alpha > 0.0:
+            raise ValueError(f"lora_bank_add: alpha must be positive, got {alpha!r}")
+        c, r = bank.hidden, bank.rank
+        want = {f"lora.layers.{i}.{t}.lora_{m}": ((r, c) if m == "A" else (c, r)) for i in range(bank.n_layers) for t in bank.targets for m in "AB"}
+        if set(lora_sd) != set(want):
+            raise KeyError(f"lora_bank_add: keys differ (missing {sorted(set(want) - set(lora_sd))[:3]}, unexpected {sorted(set(lora_sd) - set(want))[:3]})")
+        for n, shape in want.items():
+            if tuple(lora_sd[n].shape) != shape:
+                raise ValueError(f"lora_bank_add: {n} has shape {tuple(lora_sd[n].shape)}, expected {shape}")
+        slot = bank.names.index(None)
+        with torch.no_grad():
+            for i in range(bank.n_layers):
+                for t in bank.targets:
+                    a, b = bank.pair(i, slot, t)
+                    a.copy_(lora_sd[f"lora.layers.{i}.{t}.lora_A"].detach().to(torch.float32))
+                    b.copy_(lora_sd[f"lora.layers.{i}.{t}.lora_B"].detach().to(torch.float32))
+            bank.scales[slot] = alpha / r
+        bank.names[slot] = name
+        return slot
+
+    def lora_bank_remove(self, name: str) -> None:
+        """Zero and free the slot of the adaptation `name`; clips that selected it go back to the base alone."""
+        bank = self._bank("lora_bank_remove")
+        if name not in bank.names:
+            raise KeyError(f"lora_bank_remove: no adaptation named {name!r} in the bank (it holds: {', '.join(self.lora_bank_names()) or 'none'})")
+        slot = bank.names.index(name)
+        bank.names[slot] = None
+        if name in bank.selection:
+            bank.selection = [None if n == name else n for n in bank.selection]
+            bank.write_ids()
+        with torch.no_grad():
+            for t in (bank.a_qkv, bank.b_qkv, bank.a_out, bank.b_out):
+                if t is not None:
+                    t[:, slot].zero_()
+            bank.scales[slot] = 0.0
+
+    def select_adapters(self, names) -> None:
+        """One entry per clip of the batches to come: the name of an adaptation in the bank, or None for the base alone; clips beyond the given
+        entries run the base alone.  A host-to-device copy into the bank's id buffer: nothing is re-captured."""
+        bank = self._bank("select_adapters")
+        names = list(names)
+        if len(names) > LORA_BANK_MAX_CLIPS:
+            raise ValueError(f"select_adapters: {len(names)} entries; the bank's id buffer holds {LORA_BANK_MAX_CLIPS} clips")
+        for n in names:
+            if n is not None and n not in bank.names:
+                raise KeyError(f"select_adapters: no adaptation named {n!r} in the bank (it holds: {', '.join(self.lora_bank_names()) or 'none'})")
+        bank.selection = names
+        bank.write_ids()
+
+    def selected_adapters(self):
+        """What select_adapters() was last given (a copy; [] after lora_bank())."""
+        return list(self._bank("selected_adapters").selection)
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        bank = self.__dict__.get("_lora_bank")
+        if bank is not None:
+            # .to(device) / .cuda(): the bank follows the base (its dtype is the operands' and stays)
+            device = next(self.original_encoder.parameters()).device
+            if bank.device != device:
+                bank.to(device)
+                self._param_epoch = getattr(self, "_param_epoch", 0) + 1
+        return out
+
+    def _bank_for(self, x: torch.Tensor, check_only: bool = False) -> Optional[LoraBank]:
+        """The bank an eval forward of the batch `x` runs with (None: no bank), on x's device.  check_only: the refusals alone, no device work."""
+        bank = getattr(self, "_lora_bank", None)
+        if bank is None:
+            return None
+        if bank.precision != self.precision:
+            raise RuntimeError(f"lora_bank: the bank was created under precision={bank.precision!r} and holds operands of that mode; the encoder now "
+                               f"runs precision={self.precision!r}.  Set the precision before lora_bank()")
+        if x.shape[0] > LORA_BANK_MAX_CLIPS:
+            raise RuntimeError(f"lora_bank: a batch of {x.shape[0]} clips; a forward with a LoRA bank takes up to {LORA_BANK_MAX_CLIPS} (the bank's id buffer)")
+        if bank.device != x.device and not check_only:
+            bank.to(x.device)                                              # new addresses: retire the graphs captured on the old ones
+            self._param_epoch = getattr(self, "_param_epoch", 0) + 1
+        return bank
+
     def _plan_frozen(self, device) -> Wav2Vec2Plan:
         """The plan the training path runs the frozen conv feature extractor on: built from and keyed on the feature extractor's parameters
         only, so an optimizer step on the transformer re-packs nothing and no transformer weight gets a device copy it never uses.  It runs
@@ -858,12 +1083,16 @@ class HuggingFaceEncoderAdapt(nn.Module):
             # name, before any device work
             chain = train_chain(getattr(self.original_encoder.config, "model_type", "wav2vec2"))
             chain.refuse_untrainable(self)
+        else:
+            self._bank_for(audio, check_only=True)       # a bank's refusals, by name, before any device work
         _t.require_gpu(audio, "wav2vec2 encoder")
         x = audio.to(torch.float32).contiguous()
         if self.training:
             h = chain.train_forward(self, x, audio_lengths if self.mask_input else None)
         else:
-            h = self._plan(x.device).forward(x, audio_lengths if self.mask_input else None)
+            plan = self._plan(x.device)
+            plan.bank = self._bank_for(x)
+            h = plan.forward(x, audio_lengths if self.mask_input else None)
         cfg = self.original_encoder.config
         n_ad = int(cfg.num_adapter_layers) if getattr(cfg, "add_adapter", False) else 0
         return h.transpose(-1, -2), feat_extract_output_lengths(cfg.conv_kernel, cfg.conv_stride, audio_lengths, n_ad, int(getattr(cfg, "adapter_stride", 2)))

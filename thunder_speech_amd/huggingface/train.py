@@ -1101,7 +1101,10 @@ def refuse_lora(cfg) -> None:
 
 
 def refuse_untrainable_lora(adapt) -> None:
-    """The LoRA regime's refusals, by name, before any device work: nothing if `adapt` carries no LoRA parameters."""
+    """The LoRA regime's refusals, by name, before any device work: nothing if `adapt` carries no LoRA parameters and no bank."""
+    if getattr(adapt, "_lora_bank", None) is not None:
+        raise NotImplementedError("HIP fine-tuning path: training an encoder that serves a LoRA bank (lora_bank) is not implemented (the bank is an "
+                                  "inference construct); fine-tune on a copy without one and add the result with lora_bank_add()")
     if getattr(adapt, "lora", None) is None:
         return
     refuse_lora(adapt.original_encoder.config)

@@ -204,6 +204,19 @@ class BaseCTCModule(_Base):
             _, collapsed, counts = greedy_decode(pred)
         return self.text_transform.decode_collapsed(collapsed, counts)
 
+    def predict_adapted(self, x: Tensor, adapters) -> List[str]:
+        """predict(x) with clip i served by the LoRA adaptation `adapters[i]` of the encoder's bank (a name, or None for the base alone;
+        HuggingFaceEncoderAdapt.lora_bank / lora_bank_add); the selection that held before the call holds again after it.  No reference
+        counterpart.  predict, forward, align, predict_spans, predict_beam and predict_nbest see whatever selection is current."""
+        if not hasattr(self.encoder, "select_adapters"):
+            raise NotImplementedError(f"predict_adapted: the encoder ({type(self.encoder).__name__}) serves no LoRA bank (HuggingFaceEncoderAdapt does)")
+        previous = self.encoder.selected_adapters()
+        self.encoder.select_adapters(adapters)
+        try:
+            return self.predict(x)
+        finally:
+            self.encoder.select_adapters(previous)
+
     # ------------------------------------------------------------------------------------------------------------------
     # "When was it said" (no reference counterpart): forced alignment of known transcripts and the spans of the greedy transcript, on the
     # kernels of csrc/ctc_align.hip (ctc_align.py).  predict() / forward() above are untouched.
