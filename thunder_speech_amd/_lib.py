@@ -1,7 +1,8 @@
 """ctypes binding of the C ABI: the core header include/thunder_speech_amd.h and its companions, one header per feature in
 include/thunder_speech_amd/, each versioned on its own (COMPANIONS, keyed by the header's file name without ".h"), and the staged companions in
 include_staged/thunder_speech_amd/ (STAGED, keyed the same way): headers of the same kind that wait for their place in include/, and those one
-level further down in include_staged/thunder_speech_amd/queued/ (QUEUED), which wait behind them.
+level further down in include_staged/thunder_speech_amd/queued/ (QUEUED), which wait behind them.  The nesting ends there: every later companion
+goes to include_open/thunder_speech_amd/ (OPEN), a table that nothing pins as a whole, so the next header needs no further directory.
 
 The headers are the only copy of the ABI: `read_header` derives every prototype, struct and TS_* constant from them and `lib()` applies the
 result, so a new entry point needs the header and its .hip definition and nothing here -- and a new companion needs its header in that directory
@@ -16,6 +17,7 @@ import ctypes as C
 import glob
 import os
 import re
+from collections import ChainMap
 from typing import NamedTuple, Optional
 
 from .build import ROOT, lib_path
@@ -24,6 +26,7 @@ HEADER = os.path.join(ROOT, "include", "thunder_speech_amd.h")
 COMPANION_DIR = os.path.join(ROOT, "include", "thunder_speech_amd")
 STAGED_DIR = os.path.join(ROOT, "include_staged", "thunder_speech_amd")
 QUEUED_DIR = os.path.join(STAGED_DIR, "queued")
+OPEN_DIR = os.path.join(ROOT, "include_open", "thunder_speech_amd")
 
 # Parameters and struct fields: these scalars, `[const] <struct>*` as POINTER(struct), every other pointer to one of
 # _POINTEES (const or not, any depth) as c_void_p.  Return types: _RETURNS only.
@@ -33,7 +36,7 @@ _RETURNS = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "const cha
 
 
 def _ctype(decl: str, where: str, structs: dict, ret: bool = False):
-    """The ctypes type of the C type `decl` (no declarator name) used in `where`."""
+    """The ctypes type of the C type `decl` (no declarator name) used in `where`; `structs` may be a ChainMap over other headers' structs."""
     words, stars = re.findall(r"\w+", decl), decl.count("*")
     key, table = " ".join(words) + "*" * stars, _RETURNS if ret else _SCALARS
     if key in table:
@@ -47,19 +50,21 @@ def _ctype(decl: str, where: str, structs: dict, ret: bool = False):
     raise ValueError(f"thunder_speech_amd header: {where}: no ctypes binding for the type `{key}`")
 
 
-def read_header(text: str):
+def read_header(text: str, known: Optional[dict] = None):
     """(signatures, structs, defines) of a C header: {ts_name: (restype, argtypes)} in declaration order,
-    {typedef name: ctypes.Structure subclass} and {TS_NAME: int} for every `#define TS_* <integer>`."""
+    {typedef name: ctypes.Structure subclass} and {TS_NAME: int} for every `#define TS_* <integer>`.  `known`: the structs of the headers this
+    one includes, for `const <their struct>*` parameters; they are not part of the returned structs."""
     code = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     defines = {n: int(v) for n, v in re.findall(r"^\s*#\s*define\s+(TS_\w+)\s+\(?\s*(-?\d+)\s*\)?\s*$", code, flags=re.M)}
     code = re.sub(r"^\s*#.*$", "", code, flags=re.M)
     structs = {}
+    visible = ChainMap(structs, known or {})
     for body, name in re.findall(r"typedef\s+struct\s+\w*\s*\{(.*?)\}\s*(\w+)\s*;", code, flags=re.S):
         fields = []
         for decl in filter(str.strip, body.split(";")):
             first, *more = decl.split(",")
             base = re.sub(r"\w+\s*$", "", first.replace("*", " "))      # C: each declarator carries its own '*'
-            fields += [(re.findall(r"\w+", d)[-1], _ctype(base + "*" * d.count("*"), f"struct {name}", structs))
+            fields += [(re.findall(r"\w+", d)[-1], _ctype(base + "*" * d.count("*"), f"struct {name}", visible))
                        for d in [first] + more]
         cls_name = "".join(w.capitalize() for w in name.split("_")[1:])  # ts_tcs_desc -> TcsDesc
         structs[name] = type(cls_name, (C.Structure,), {"__doc__": f"struct {name}", "_fields_": fields})
@@ -69,8 +74,8 @@ def read_header(text: str):
         argtypes = []
         for p in params:
             m = re.fullmatch(r"(.*[\s*])\w+\s*", p, flags=re.S)          # drop the parameter's name
-            argtypes.append(_ctype(m.group(1) if m else p, name, structs))
-        signatures[name] = (_ctype(ret, name, structs, ret=True), argtypes)
+            argtypes.append(_ctype(m.group(1) if m else p, name, visible))
+        signatures[name] = (_ctype(ret, name, visible, ret=True), argtypes)
     return signatures, structs, defines
 
 
@@ -88,11 +93,11 @@ class Header(NamedTuple):
         return self.defines[self.version_define]
 
 
-def _read_installed_header(path: str) -> Header:
+def _read_installed_header(path: str, known: Optional[dict] = None) -> Header:
     if not os.path.exists(path):
         raise RuntimeError(f"thunder_speech_amd: the C header {path} is missing; the ctypes binding is derived from it")
     with open(path) as f:
-        signatures, structs, defines = read_header(f.read())
+        signatures, structs, defines = read_header(f.read(), known)
     version_defines = [n for n in defines if re.fullmatch(r"TS_(\w+_)?ABI_VERSION", n)]
     version_functions = [n for n, (_, argtypes) in signatures.items() if re.fullmatch(r"ts_(\w+_)?abi_version", n) and not argtypes]
     if len(version_defines) != 1 or len(version_functions) != 1:
@@ -109,13 +114,17 @@ COMPANIONS = {os.path.basename(p)[:-len(".h")]: _read_installed_header(p) for p 
 STAGED = {os.path.basename(p)[:-len(".h")]: _read_installed_header(p) for p in sorted(glob.glob(os.path.join(STAGED_DIR, "*.h")))}
 # queued companions: the same again, for headers that arrived while the staged set was pinned too
 QUEUED = {os.path.basename(p)[:-len(".h")]: _read_installed_header(p) for p in sorted(glob.glob(os.path.join(QUEUED_DIR, "*.h")))}
+# open companions: the same once more, in a table without a pinned length; one of them may include a companion and take its structs
+_companion_structs = {n: s for h in COMPANIONS.values() for n, s in h.structs.items()}
+OPEN = {os.path.basename(p)[:-len(".h")]: _read_installed_header(p, _companion_structs) for p in sorted(glob.glob(os.path.join(OPEN_DIR, "*.h")))}
 _declared_in = {}
-for _h in (CORE, *COMPANIONS.values(), *STAGED.values(), *QUEUED.values()):
+for _h in (CORE, *COMPANIONS.values(), *STAGED.values(), *QUEUED.values(), *OPEN.values()):
     for _name in _h.signatures:
         if _name in _declared_in:
             raise RuntimeError(f"thunder_speech_amd: {_name} is declared by two headers, {_declared_in[_name]} and {_h.path}")
         _declared_in[_name] = _h.path
 CtcLm = COMPANIONS["ctc_beam_lm"].structs["ts_ctc_lm"]
+CtcLexicon = OPEN["ctc_beam_word_lm"].structs["ts_ctc_lexicon"]
 TcsDesc, FrontendDesc, WgradItem = STRUCTS["ts_tcs_desc"], STRUCTS["ts_frontend_desc"], STRUCTS["ts_wgrad_item"]
 TcsLaunch = STRUCTS["ts_tcs_launch"]
 EXPORTED_SYMBOLS = list(SIGNATURES)
@@ -144,7 +153,7 @@ def lib() -> C.CDLL:
             "`python -m thunder_speech_amd.build` (needs hipcc / ROCm); there is no CPU fallback.")
     import torch  # noqa: F401  -- must initialise its bundled HIP runtime BEFORE our code object is loaded
     L = C.CDLL(path)
-    headers = (CORE, *COMPANIONS.values(), *STAGED.values(), *QUEUED.values())
+    headers = (CORE, *COMPANIONS.values(), *STAGED.values(), *QUEUED.values(), *OPEN.values())
     missing = [name for h in headers for name in h.signatures if not hasattr(L, name)]
     if missing:
         raise RuntimeError(f"thunder_speech_amd: {path} does not export {missing}; rebuild it")

@@ -32,15 +32,17 @@ def sources():
 
 def header_deps():
     """Every header of the C ABI: the core header in include/, its companions in include/thunder_speech_amd/, the staged companions in
-    include_staged/thunder_speech_amd/ (headers waiting for their place in include/: _lib.STAGED) and the queued ones below them (_lib.QUEUED)."""
+    include_staged/thunder_speech_amd/ (headers waiting for their place in include/: _lib.STAGED), the queued ones below them (_lib.QUEUED) and
+    the open-ended table in include_open/thunder_speech_amd/ (_lib.OPEN)."""
     return (glob.glob(os.path.join(ROOT, "include", "*.h")) + glob.glob(os.path.join(ROOT, "include", "thunder_speech_amd", "*.h"))
             + glob.glob(os.path.join(ROOT, "include_staged", "thunder_speech_amd", "*.h"))
-            + glob.glob(os.path.join(ROOT, "include_staged", "thunder_speech_amd", "queued", "*.h")))
+            + glob.glob(os.path.join(ROOT, "include_staged", "thunder_speech_amd", "queued", "*.h"))
+            + glob.glob(os.path.join(ROOT, "include_open", "thunder_speech_amd", "*.h")))
 
 
 def common_flags():
     """What the product build and the sanitizer build share: language, include path, target name."""
-    return ["-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "include_staged"), "-I" + os.path.join(PKG, "csrc"), f'-DTS_BUILD_TARGET="{ARCH}"']
+    return ["-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "include_staged"), "-I" + os.path.join(ROOT, "include_open"), "-I" + os.path.join(PKG, "csrc"), f'-DTS_BUILD_TARGET="{ARCH}"']
 
 
 def needs_build() -> bool:

@@ -4,12 +4,16 @@ The LM's words are the acoustic model's CTC classes: characters for QuartzNet an
 (this module, numpy only) reads an ARPA file (`read_arpa`), matches its words to the classes and compiles the table to a back-off automaton
 (`NGramLM`); `NGramLM.weights(alpha, beta)` forms the f64 factors of one setting on the host, so that the device takes no exp and no log of the
 LM, and `beam_search_lm` runs the three launches of csrc/ctc_beam_lm.hip on them.  The algorithm is specified in thunder_speech_amd/ctc_beam_lm.h.  There is
-no CPU path for the search."""
+no CPU path for the search.
+
+For the character vocabularies (QuartzNet, the wav2vec2 family) the second half of this module fuses a WORD-level ARPA LM instead: `WordNGramLM`
+compiles the words to the same automaton (word ids as classes) and spells them into a lexicon trie, with hot words; `beam_search_word_lm` runs
+csrc/ctc_beam_word_lm.hip on them (thunder_speech_amd/ctc_beam_word_lm.h)."""
 from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Any, Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -295,4 +299,238 @@ def beam_search_lm(logits, lm: NGramLM, alpha: float, beta: float, lengths=None,
                                  out_len.data_ptr(), scores.data_ptr(), lm_scores.data_ptr(), counts.data_ptr(), ws.data_ptr(),
                                  torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(st, "ts_ctc_beam_lm_search")
+    return BeamLMResult(tokens, frames, out_len, scores, counts, lm_scores)
+
+
+# ---- word-level LM over a character vocabulary: lexicon trie, hot words (thunder_speech_amd/ctc_beam_word_lm.h) ---------------------------------
+class WordStep(NamedTuple):
+    """What one class does to the pair (word state, lexicon state) on the host: the unweighted log10 met, the pair entered, whether the OOV
+    factor is paid here, and the lexicon word that ended here (None: none, or a word outside the lexicon)."""
+    log10: float
+    state: int
+    x: int
+    oov: bool
+    word: Optional[int]
+
+
+@dataclass
+class WordLMWeights:
+    """Device tables of one (alpha, beta, oov_score, boosts) setting: `lm` the word automaton's (LMWeights), `struct` the ts_ctc_lexicon."""
+    lm: LMWeights
+    oov_score: float
+    boosts: Tuple[float, ...]
+    tensors: dict
+    struct: object
+
+
+class WordNGramLM:
+    """A word-level back-off n-gram LM for a CHARACTER vocabulary, with the lexicon trie that spells its words in CTC classes.
+
+    `words` are the lexicon's words in trie order, `spellings[w]` the classes of word w, `hot[w]` whether it is a hot word, `word_class[w]` its
+    class in the word automaton `lm` -- an `NGramLM` whose classes are the ids of the LM's spellable words (`lm_words`), then `unk_class` for
+    <unk>-as-a-word (a lexicon word the LM lacks has that class), then a class that plays the blank and is never looked up.  Trie: node 0 is the
+    root, `edges[x]` the (class, next node) pairs of node x sorted by class, `node_word[x]` the word that ends at x or -1.  Two words with one
+    spelling share a node; the first in sorted order is the node's word."""
+
+    def __init__(self, order: int, grams: Dict[Tuple[str, ...], Tuple[float, float]], itos: Sequence[str], blank_idx: int, delimiter: str = " ",
+                 lexicon=None, hotwords=(), spell: Optional[Callable[[str], str]] = None, unk_log10: float = -10.0):
+        self.n_classes, self.blank_idx = len(itos), int(blank_idx)
+        where = [c for c, tok in enumerate(itos) if tok == delimiter and c != self.blank_idx]
+        if not where:
+            raise ValueError(f"WordNGramLM: the vocabulary has no class {delimiter!r} to end a word")
+        self.delimiter = where[0]
+        letters: Dict[str, int] = {}
+        for c, tok in enumerate(itos):
+            if c not in (self.blank_idx, self.delimiter) and tok not in _SPECIAL and len(tok) == 1:
+                letters.setdefault(tok, c)
+        unspellable = set()
+
+        def spelled(word: str) -> Optional[Tuple[int, ...]]:
+            text = spell(word) if spell else word
+            if not text or any(ch not in letters for ch in text):
+                unspellable.add(word)
+                return None
+            return tuple(letters[ch] for ch in text)
+
+        # the word automaton: the existing machinery, with word ids as classes
+        lm_words = sorted({w for g in grams for w in g if w not in _SPECIAL})
+        self.lm_words: List[str] = [w for w in lm_words if spelled(w) is not None]
+        lm_id = {w: i for i, w in enumerate(self.lm_words)}
+        self.unk_class = len(self.lm_words)
+        id_grams, self.dropped_ngrams = {}, 0
+        for g, val in grams.items():
+            ids = tuple(_SPECIAL[w] if w in _SPECIAL else lm_id.get(w) for w in g)
+            if None in ids:
+                self.dropped_ngrams += 1
+            else:
+                id_grams.setdefault(ids, val)
+        self.order = int(order)
+        self.lm = NGramLM(order, id_grams, self.unk_class + 2, self.unk_class + 1, unk_log10, self.dropped_ngrams)
+        # the lexicon: the given words (default: the LM's spellable unigrams) and the hot words
+        hot = set(hotwords)
+        listed = [w for w in self.lm_words if (w,) in grams] if lexicon is None else list(lexicon)
+        spellings = {w: spelled(w) for w in sorted(set(listed) | hot) if w not in _SPECIAL}
+        self.words: List[str] = [w for w, sp in spellings.items() if sp is not None]
+        self.spellings: List[Tuple[int, ...]] = [spellings[w] for w in self.words]
+        self.hot: List[bool] = [w in hot for w in self.words]
+        self.word_class: List[int] = [lm_id.get(w, self.unk_class) for w in self.words]
+        self.dropped = len(unspellable)
+        prefixes = sorted({sp[:k] for sp in self.spellings for k in range(len(sp) + 1)} | {()}, key=lambda p: (len(p), p))
+        self.node_id: Dict[Tuple[int, ...], int] = {p: i for i, p in enumerate(prefixes)}
+        self.edges: List[List[Tuple[int, int]]] = [[] for _ in prefixes]
+        for p in prefixes[1:]:
+            self.edges[self.node_id[p[:-1]]].append((p[-1], self.node_id[p]))
+        for e in self.edges:
+            e.sort()
+        self.node_word: List[int] = [-1] * len(prefixes)
+        for w, sp in enumerate(self.spellings):
+            if self.node_word[self.node_id[sp]] < 0:
+                self.node_word[self.node_id[sp]] = w
+        self._static: dict = {}
+        self._cache: dict = {}
+
+    @classmethod
+    def from_arpa(cls, path: str, itos: Sequence[str], blank_idx: int, delimiter: str = " ", lexicon=None, hotwords=(),
+                  spell: Optional[Callable[[str], str]] = None, unk_log10: float = -10.0) -> "WordNGramLM":
+        """The word LM of an ARPA file over the character classes `itos`.  A word is kept if `spell(word)` (default: the word itself) can be
+        written in the one-character classes without the blank and without the class `delimiter`; n-grams with another word are dropped.
+        `lexicon` (an iterable of words; default: the LM's spellable unigrams) and `hotwords` form the trie; a word of either that the LM lacks
+        is scored as <unk>.  `dropped` counts the words -- of the file, the lexicon or the hot words -- that cannot be spelled."""
+        order, tables = read_arpa(path)
+        return cls(order, {g: v for t in tables for g, v in t.items()}, itos, blank_idx, delimiter, lexicon, hotwords, spell, unk_log10)
+
+    # ---- lookup on the host (what the kernel does on the device tables) ----
+    @property
+    def n_nodes(self) -> int:
+        return len(self.node_word)
+
+    @property
+    def start_state(self) -> int:
+        return self.lm.start_state
+
+    def finish(self, state: int, x: int) -> WordStep:
+        """The end of the pending word, as if a delimiter followed; nothing happens at the root."""
+        if x == 0:
+            return WordStep(0.0, state, 0, False, None)
+        w = self.node_word[x] if x > 0 else -1
+        p, nxt = self.lm.step(state, self.word_class[w] if w >= 0 else self.unk_class)
+        return WordStep(p, nxt, 0, w < 0 and x > 0, w if w >= 0 else None)
+
+    def step(self, state: int, x: int, c: int) -> WordStep:
+        """Class c (neither the blank nor outside the classes) from the pair (state, x)."""
+        c = int(c)
+        if c == self.blank_idx or not 0 <= c < self.n_classes:
+            raise ValueError(f"WordNGramLM.step: class {c} is the blank, or outside the classes")
+        if c == self.delimiter:
+            return self.finish(state, x)
+        if x < 0:
+            return WordStep(0.0, state, -1, False, None)
+        for cls_, nxt in self.edges[x]:
+            if cls_ == c:
+                return WordStep(0.0, state, nxt, False, None)
+        return WordStep(0.0, state, -1, True, None)
+
+    def walk(self, labels: Sequence[int], eos: bool = False) -> Tuple[float, int, List[int]]:
+        """(log10 P(words [</s>]), OOV words, lexicon words in order) of a label string from the start, the pending word included."""
+        s, x, total, oov, words = self.start_state, 0, 0.0, 0, []
+        for k in range(len(labels) + 1):
+            r = self.step(s, x, labels[k]) if k < len(labels) else self.finish(s, x)
+            total, s, x, oov = total + r.log10, r.state, r.x, oov + int(r.oov)
+            if r.word is not None:
+                words.append(r.word)
+        return total + (self.lm.eos(s) if eos and self.lm.has_eos else 0.0), oov, words
+
+    def score(self, labels: Sequence[int], eos: bool = False) -> float:
+        """log10 P(the words of labels [</s>]) from the start state: a word outside the lexicon is <unk>; the pending word counts."""
+        return self.walk(labels, eos)[0]
+
+    # ---- device tables ----
+    def word_boosts(self, hotword_weight: float = 0.0, boosts: Optional[Dict[str, float]] = None) -> Tuple[float, ...]:
+        """The boost of every lexicon word: `boosts[word]` where given, else `hotword_weight` for a hot word, else 0."""
+        boosts = dict(boosts or {})
+        unknown = [w for w in boosts if w not in self.words or not self.hot[self.words.index(w)]]
+        if unknown:
+            raise ValueError(f"WordNGramLM: boosts for {unknown}, which are not hot words of this LM")
+        return tuple(float(boosts.get(w, hotword_weight)) if h else 0.0 for w, h in zip(self.words, self.hot))
+
+    def lexicon_tables(self, oov_score: float = -10.0, hotword_weight: float = 0.0, boosts: Optional[Dict[str, float]] = None) -> Dict[str, np.ndarray]:
+        """The numpy tables of ts_ctc_lexicon for one setting: oov_factor = e^oov_score, word_factor = e^boost (1 for a word that is not hot),
+        each one f64 formed here."""
+        begin = np.zeros(self.n_nodes + 1, np.int32)
+        begin[1:] = np.cumsum([len(e) for e in self.edges])
+        flat = [x for e in self.edges for x in e]
+        return {"edge_begin": begin, "edge_class": np.array([x[0] for x in flat], np.int32).reshape(-1),
+                "edge_next": np.array([x[1] for x in flat], np.int32).reshape(-1), "node_word": np.array(self.node_word, np.int32),
+                "word_class": np.array(self.word_class, np.int32).reshape(-1),
+                "word_factor": np.exp(np.array(self.word_boosts(hotword_weight, boosts), np.float64)).reshape(-1),
+                "oov_factor": np.exp(np.array([float(oov_score)], np.float64))}
+
+    def weights(self, alpha: float, beta: float, oov_score: float = -10.0, hotword_weight: float = 0.0, boosts: Optional[Dict[str, float]] = None,
+                device=None) -> WordLMWeights:
+        """The device tables of one setting, cached per (alpha, beta, oov_score, boosts of the words, device).  A NEW setting gets NEW
+        word_factor / oov_factor tensors (and, for a new (alpha, beta), new factor tables of the word automaton): nothing is written at the
+        addresses of another setting, so a graph captured under the old setting keeps replaying the old setting.  The trie's tables do not
+        depend on the setting and are shared per device."""
+        import torch
+        from . import _lib
+        per_word = self.word_boosts(hotword_weight, boosts)
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("WordNGramLM.weights: GPU tensors required (no CPU fallback)")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        key = (float(alpha), float(beta), float(oov_score), per_word, str(dev))
+        if key not in self._cache:
+            up = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)
+            tables = self.lexicon_tables(oov_score, hotword_weight, boosts)
+            if str(dev) not in self._static:
+                self._static[str(dev)] = {k: up(tables[k]) for k in ("edge_begin", "edge_class", "edge_next", "node_word", "word_class")}
+            t = dict(self._static[str(dev)], word_factor=up(tables["word_factor"]), oov_factor=up(tables["oov_factor"]))
+            st = _lib.CtcLexicon(n_nodes=self.n_nodes, n_edges=int(t["edge_class"].numel()), n_words=len(self.words), delimiter=self.delimiter,
+                                 unk_class=self.unk_class, **{k: v.data_ptr() for k, v in t.items()})
+            self._cache[key] = WordLMWeights(self.lm.weights(alpha, beta, dev), float(oov_score), per_word, t, st)
+        return self._cache[key]
+
+
+def beam_search_word_lm(logits, lm: WordNGramLM, alpha: float, beta: float, lengths=None, blank_idx: int = 0, beam_width: int = 16,
+                        token_cap: int = 8, n_best: int = 1, score_eos: bool = True, oov_score: float = -10.0, hotword_weight: float = 0.0,
+                        boosts: Optional[Dict[str, float]] = None):
+    """`beam_search` over a character vocabulary with the word-level n-gram LM, its lexicon and its hot words fused into the search
+    (csrc/ctc_beam_word_lm.hip): score = log(CTC mass of the surviving alignments) + alpha ln 10 log10 P_LM(words [</s>]) + beta (number of
+    words) + oov_score (number of words outside the lexicon) + the boosts of the hot words; the word that the clip ends in counts.  Returns a
+    `BeamLMResult`; `lm_scores` is the unweighted log10 LM score of the words."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    from .ctc_align import _logits_f32
+    lg = _logits_f32(logits, "beam_search_word_lm")
+    b, v, t = lg.shape
+    if b == 0 or t == 0:
+        raise ValueError("beam_search_word_lm: empty logits")
+    if not isinstance(lm, WordNGramLM):
+        raise TypeError("beam_search_word_lm: lm must be a WordNGramLM")
+    if lm.n_classes != v or lm.blank_idx != int(blank_idx):
+        raise ValueError(f"beam_search_word_lm: the LM was compiled for {lm.n_classes} classes with blank {lm.blank_idx}, the logits have {v} with blank {int(blank_idx)}")
+    dev = lg.device
+    il = None if lengths is None else lengths.to(device=dev, dtype=torch.int64).to(torch.int32).contiguous()
+    L = _lib.lib()
+    nbytes = L.ts_ctc_beam_word_lm_workspace_bytes(b, t, int(beam_width), int(token_cap))
+    if nbytes < 0:
+        _lib.check(int(nbytes), "ts_ctc_beam_word_lm_workspace_bytes")
+    n_best = int(n_best)
+    if not 1 <= n_best <= int(beam_width):
+        raise ValueError("beam_search_word_lm: 1 <= n_best <= beam_width required")
+    w = lm.weights(alpha, beta, oov_score, hotword_weight, boosts, dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    tokens = torch.empty(b, n_best, t, dtype=torch.int32, device=dev)
+    frames = torch.empty(b, n_best, t, dtype=torch.int32, device=dev)
+    out_len = torch.empty(b, n_best, dtype=torch.int32, device=dev)
+    scores = torch.empty(b, n_best, dtype=torch.float32, device=dev)
+    lm_scores = torch.empty(b, n_best, dtype=torch.float32, device=dev)
+    counts = torch.empty(b, dtype=torch.int32, device=dev)
+    st = L.ts_ctc_beam_word_lm_search(lg.data_ptr(), b, v, t, lg.stride(1), None if il is None else il.data_ptr(), int(blank_idx), int(beam_width),
+                                      int(token_cap), n_best, int(bool(score_eos)), C.byref(w.lm.struct), C.byref(w.struct), tokens.data_ptr(),
+                                      frames.data_ptr(), out_len.data_ptr(), scores.data_ptr(), lm_scores.data_ptr(), counts.data_ptr(),
+                                      ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(st, "ts_ctc_beam_word_lm_search")
     return BeamLMResult(tokens, frames, out_len, scores, counts, lm_scores)

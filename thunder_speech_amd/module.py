@@ -298,38 +298,53 @@ class BaseCTCModule(_Base):
 
     # ------------------------------------------------------------------------------------------------------------------
     # CTC prefix beam search (no reference counterpart), on the kernels of csrc/ctc_beam.hip (ctc_beam.py).  predict() is untouched.
-    def predict_beam(self, x: Tensor, beam_width: int = 16, token_cap: int = 8, lm=None, alpha: float = 0.5, beta: float = 1.0) -> List[str]:
+    def _beam_search(self, what: str, x: Tensor, n_best: int, beam_width: int, token_cap: int, lm, alpha: float, beta: float, oov_score: float,
+                     hotword_weight: float, boosts):
+        """The search that `lm`'s type asks for: none, the token-level ctc_lm.NGramLM, or the word-level ctc_lm.WordNGramLM with its lexicon and
+        hot words.  The keywords are checked before anything runs."""
+        from . import ctc_beam as B
+        from . import ctc_lm as M
+        blank, word_level = self.text_transform.vocab.blank_idx, isinstance(lm, M.WordNGramLM)
+        if word_level:
+            shown = [c for c, tok in enumerate(self.text_transform.vocab.itos) if tok == " " and c != blank]
+            if not shown or shown[0] != lm.delimiter:
+                raise ValueError(f"{what}: the LM ends a word at class {lm.delimiter}, this module's vocabulary shows " +
+                                 (f"class {shown[0]}" if shown else "no class") + " as ' '")
+        elif (oov_score, hotword_weight, boosts) != (-10.0, 0.0, None):
+            raise ValueError(f"{what}: oov_score, hotword_weight and boosts belong to a ctc_lm.WordNGramLM; this search has no lexicon")
+        logits, _ = self._eval_logits(x, None)
+        if word_level:
+            return M.beam_search_word_lm(logits, lm, alpha, beta, None, blank, beam_width, token_cap, n_best, True, oov_score, hotword_weight, boosts)
+        if lm is None:
+            return B.beam_search(logits, None, blank, beam_width, token_cap, n_best)
+        return M.beam_search_lm(logits, lm, alpha, beta, None, blank, beam_width, token_cap, n_best)
+
+    def predict_beam(self, x: Tensor, beam_width: int = 16, token_cap: int = 8, lm=None, alpha: float = 0.5, beta: float = 1.0,
+                     oov_score: float = -10.0, hotword_weight: float = 0.0, boosts=None) -> List[str]:
         """Transcription by CTC prefix beam search: per clip the transcript whose alignments carry the most probability among the
         `beam_width` prefixes kept per frame (predict() follows the single best path instead).  Every clip is treated as full length.
         With `lm` (a ctc_lm.NGramLM over this module's classes) the n-gram LM is fused into the search on the kernels of
-        csrc/ctc_beam_lm.hip: LM weight `alpha`, token bonus `beta`."""
+        csrc/ctc_beam_lm.hip: LM weight `alpha`, token bonus `beta`.  With a ctc_lm.WordNGramLM (a word-level LM over a character
+        vocabulary) the search is that of csrc/ctc_beam_word_lm.hip: `beta` is a word bonus, `oov_score` what a word outside the lexicon
+        pays, `hotword_weight` the boost of every hot word and `boosts` a hot word's own; only that LM takes these three."""
         from . import ctc_align as A
-        from . import ctc_beam as B
-        logits, _ = self._eval_logits(x, None)
-        if lm is None:
-            res = B.beam_search(logits, None, self.text_transform.vocab.blank_idx, beam_width, token_cap, 1)
-        else:
-            from . import ctc_lm as M
-            res = M.beam_search_lm(logits, lm, alpha, beta, None, self.text_transform.vocab.blank_idx, beam_width, token_cap, 1)
+        res = self._beam_search("predict_beam", x, 1, beam_width, token_cap, lm, alpha, beta, oov_score, hotword_weight, boosts)
         ids, counts = A._to_host(res.tokens[:, 0], res.lengths[:, 0])                                                    # one copy
         return self.text_transform.decode_collapsed(torch.from_numpy(ids), torch.from_numpy(counts))
 
     def predict_nbest(self, x: Tensor, n_best: int, beam_width: int = 16, token_cap: int = 8, lm=None, alpha: float = 0.5,
-                      beta: float = 1.0) -> List[List["Hypothesis"]]:
+                      beta: float = 1.0, oov_score: float = -10.0, hotword_weight: float = 0.0, boosts=None) -> List[List["Hypothesis"]]:
         """The `n_best` best transcripts of each clip under CTC prefix beam search, best first: text, score (log of the summed probability
         of the transcript's surviving alignments) and per token the frame and time at which it entered the hypothesis.  With `lm` the
         search is the fused one of predict_beam: `score` is the fused score and every hypothesis carries `lm_score`, the unweighted
-        log10 LM score of its tokens and </s>."""
+        log10 LM score of its tokens (its words, for a WordNGramLM) and </s>."""
         from . import ctc_align as A
         from . import ctc_beam as B
-        logits, _ = self._eval_logits(x, None)
+        res = self._beam_search("predict_nbest", x, n_best, beam_width, token_cap, lm, alpha, beta, oov_score, hotword_weight, boosts)
         if lm is None:
-            res = B.beam_search(logits, None, self.text_transform.vocab.blank_idx, beam_width, token_cap, n_best)
             tokens, frames, lengths, scores, counts = A._to_host(res.tokens, res.frames, res.lengths, res.scores, res.counts)  # one copy
             lm_scores = None
         else:
-            from . import ctc_lm as M
-            res = M.beam_search_lm(logits, lm, alpha, beta, None, self.text_transform.vocab.blank_idx, beam_width, token_cap, n_best)
             tokens, frames, lengths, scores, counts, lm_scores = A._to_host(res.tokens, res.frames, res.lengths, res.scores, res.counts,
                                                                             res.lm_scores)                                # one copy
         return B.hypotheses_from_tables(tokens, frames, lengths, scores, counts, self.text_transform.vocab.itos, self.text_transform._ids_to_text,
