@@ -12,23 +12,15 @@
 //   * one wave walks the back-pointers from the last frame to the first: a chain of T LDS reads, or, from the workspace, of T / 16 round trips
 //     (the path moves at most two states per frame, so 16 frames back it is in the same 64-state word or the one below: 64 lanes fetch
 //     16 frames x 2 words x 2 ballots at once).
-#include "ts_common.hpp"
+#include "ctc_align_common.hpp"      // ALIGN_NEG_INF, align_lds_barrier, frame_logp: shared with csrc/ctc_align_long.hip
 
 #include "thunder_speech_amd/ctc_align.h"
 
 namespace ts {
 
-constexpr float ALIGN_NEG_INF = -__builtin_huge_valf();
 constexpr int ALIGN_PF = 8;                          // emission prefetch distance in time steps
 constexpr size_t ALIGN_LDS_MAX = 160 * 1024;
 constexpr int ALIGN_RED_BYTES = 64;                  // 16 floats: the score's per-wave partial sums
-
-// workgroup barrier that orders LDS traffic only (csrc/ctc.hip: __syncthreads() would also wait for the emission prefetch ring at every step)
-__device__ __forceinline__ void align_lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 struct AlignArgs {
   const float* logits;      // [B][V][pitch]
@@ -45,28 +37,6 @@ struct AlignArgs {
   int n_classes, n_frames, pitch, s_max, lmax, blank;
   int nwt;                  // 64-state words per frame: states per thread x waves (state s is bit s & 63 of word s >> 6)
 };
-
-// log_softmax(lg[:, t])[tok]: maximum in f32 (exact), the sum of exponentials, the logarithm and the difference in f64, rounded to f32 once.
-// Batches of 8 independent loads, as the log-sum-exp prologue of csrc/ctc.hip.
-__device__ __forceinline__ float frame_logp(const float* lg, int V, int pitch, int t, int tok) {
-  float m = lg[t];
-  for (int v0 = 1; v0 < V; v0 += 8) {
-    float x[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) x[u] = lg[(size_t)min(v0 + u, V - 1) * pitch + t];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) m = fmaxf(m, x[u]);
-  }
-  double sum = 0.0;
-  for (int v0 = 0; v0 < V; v0 += 8) {
-    float x[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) x[u] = lg[(size_t)min(v0 + u, V - 1) * pitch + t];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) sum += (v0 + u < V) ? exp((double)x[u] - (double)m) : 0.0;
-  }
-  return (float)((double)lg[(size_t)tok * pitch + t] - (double)m - log(sum));
-}
 
 template <int SPT, bool BP_LDS>
 __global__ __launch_bounds__(1024) void ctc_align_kernel(const AlignArgs a) {
@@ -210,49 +180,7 @@ __global__ __launch_bounds__(1024) void ctc_align_kernel(const AlignArgs a) {
     if (lane == 0) st[0] = s;
   }
   __syncthreads();
-  // the path's cells in parallel over the frames: token, log-probability, span boundaries
-  const int Tp = feasible ? T : 0;
-  float part = 0.f;
-  for (int t = lane; t < Tp; t += NT) {
-    const int s = min(max(st[t], 0), L - 1);
-    const int sp = t > 0 ? st[t - 1] : -1, sn = t + 1 < Tp ? st[t + 1] : -1;
-    const int tok = ext[s];
-    const float lp = frame_logp(lg, V, a.pitch, t, tok);
-    path[t] = tok;
-    lpw[t] = lp;
-    part += lp;
-    if (s & 1) {
-      if (sp != s) spans[(s >> 1) * 2] = t;
-      if (sn != s) spans[(s >> 1) * 2 + 1] = t + 1;
-    }
-  }
-  for (int t = Tp + lane; t < a.n_frames; t += NT) path[t] = -1;
-  part = wave_sum(part);
-  if ((lane & 63) == 0) red[wave] = part;
-  __syncthreads();                                 // and the spans and log-probabilities above are visible to the workgroup
-  if (lane == 0) {
-    float sc = 0.f;
-    for (int w = 0; w < (NT >> 6); ++w) sc += red[w];
-    a.score[b] = feasible ? sc : ALIGN_NEG_INF;
-  }
-  // one thread per label: the span's log-probabilities summed in frame order, 8 independent loads at a time
-  const int Sp = feasible ? S : 0;
-  for (int j = lane; j < a.s_max; j += NT) {
-    if (j >= Sp) {
-      spans[j * 2] = 0; spans[j * 2 + 1] = 0; span_logp[j] = 0.f;
-      continue;
-    }
-    const int t0 = min(max(spans[j * 2], 0), Tp), t1 = min(max(spans[j * 2 + 1], t0), Tp);
-    float sum = 0.f;
-    for (int t = t0; t < t1; t += 8) {
-      float x[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) x[u] = lpw[min(t + u, t1 - 1)];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) sum += (t + u < t1) ? x[u] : 0.f;
-    }
-    span_logp[j] = sum;
-  }
+  align_epilogue(lg, V, a.pitch, a.n_frames, a.s_max, T, S, L, feasible, st, lpw, path, spans, span_logp, a.score + b, red, [&](int s) { return ext[s]; });
 }
 
 // Greedy spans, one 1024-thread workgroup per utterance.  Pass 1, a thread per frame: argmax (lowest index wins, as greedy_kernel of

@@ -70,10 +70,24 @@ def forced_align(logits: Tensor, targets: Tensor, input_lengths: Tensor, target_
     """Best CTC path of each transcript through its clip.  Arguments as `calculate_ctc`: logits [B, V, T'] before softmax, targets
     [B, S] padded or the 1-D concatenation, lengths of any integer or float dtype; targets and lengths go through the loss's own
     preparation (a device transcript with an id outside [0, V) becomes infeasible: score -inf, no spans)."""
-    lg = _logits_f32(logits, "forced_align")
+    return _forced_align("forced_align", logits, targets, input_lengths, target_lengths, blank_idx, None)
+
+
+def forced_align_long(logits: Tensor, targets: Tensor, input_lengths: Tensor, target_lengths: Tensor, blank_idx: int,
+                      states_per_thread: int = 0) -> Alignment:
+    """`forced_align` on ts_ctc_align_long (thunder_speech_amd/longform.h): the same arguments, results, tie rules and arithmetic, for
+    transcripts of up to 32 767 labels where `forced_align` refuses more than 2 047.  `states_per_thread` 0: chosen from the label
+    capacity; 8, 16, 32 or 64: that instantiation."""
+    return _forced_align("forced_align_long", logits, targets, input_lengths, target_lengths, blank_idx, int(states_per_thread))
+
+
+def _forced_align(what: str, logits: Tensor, targets: Tensor, input_lengths: Tensor, target_lengths: Tensor, blank_idx: int,
+                  states_per_thread: Optional[int]) -> Alignment:
+    """The two aligners' shared preparation and call; states_per_thread None: ts_ctc_align, else ts_ctc_align_long."""
+    lg = _logits_f32(logits, what)
     b, v, t = lg.shape
     if b == 0 or t == 0:
-        raise ValueError("forced_align: empty logits")
+        raise ValueError(f"{what}: empty logits")
     dev = lg.device
     if targets.is_cuda and targets.dim() == 2:
         tg, tl, il = _prepare_on_device(targets, target_lengths, input_lengths, b, v, dev)
@@ -85,18 +99,19 @@ def forced_align(logits: Tensor, targets: Tensor, input_lengths: Tensor, target_
             tl = torch.where(bad_rows & (tl == 0), torch.ones_like(tl), tl)
     s_max = tg.shape[1]
     L = _lib.lib()
-    nbytes = L.ts_ctc_align_workspace_bytes(b, t, s_max)
+    name = "ts_ctc_align" if states_per_thread is None else "ts_ctc_align_long"
+    nbytes = getattr(L, name + "_workspace_bytes")(b, t, s_max)
     if nbytes < 0:
-        _lib.check(int(nbytes), "ts_ctc_align_workspace_bytes")
+        _lib.check(int(nbytes), name + "_workspace_bytes")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     path = torch.empty(b, t, dtype=torch.int32, device=dev)
     spans = torch.empty(b, s_max, 2, dtype=torch.int32, device=dev)
     span_logp = torch.empty(b, s_max, dtype=torch.float32, device=dev)
     score = torch.empty(b, dtype=torch.float32, device=dev)
-    st = L.ts_ctc_align(lg.data_ptr(), b, v, t, lg.stride(1), tg.data_ptr(), s_max, il.data_ptr(), tl.data_ptr(), int(blank_idx),
-                        path.data_ptr(), spans.data_ptr(), span_logp.data_ptr(), score.data_ptr(), ws.data_ptr(),
-                        torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(st, "ts_ctc_align")
+    head = (lg.data_ptr(), b, v, t, lg.stride(1), tg.data_ptr(), s_max, il.data_ptr(), tl.data_ptr(), int(blank_idx))
+    tail = (path.data_ptr(), spans.data_ptr(), span_logp.data_ptr(), score.data_ptr(), ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    st = L.ts_ctc_align(*head, *tail) if states_per_thread is None else L.ts_ctc_align_long(*head, states_per_thread, *tail)
+    _lib.check(st, name)
     return Alignment(path, spans, span_logp, score, tg, tl.clamp(0, s_max))
 
 

@@ -4,6 +4,7 @@ Subclasses pytorch_lightning.LightningModule when Lightning is installed (it is 
 plain nn.Module with the same methods, so `pl.Trainer.fit` keeps working where available."""
 from __future__ import annotations
 
+import contextlib
 from typing import Any, Dict, List, Optional, Tuple, Union
 
 import torch
@@ -251,23 +252,29 @@ class BaseCTCModule(_Base):
                     n *= int(m.stride)
         return n
 
+    @contextlib.contextmanager
+    def _eval_no_grad(self):
+        """Eval mode and no_grad for the forwards inside; afterwards every submodule gets its own flag back (a frozen encoder stays in eval mode)."""
+        modes = [(m, m.training) for m in self.modules()]
+        if any(on for _, on in modes):
+            self.eval()
+        try:
+            with torch.no_grad():
+                yield
+        finally:
+            if any(on for _, on in modes):
+                for m, on in modes:
+                    m.training = on
+                self.reset_inference_graphs()
+
     def _eval_logits(self, x: Tensor, lengths: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
         """(logits, output lengths) of the eval-mode forward under no_grad; lengths None: every clip is full length, as predict()."""
         if not x.is_cuda:
             raise RuntimeError("align / predict_spans: GPU tensors required (no CPU fallback)")
         if lengths is None:
             lengths = torch.full((x.shape[0],), x.shape[-1], dtype=torch.int32, device=x.device)
-        modes = [(m, m.training) for m in self.modules()]
-        if any(on for _, on in modes):
-            self.eval()
-        try:
-            with torch.no_grad():
-                logits, out_lengths = self(x, lengths)
-        finally:
-            if any(on for _, on in modes):                    # every submodule gets its own flag back (a frozen encoder stays in eval mode)
-                for m, on in modes:
-                    m.training = on
-                self.reset_inference_graphs()
+        with self._eval_no_grad():
+            logits, out_lengths = self(x, lengths)
         if out_lengths is None:
             out_lengths = torch.full((x.shape[0],), logits.shape[-1], dtype=torch.int32, device=x.device)
         return logits, out_lengths
@@ -298,10 +305,11 @@ class BaseCTCModule(_Base):
 
     # ------------------------------------------------------------------------------------------------------------------
     # CTC prefix beam search (no reference counterpart), on the kernels of csrc/ctc_beam.hip (ctc_beam.py).  predict() is untouched.
-    def _beam_search(self, what: str, x: Tensor, n_best: int, beam_width: int, token_cap: int, lm, alpha: float, beta: float, oov_score: float,
-                     hotword_weight: float, boosts):
-        """The search that `lm`'s type asks for: none, the token-level ctc_lm.NGramLM, or the word-level ctc_lm.WordNGramLM with its lexicon and
-        hot words.  The keywords are checked before anything runs."""
+    def _beam_search_on(self, what: str, logits: Tensor, lengths: Optional[Tensor], n_best: int, beam_width: int, token_cap: int, lm, alpha: float,
+                        beta: float, oov_score: float, hotword_weight: float, boosts):
+        """The search that `lm`'s type asks for, on `logits` with their `lengths` (None: every frame): none, the token-level ctc_lm.NGramLM, or
+        the word-level ctc_lm.WordNGramLM with its lexicon and hot words.  `logits` may be a function that returns (logits, lengths): the
+        keywords are checked before it runs."""
         from . import ctc_beam as B
         from . import ctc_lm as M
         blank, word_level = self.text_transform.vocab.blank_idx, isinstance(lm, M.WordNGramLM)
@@ -312,12 +320,19 @@ class BaseCTCModule(_Base):
                                  (f"class {shown[0]}" if shown else "no class") + " as ' '")
         elif (oov_score, hotword_weight, boosts) != (-10.0, 0.0, None):
             raise ValueError(f"{what}: oov_score, hotword_weight and boosts belong to a ctc_lm.WordNGramLM; this search has no lexicon")
-        logits, _ = self._eval_logits(x, None)
+        if callable(logits):
+            logits, lengths = logits()
         if word_level:
-            return M.beam_search_word_lm(logits, lm, alpha, beta, None, blank, beam_width, token_cap, n_best, True, oov_score, hotword_weight, boosts)
+            return M.beam_search_word_lm(logits, lm, alpha, beta, lengths, blank, beam_width, token_cap, n_best, True, oov_score, hotword_weight, boosts)
         if lm is None:
-            return B.beam_search(logits, None, blank, beam_width, token_cap, n_best)
-        return M.beam_search_lm(logits, lm, alpha, beta, None, blank, beam_width, token_cap, n_best)
+            return B.beam_search(logits, lengths, blank, beam_width, token_cap, n_best)
+        return M.beam_search_lm(logits, lm, alpha, beta, lengths, blank, beam_width, token_cap, n_best)
+
+    def _beam_search(self, what: str, x: Tensor, n_best: int, beam_width: int, token_cap: int, lm, alpha: float, beta: float, oov_score: float,
+                     hotword_weight: float, boosts):
+        """_beam_search_on the clips `x`, every clip full length."""
+        return self._beam_search_on(what, lambda: (self._eval_logits(x, None)[0], None), None, n_best, beam_width, token_cap, lm, alpha, beta,
+                                    oov_score, hotword_weight, boosts)
 
     def predict_beam(self, x: Tensor, beam_width: int = 16, token_cap: int = 8, lm=None, alpha: float = 0.5, beta: float = 1.0,
                      oov_score: float = -10.0, hotword_weight: float = 0.0, boosts=None) -> List[str]:
@@ -349,6 +364,152 @@ class BaseCTCModule(_Base):
                                                                             res.lm_scores)                                # one copy
         return B.hypotheses_from_tables(tokens, frames, lengths, scores, counts, self.text_transform.vocab.itos, self.text_transform._ids_to_text,
                                         self.samples_per_frame, self.sample_rate, lm_scores)
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # Recordings longer than one forward pass (no reference counterpart: module.py:88-100 takes one batch): overlapping full-length windows
+    # on the captured inference graph of ONE signature, stitched back onto the recording's frame grid (longform.py, csrc/longform.hip), and
+    # the existing decoders, plus the long aligner (csrc/ctc_align_long.hip), on the stitched logits.  The methods above are untouched.
+    def _frames_of(self, n_samples: int) -> int:
+        """Output frames of a clip of `n_samples` samples by the module's own length arithmetic (host only: the front end's and the encoder's
+        length functions on a CPU tensor)."""
+        lengths = torch.tensor([int(n_samples)])
+        cfg = getattr(getattr(self.encoder, "original_encoder", None), "config", None)
+        if cfg is not None:
+            from .huggingface.encoder import feat_extract_output_lengths
+            adapters = int(cfg.num_adapter_layers) if getattr(cfg, "add_adapter", False) else 0
+            return int(feat_extract_output_lengths(cfg.conv_kernel, cfg.conv_stride, lengths, adapters, int(getattr(cfg, "adapter_stride", 2))))
+        front = [m for m in self.audio_transform.modules() if hasattr(m, "get_sequence_length")]
+        if len(front) != 1:
+            raise NotImplementedError("logits_long: the audio transform is neither the mel front end nor a transformers one")
+        lengths = front[0].get_sequence_length(lengths)
+        for blk in self.encoder.children():
+            main = getattr(blk, "mconv", blk)
+            for m in main.modules():
+                if hasattr(m, "get_seq_len") and hasattr(m, "stride"):
+                    lengths = m.get_seq_len(lengths)
+        return int(lengths)
+
+    def _long_recordings(self, what: str, recordings) -> List[Tensor]:
+        recs = [recordings] if isinstance(recordings, Tensor) else list(recordings)
+        if not recs:
+            raise ValueError(f"{what}: no recordings")
+        for r in recs:
+            if not isinstance(r, Tensor) or r.dim() != 1 or r.numel() == 0:
+                raise ValueError(f"{what}: every recording is a 1-D waveform tensor with at least one sample")
+            if not r.is_cuda:
+                raise RuntimeError(f"{what}: GPU tensors required (no CPU fallback)")
+            if r.dtype != torch.float32:
+                raise ValueError(f"{what}: float32 waveforms required")
+        return recs
+
+    def logits_long(self, recordings, chunk_s: float = 20.0, context_s: float = 2.0, batch_size: int = 16) -> "LongLogits":
+        """The logits of recordings of any length on each recording's own frame grid: LongLogits(logits f32 [R, V, T_max], lengths int32 [R],
+        plans).  `recordings`: a 1-D GPU f32 waveform or a list of them.  A recording longer than `chunk_s` seconds is run as overlapping
+        windows of that length, `context_s` seconds of every window's ends discarded in favour of its neighbour (longform.plan_windows); the
+        windows of all recordings are pooled and run `batch_size` at a time through the eval-mode forward under no_grad, entering through one
+        staging buffer, so the inference graph of that one signature is captured once and replayed; one launch stitches the windows' logits.
+        Nothing synchronises with the host between the batches.  A recording that fits one window runs as one clip of its own length: its row
+        is what `module(x[None], ...)` gives.  A LoRA bank selection (select_adapters) holds for every batch of windows as it does for predict:
+        entry i serves row i of each batch."""
+        from . import longform as LF
+        recs = self._long_recordings("logits_long", recordings)
+        dev, spf, sr = recs[0].device, self.samples_per_frame, self.sample_rate
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError("logits_long: batch_size must be at least 1")
+        chunk = int(round(float(chunk_s) * sr))
+        context = int(round(float(context_s) * sr / spf))
+        if chunk < spf:
+            raise ValueError(f"logits_long: chunk_s = {chunk_s} is shorter than one frame ({spf} samples)")
+        frames = self._frames_of(chunk)
+        multiple = LF.grid_multiple(getattr(getattr(self.encoder, "original_encoder", None), "config", None))
+        plans = [LF.plan_windows(int(r.shape[0]), chunk, context, spf, frames, multiple) for r in recs]      # refusals before any device work
+        table = [(i, s) for i, p in enumerate(plans) if p is not None for s in p.starts]
+        short = [i for i, p in enumerate(plans) if p is None]
+        with self._eval_no_grad():
+            short_out = []
+            for i in short:
+                x = recs[i][None]
+                lg, ln = self(x, torch.full((1,), x.shape[-1], dtype=torch.int32, device=dev))
+                short_out.append((i, lg, ln))
+            win = None
+            if table:
+                audio, rec_begin, _ = LF.pack_recordings(recs)
+                n_win = len(table)
+                n_batches = -(-n_win // batch_size)
+                windows = torch.tensor(table + [(0, 0)] * (n_batches * batch_size - n_win), dtype=torch.int64).to(dev, non_blocking=True)
+                stages = self.__dict__.setdefault("_long_stages", {})
+                stage = stages.get((batch_size, chunk, str(dev)))
+                if stage is None:                                  # kept: the zero-copy graph is keyed by this address
+                    stages.clear()
+                    stage = stages[(batch_size, chunk, str(dev))] = torch.zeros(batch_size, chunk, dtype=torch.float32, device=dev)
+                full = torch.full((batch_size,), chunk, dtype=torch.int32, device=dev)
+                for k in range(n_batches):
+                    rows = min(batch_size, n_win - k * batch_size)
+                    LF.gather_windows(audio, rec_begin, windows[k * batch_size:], rows, stage)
+                    lg, _ = self(stage, full)
+                    if win is None:
+                        if lg.shape[-1] != frames:
+                            raise RuntimeError(f"logits_long: the forward returned {lg.shape[-1]} frames for a window of {chunk} samples, the "
+                                               f"module's length arithmetic says {frames}")
+                        win = torch.empty(n_batches * batch_size, lg.shape[1], frames, dtype=lg.dtype, device=dev)
+                    win[k * batch_size: (k + 1) * batch_size].copy_(lg)
+        n_classes = win.shape[1] if win is not None else short_out[0][1].shape[1]
+        t_max = max([p.n_frames for p in plans if p is not None] + [lg.shape[-1] for _, lg, _ in short_out])
+        logits = torch.zeros(len(recs), n_classes, t_max, dtype=torch.float32, device=dev)
+        lengths = torch.zeros(len(recs), dtype=torch.int32, device=dev)
+        for i, lg, ln in short_out:
+            logits[i, :, : lg.shape[-1]].copy_(lg[0])
+            lengths[i: i + 1].copy_(ln if ln is not None else torch.full((1,), lg.shape[-1], dtype=torch.int32, device=dev))
+        if win is not None:
+            cuts = torch.tensor(LF.cut_table(plans), dtype=torch.int32).to(dev, non_blocking=True)
+            LF.stitch_windows(win[: len(table)], cuts, logits, lengths)
+        return LF.LongLogits(logits, lengths, plans)
+
+    def transcribe_long(self, recordings, chunk_s: float = 20.0, context_s: float = 2.0, batch_size: int = 16, beam_width: Optional[int] = None,
+                        token_cap: int = 8, lm=None, alpha: float = 0.5, beta: float = 1.0, oov_score: float = -10.0, hotword_weight: float = 0.0,
+                        boosts=None) -> List[str]:
+        """One transcript per recording of any length (logits_long).  beam_width None: greedy (the spans of ctc_align.greedy_spans on the
+        stitched logits and their lengths, joined); otherwise the prefix beam search that `lm`'s type asks for, with predict_beam's keywords."""
+        from . import ctc_align as A
+        if beam_width is None:
+            if lm is not None or (oov_score, hotword_weight, boosts) != (-10.0, 0.0, None):
+                raise ValueError("transcribe_long: lm, oov_score, hotword_weight and boosts belong to the beam search; give a beam_width")
+            ll = self.logits_long(recordings, chunk_s, context_s, batch_size)
+            gs = A.greedy_spans(ll.logits, ll.lengths, self.text_transform.vocab.blank_idx)
+            return self.text_transform.decode_collapsed(gs.tokens, gs.counts)
+
+        def stitched():
+            ll = self.logits_long(recordings, chunk_s, context_s, batch_size)
+            return ll.logits, ll.lengths
+        res = self._beam_search_on("transcribe_long", stitched, None, 1, beam_width, token_cap, lm, alpha, beta, oov_score, hotword_weight, boosts)
+        ids, counts = A._to_host(res.tokens[:, 0], res.lengths[:, 0])                                                    # one copy
+        return self.text_transform.decode_collapsed(torch.from_numpy(ids), torch.from_numpy(counts))
+
+    def predict_spans_long(self, recordings, chunk_s: float = 20.0, context_s: float = 2.0, batch_size: int = 16) -> List["AlignedClip"]:
+        """predict_spans for recordings of any length: the tokens of the greedy transcript with their spans; times are absolute in the
+        recording (the stitched grid is the recording's)."""
+        from . import ctc_align as A
+        ll = self.logits_long(recordings, chunk_s, context_s, batch_size)
+        gs = A.greedy_spans(ll.logits, ll.lengths, self.text_transform.vocab.blank_idx)
+        ids, spans, logp, counts = A._to_host(gs.tokens, gs.spans, gs.span_logp, gs.counts)                              # one copy
+        scores = [float(logp[b, : int(counts[b])].sum()) for b in range(len(counts))]
+        return A.clips_from_spans(ids, spans, logp, counts, scores, self.text_transform.vocab.itos, self.samples_per_frame, self.sample_rate)
+
+    def align_long(self, recordings, texts: List[str], chunk_s: float = 20.0, context_s: float = 2.0, batch_size: int = 16) -> List["AlignedClip"]:
+        """align for recordings of any length and transcripts of up to 32 767 tokens (ctc_align.forced_align_long on the stitched logits):
+        per recording the score and one TokenSpan per token, times absolute in the recording.  A transcript that does not fit its recording
+        gives score -inf and no tokens."""
+        from . import ctc_align as A
+        texts = list(texts)
+        ll = self.logits_long(recordings, chunk_s, context_s, batch_size)
+        if len(texts) != ll.logits.shape[0]:
+            raise ValueError(f"align_long: {len(texts)} texts for {ll.logits.shape[0]} recordings")
+        y, y_lengths = self.text_transform.encode(texts, device=ll.logits.device)
+        al = A.forced_align_long(ll.logits, y, ll.lengths, y_lengths, self.text_transform.vocab.blank_idx)
+        ids, spans, logp, counts, scores = A._to_host(al.targets, al.spans, al.span_logp, al.target_lengths, al.score)     # one copy
+        counts = [0 if scores[b] == float("-inf") else int(counts[b]) for b in range(len(counts))]
+        return A.clips_from_spans(ids, spans, logp, counts, scores, self.text_transform.vocab.itos, self.samples_per_frame, self.sample_rate)
 
     def training_step(self, batch, batch_idx: int) -> torch.Tensor:
         audio, audio_lengths, texts = batch
