@@ -138,6 +138,12 @@ class _Conv1dDecoder(nn.Conv1d):
     def _layer(self):
         return self._cache.get([self.weight, self.bias], lambda: self._build(False))
 
+    def _head_fragments(self):
+        """The weights in the k-order of ts_qn_head_fwd (plan.pack_head_wd), cached like the packed layer; for at most 32 classes."""
+        cache = self.__dict__.setdefault("_head_cache", _PackedCache())
+        return cache.get([self.weight], lambda: _plan.pack_head_wd(
+            self.weight.detach().to(device="cpu", dtype=torch.float32).reshape(self.out_channels, self.in_channels)).to(self.weight.device))
+
     def forward(self, x: Tensor) -> Tensor:
         _t.require_gpu(x, "conv1d_decoder")
         grad_on = torch.is_grad_enabled()

@@ -72,6 +72,9 @@ class BaseCTCModule(_Base):
     # forward is module.py:74-86).  `graph_inference`: None = automatic (on for the model families whose whole forward is capture-safe: the
     # mel front end + QuartzNet / Citrinet encoder + this package's decoders), True / False = forced on / off.
     graph_inference: Optional[bool] = None
+    # QuartzNet's last block (1x1 conv + BN + ReLU) and the conv1d decoder as one launch (thunder_speech_amd/qn_head.h) where the model has that
+    # shape; False: the two launches of ts_tcs_subblock_fwd, always.  Part of the inference graphs' stamp.
+    fused_head: bool = True
     MAX_INFERENCE_GRAPHS = 8             # graphs kept per module (outputs + at most one static input copy per signature; the launch arena is shared)
 
     def _inference_graph_ok(self, x: Tensor) -> bool:
@@ -104,12 +107,13 @@ class BaseCTCModule(_Base):
             ts = self._stamp_tensors = [t for m in (self.audio_transform, self.encoder, self.decoder)
                                         for t in list(m.parameters()) + list(m.buffers())]
             self.__dict__["_stamp_epoch"] = epoch
-        return sum(t._version for t in ts) + (epoch << 48)
+        return sum(t._version for t in ts) + (epoch << 48) + (int(bool(self.fused_head)) << 47)
 
     def reset_inference_graphs(self) -> None:
         self.__dict__.pop("_stamp_tensors", None)
         self.__dict__.pop("_infer_graphs", None)
         self.__dict__.pop("_graph_auto", None)
+        self.__dict__.pop("_frozen_head", None)
 
     def train(self, mode: bool = True):
         self.reset_inference_graphs()
@@ -178,13 +182,52 @@ class BaseCTCModule(_Base):
         graphed = getattr(self, "_frozen_graph", None)
         if graphed is not None and x.is_cuda and not self.encoder.training and \
                 not any(p.requires_grad for p in self.encoder.parameters()):
+            if self._fused_head_ok(x):                             # inference on the frozen encoder: the same launches as without the graph
+                return self._frozen_head_forward(x, lengths)
             encoded, out_lengths = graphed(x, lengths)             # front end + frozen encoder replayed from a hipGraph
             return self.decoder(encoded), out_lengths
         from . import tensors as _t
         with _t.lengths_scope():       # the front end's frame lengths reach the encoder with their int32 copy already made
             features, feature_lengths = self.audio_transform(x, lengths)
+            if self._fused_head_ok(x):
+                fused = self.encoder.forward_head(features, feature_lengths, self.decoder)
+                if fused is not None:
+                    return fused
             encoded, out_lengths = self.encoder(features, feature_lengths)
         return self.decoder(encoded), out_lengths
+
+    def _frozen_head_forward(self, x: Tensor, lengths: Tensor) -> Tuple[Tensor, Optional[Tensor]]:
+        """graph_frozen_encoder() while the fused head applies: the graph ends in ts_qn_head_fwd instead of the last block, so a forward gives
+        the bits it gives without the graph.  The decoder's packed weights are captured with it: the graph is dropped when they change (the
+        decoder is what trains over a frozen encoder) and with the inference graphs (train(), .to(), load_state_dict)."""
+        from .utils import GraphedForward
+        dec = self.decoder
+        key = tuple((t.data_ptr(), t._version) for t in (dec.weight, dec.bias))
+        cur = self.__dict__.get("_frozen_head")
+        if cur is None or cur[0] != key:
+            cur = self.__dict__["_frozen_head"] = (key, GraphedForward(
+                lambda xx, ll: self.encoder.forward_head(*self.audio_transform(xx, ll), dec)))
+        logits, out_lengths = cur[1](x, lengths)
+        return logits.clone(), out_lengths                         # the caller may keep them: never hand out the graph's buffer
+
+    def _fused_head_ok(self, x: Tensor) -> bool:
+        """The last encoder block and the decoder may run as one launch (EncoderSequential.forward_head): inference only (eval mode, no
+        autograd, GPU), a QuartzNet-shaped end (EncoderSequential.head_block) in front of a conv1d decoder of at most 32 classes, and no
+        forward hook that would want to see the tensor in between.  Whether the kernel takes the geometry is forward_head's business."""
+        if not self.fused_head or not x.is_cuda or torch.is_grad_enabled():
+            return False
+        enc, dec = self.encoder, self.decoder
+        if self.training or enc.training or dec.training:
+            return False
+        from .blocks import _Conv1dDecoder
+        from .quartznet.blocks import EncoderSequential
+        if not isinstance(enc, EncoderSequential) or type(dec) is not _Conv1dDecoder or dec.out_channels > 32:
+            return False
+        last = enc.head_block()
+        if last is None or last.training or dec.in_channels != last.mconv[0].conv.out_channels:
+            return False
+        hooked = lambda m: bool(m._forward_hooks or m._forward_pre_hooks)
+        return not (hooked(enc) or hooked(last) or hooked(dec))
 
     def graph_frozen_encoder(self, enable: bool = True) -> "BaseCTCModule":
         """Opt-in (no reference counterpart): while the encoder is frozen and in eval mode -- the first phase of the reference's
@@ -192,6 +235,7 @@ class BaseCTCModule(_Base):
         ~80 kernels from Python every step.  The encoder output then lives in the graph's buffer until the next forward."""
         from .utils import GraphedForward
         self._frozen_graph = GraphedForward(lambda x, lengths: self.encoder(*self.audio_transform(x, lengths))) if enable else None
+        self.__dict__.pop("_frozen_head", None)
         return self
 
     def predict(self, x: Tensor) -> List[str]:

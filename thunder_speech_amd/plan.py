@@ -125,6 +125,22 @@ def pack_pw_frags16(wf: torch.Tensor) -> torch.Tensor:
     return fr.reshape(cop // 16, cip // 32, 64, 8).to(torch.bfloat16).contiguous()
 
 
+def pack_head_wd(w: torch.Tensor) -> torch.Tensor:
+    """w: [V <= 32, H] decoder weights (H a multiple of 64) -> bf16 [H / 64, 2, 2, 64, 8], the A fragments of v_mfma_f32_16x16x32_bf16 for
+    logitsT[v][t] += Wd[v][c] hT[c][t] in ts_qn_head_fwd (thunder_speech_amd/qn_head.h).
+
+    Fragment (g, p, vt), lane l (n = l & 15, kg = l >> 4), element e  =  W[16 vt + n][64 g + 16 (2 p + (e >> 2)) + 4 kg + (e & 3)], 0 for rows
+    >= V: the k-order of the fragment is the order in which a lane of the first product holds its hidden channels -- four accumulators
+    (channels 4 kg .. 4 kg + 3) of each of two 16-channel tiles -- so that the packed accumulators are the B fragment as they stand."""
+    v, h = w.shape
+    if v > 32 or h % KC:
+        raise ValueError(f"pack_head_wd: {v} classes x {h} channels (at most 32 classes, channels a multiple of {KC})")
+    wp = torch.zeros(32, h, dtype=torch.float32, device=w.device)
+    wp[:v] = w
+    fr = wp.view(2, 16, h // 64, 2, 2, 4, 4).permute(2, 3, 0, 5, 1, 4, 6)      # [vt][n][g][p][tile of the pair][kg][i] -> [g][p][vt][kg][n][tile][i]
+    return fr.reshape(h // 64, 2, 2, 64, 8).to(torch.bfloat16).contiguous()
+
+
 def pad_bias(b: torch.Tensor) -> torch.Tensor:
     out = torch.zeros(round_up(b.shape[0], 32), dtype=torch.float32, device=b.device)
     out[: b.shape[0]] = b

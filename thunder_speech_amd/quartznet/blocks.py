@@ -16,6 +16,7 @@ import torch
 from torch import nn
 from torch.nn.common_types import _size_1_t
 
+from .. import _lib
 from .. import plan as _plan
 from .. import tensors as _t
 from ..blocks import Masked, MultiSequential, _PackedCache, get_same_padding
@@ -370,6 +371,54 @@ class EncoderSequential(MultiSequential):
                 else:
                     x, audio_lengths = blk(x, audio_lengths)
         return x, audio_lengths
+
+    def head_block(self):
+        """The last block when it is what ts_qn_head_fwd fuses with the decoder -- one non-separable kernel-1 sub-block (1x1 conv + BN + ReLU),
+        stride 1, no residual, no squeeze-excite, behind at least one other fused block -- else None."""
+        blocks = list(self.children())
+        if len(blocks) < 2 or not all(isinstance(blk, _FusedBlockBase) for blk in blocks):
+            return None
+        last = blocks[-1]
+        if last.separable or last.repeat != 1 or last.res is not None or last._has_se():
+            return None
+        pw = last.mconv[0]
+        if pw.kernel_size != 1 or pw.stride != 1 or pw.padding != 0 or pw.conv.groups != 1 or pw.conv.bias is not None:
+            return None
+        return last
+
+    def forward_head(self, audio: torch.Tensor, audio_lengths: torch.Tensor, decoder) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+        """forward() followed by `decoder` (a conv1d decoder of at most 32 classes), with the last block and the decoder as ONE launch
+        (ts_qn_head_fwd): the last block's output never reaches memory.  The logits are what the two launches give -- the hidden tensor rounded to
+        bf16 as it is stored today, unmasked (frames beyond a clip's length keep the values the reference leaves there, quirk A2) -- up to the
+        order of the f32 sums of the decoder.  A geometry the library refuses runs as today's two launches; None (nothing has run) when the encoder
+        does not end in such a block or is in training mode."""
+        _t.require_gpu(audio, "encoder")
+        last = self.head_block()
+        if last is None or self.training:
+            return None
+        with _t.lengths_scope():
+            x = audio if _t.is_internal(audio) else _t.pack(audio, audio_lengths, slot=("enc", id(self)))
+            blocks = list(self.children())
+            for i, blk in enumerate(blocks[:-1]):
+                x, audio_lengths, _ = blk._run_fused(x, audio_lengths, internal=True, slot=(id(self), i % 2))
+            layer = last._cache.get(last._params(), last._compile)[0]
+            out = None
+            if _t.is_tail_zero(x) and layer.pw16 is not None:
+                b, _, t = x.shape
+                xb = _t.backing(x)
+                dec = decoder._layer()
+                wd = decoder._head_fragments()
+                logits = torch.empty(b, decoder.out_channels, _lib.time_pitch(t), device=x.device, dtype=torch.float32)
+                st = _lib.lib().ts_qn_head_fwd(xb.data_ptr(), None, layer.pw16.data_ptr(), layer.bias.data_ptr(), wd.data_ptr(), dec.bias.data_ptr(),
+                                               logits.data_ptr(), b, layer.c_in, layer.c_out, decoder.out_channels, t, xb.shape[2], logits.shape[2],
+                                               layer.kernel, layer.stride, layer.c_res, torch.cuda.current_stream(x.device).cuda_stream)
+                if st != _lib.TS_EUNSUPPORTED:
+                    _lib.check(st, "ts_qn_head_fwd")
+                    out = logits[:, :, :t]
+            if out is None:          # today's two launches
+                y, audio_lengths, _ = last._run_fused(x, audio_lengths, internal=False, slot=(id(self), (len(blocks) - 1) % 2))
+                out = decoder(y)
+        return out, audio_lengths
 
 
 def stem(feat_in: int) -> QuartznetBlock:
