@@ -1,5 +1,5 @@
-// The row code of the MMS attention adapter, shared by its inference / training forward (mms_adapter_kernel, csrc/mms.hip) and its backward
-// (csrc/mms_adapter_train.hip).  Workgroup = 16 rows, NW waves; the row tile lives in registers, split by columns: the columns come in chunks of
+// The row code of the MMS attention adapter, shared by its inference / training forward (mms_adapter_kernel, csrc/mms.hip), the language bank's
+// forward (mms_lang_adapter_kernel, csrc/mms_lang_bank.hip) and its backward (csrc/mms_adapter_train.hip).  Workgroup = 16 rows, NW waves; the row tile lives in registers, split by columns: the columns come in chunks of
 // 16, wave w owns chunks w NQ .. w NQ + NQ - 1, and lane (row = lane & 15, g = lane >> 4) holds columns 16 q + 4 g .. + 3 of its row for each of
 // them (one f32x4 per chunk).  That is the accumulator layout of a 16 x 16 MFMA whose N index is the row and whose M index is the column, so both
 // kinds of product run on the matrix cores without moving the tile:
@@ -26,8 +26,36 @@ struct AdArgs {
   float* y_next;
   unsigned short* y_next16;
 };
-// launches mms_adapter_kernel for checked arguments (csrc/mms.hip): the one place that maps c to a tile shape
+// launches mms_adapter_kernel for checked arguments (csrc/mms.hip)
 int adapter_launch(const AdArgs& p, int precision, hipStream_t stream);
+
+// The argument checks of ts_mms_attn_adapter_fwd (thunder_speech_amd/mms.h) that do not concern the number of rows: 0, TS_EINVAL or TS_EUNSUPPORTED
+inline int ad_check_args(const float* h, int c, int a, const float* norm_w, const float* norm_b, const void* w1, const float* b1, const void* w2,
+                         const float* b2, const float* next_w, const float* next_b, const float* y_next, const void* y_next_op, int precision) {
+  if (!h || !norm_w || !norm_b || !w1 || !b1 || !w2 || !b2 || c <= 0 || a <= 0) return TS_EINVAL;
+  if (next_w && (!next_b || (!y_next && !y_next_op))) return TS_EINVAL;
+  if (a % 16 || a > 64 || c % 8 || c > 4096 || precision < 0 || precision > 1 || (y_next_op && !precision)) return TS_EUNSUPPORTED;
+  if (misaligned(h) || misaligned(norm_w) || misaligned(norm_b) || misaligned(w1) || misaligned(b1) || misaligned(w2) || misaligned(b2) ||
+      misaligned(next_w) || misaligned(next_b) || misaligned(y_next) || misaligned(y_next_op, 7))
+    return TS_EUNSUPPORTED;
+  return TS_OK;
+}
+
+// The one place that maps c to a tile shape: f(NQ, NW) as integral constants.  NW waves x NQ chunks of 16 columns cover c.  At most 10 chunks
+// per wave up to c = 2048: 72 .. 122 VGPRs, no scratch, occupancy 4 (compiler's report); wider rows (no published checkpoint has them) take 16
+// chunks on 16 waves, where the 128-VGPR budget of 1024 threads makes the compiler spill: 93 VGPRs (184 bytes of scratch) in the bf16 kernel,
+// 388 (180 bytes) in the f32 one.  The shape fixes the order of every sum of a row, so launchers that must agree bit for bit share it.
+template <int V>
+struct AdInt { static constexpr int value = V; };
+template <class F>
+inline void ad_tile_shape(int c, F&& f) {
+  if (c <= 256) f(AdInt<4>{}, AdInt<4>{});
+  else if (c <= 512) f(AdInt<8>{}, AdInt<4>{});
+  else if (c <= 1024) f(AdInt<8>{}, AdInt<8>{});
+  else if (c <= 1280) f(AdInt<10>{}, AdInt<8>{});
+  else if (c <= 2048) f(AdInt<8>{}, AdInt<16>{});
+  else f(AdInt<16>{}, AdInt<16>{});
+}
 
 constexpr int AD_WAVES = 4;    // waves per SIMD the register budget is set for: the launch is bound by memory, the resident workgroups overlap their phases
 // The chunk loops are fully unrolled (the tile is a register array) and the scheduler would hoist every chunk's weight loads to the top: twice the
@@ -203,6 +231,96 @@ __device__ __forceinline__ f32x4 ad_out_chunk(f32x4 acc, const float* w, int cm,
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(cm < c ? w2r[sidx * step] : 0.f, zf[sidx], acc, 0, 0, 0);
   }
   return acc;
+}
+
+// ---- the adapter's forward on one workgroup's 16 rows, with the LayerNorm behind it: the body of mms_adapter_kernel (csrc/mms.hip) and of the
+// language bank's kernel (csrc/mms_lang_bank.hip), which differ in where a tile's rows and tensors lie.  `row`: the lane's row of p.h / p.in /
+// p.y_next; !row_ok: a row past the end, which repeats a valid one and is never stored.  Every weight is read once per workgroup (from L2) for
+// its 16 rows: 2 a c / 16 values per row next to the row's own 2 c.
+template <int NQ, int NW, bool BF>
+__device__ __forceinline__ void ad_fwd_tile(const AdArgs& p, long long row, bool row_ok) {
+  __shared__ float red[4][NW * 16];
+  __shared__ __attribute__((aligned(16))) float zp[NW][16][AD_ZP];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // scalar: the tests on the wave's columns below are uniform branches
+  const int rl = lane & 15, g = lane >> 4;
+  const long long row_off = row * p.c;
+  float* hr = p.h + row_off;
+  const int c = p.c, a = p.a;
+  const int col0 = 16 * wave * NQ + 4 * g;                      // the lane's columns of chunk i: col0 + 16 i + 0..3
+  f32x4 v[NQ];
+  float mu, rs;
+  ad_load_stats<NQ, NW>(p.in ? p.in + row_off : hr, c, col0, v, red[0], red[1], wave, rl, g, mu, rs);
+
+  // ---- z = LN(h) W1^T: this wave's columns; the partial tile goes to zp[wave][row][j]
+  ad_prod_in<NQ, NW, BF, false>([&](int i) { return ad_xhat(v[i], col0 + 16 * i, c, mu, rs, p.norm_w, p.norm_b); }, p.w1, c, a, wave, rl, g, col0, zp);
+  __syncthreads();
+  // relu(z + b1)[row][j], summed over the waves in a fixed order
+  auto zval = [&](int j) -> float {
+    if (j >= a) return 0.f;
+    return fmaxf(ad_zsum<NW>(zp, p.b1[j], rl, j), 0.f);
+  };
+
+  // ---- h^T += W2 relu(z)^T, chunk by chunk; then + b2
+  if constexpr (BF) {
+    s16x8 zb[2];
+    ad_out_b(zval, g, zb);
+    const unsigned short* w2 = static_cast<const unsigned short*>(p.w2);
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+      const int cm = 16 * (wave * NQ + i) + rl;                  // A operand: this lane's W2 row (= output column)
+      if (cm - rl >= c) break;                                   // uniform
+      v[i] = ad_out_chunk<false>(v[i], w2, cm, c, a, g, zb);
+      if (i % 4 == 3 && i + 1 < NQ) AD_FENCE;
+    }
+  } else {
+    float zf[16];
+    ad_out_b(zval, g, zf);
+    const float* w2 = static_cast<const float*>(p.w2);
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+      const int cm = 16 * (wave * NQ + i) + rl;
+      if (cm - rl >= c) break;
+      v[i] = ad_out_chunk<false>(v[i], w2, cm, c, a, g, zf);
+      if (i % 4 == 3 && i + 1 < NQ) AD_FENCE;
+    }
+  }
+  AD_MFMA_DRAIN;                                                 // as above, before the tile's accumulators are read by vector instructions
+  float s2 = 0.f;
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) {
+    const int col = col0 + 16 * i;
+    if (col < c) {
+      v[i] += *reinterpret_cast<const f32x4*>(p.b2 + col);
+      if (row_ok) *reinterpret_cast<f32x4*>(hr + col) = v[i];
+      s2 += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+    }
+    if (i % 4 == 3) AD_FENCE;
+  }
+  if (!p.next_w) return;                                         // uniform
+
+  // ---- the LayerNorm that follows, on the updated row
+  const float mu2 = ad_row_sum<NW>(s2, red[2], wave, rl, g) / c;
+  float q2 = 0.f;
+#pragma unroll
+  for (int i = 0; i < NQ; ++i)
+    if (col0 + 16 * i < c) {
+      const f32x4 d = v[i] - mu2;
+      q2 += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+    }
+  const float rs2 = rsqrtf(ad_row_sum<NW>(q2, red[3], wave, rl, g) / c + p.next_eps);
+  if (!row_ok) return;
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) {
+    const int col = col0 + 16 * i;
+    if (col < c) {
+      const f32x4 w4 = *reinterpret_cast<const f32x4*>(p.next_w + col), b4 = *reinterpret_cast<const f32x4*>(p.next_b + col);
+      const f32x4 y = (v[i] - mu2) * rs2 * w4 + b4;
+      if (p.y_next) *reinterpret_cast<f32x4*>(p.y_next + row_off + col) = y;
+      if (p.y_next16) *reinterpret_cast<uint2*>(p.y_next16 + row_off + col) = uint2{pack_bf16(y[0], y[1]), pack_bf16(y[2], y[3])};
+    }
+    if (i % 4 == 3) AD_FENCE;
+  }
 }
 
 }  // namespace ts

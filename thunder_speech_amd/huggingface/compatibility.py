@@ -74,7 +74,10 @@ def load_huggingface_checkpoint(model_name: str, target_lang: Optional[str] = No
     `target_lang` (MMS: "facebook/mms-1b-all" and its kin) selects one language of a multilingual checkpoint: transformers loads that
     language's `adapter.<lang>.safetensors` (attention adapters and lm_head, which it resizes: `ignore_mismatched_sizes=True` unless the caller
     set it) and the tokenizer takes that language's entry of the nested vocab.json, so the decoder and text_transform are that language's.
-    Another language needs another module: load the checkpoint again.
+    Further languages of the same checkpoint are served by the same module, every clip of a batch with its own:
+        module.language_bank(target_lang, capacity=8)               # the loaded language becomes slot 0 of a bank
+        module.language_bank_load(dir, ["fra", "deu"])              # adapter.<lang>.safetensors + that entry of vocab.json
+        texts = module.predict_languages(x, ["fra", None, "deu"])   # None: the loaded language
 
     Teaching such a checkpoint a new language trains the attention adapters and the CTC head on the frozen base:
         module = load_huggingface_checkpoint(dir, target_lang=...)

@@ -479,11 +479,19 @@ class Wav2Vec2Plan:
         _lib.check(st, "ts_w2v_layernorm_fwd")
         return y, (y_op if self.prec else y)
 
-    def _attn_adapter(self, L, stream, h, ad, next_ln, last: bool):
+    # ---- a bank of MMS languages (BaseCTCModule.language_bank): None, or the LanguageBank whose adapters replace this plan's own, per clip ------
+    lang_bank = None
+
+    def _attn_adapter(self, L, stream, h, lw, next_ln, last: bool):
         """h += adapter(h) in place, and LN(h; next_ln) in the same launch: the next layer's layer_norm as the GEMM operand of its QKV product, or
-        (`last`) encoder.layer_norm as the f32 result of the encoder.  -> (f32 result or None, GEMM operand or None)."""
+        (`last`) encoder.layer_norm as the f32 result of the encoder.  -> (f32 result or None, GEMM operand or None).  The adapter is layer
+        `lw`'s own, or with a language bank the one of each clip's language (ts_mms_lang_bank_adapter_fwd, the same arithmetic)."""
         y = torch.empty_like(h) if (last or not self.prec) else None
         y_op = self._op(*h.shape) if (self.prec and not last) else None
+        if self.lang_bank is not None:
+            self.lang_bank.adapter(L, stream, h, lw["index"], next_ln, self.eps, y, y_op, self.prec)
+            return y, (y_op if self.prec else y)
+        ad = lw["ad"]
         a = ad["w1"].shape[0]
         st = L.ts_mms_attn_adapter_fwd(h.data_ptr(), h.shape[0] * h.shape[1], h.shape[2], a, ad["norm"][0].data_ptr(), ad["norm"][1].data_ptr(),
                                        ad["w1"].data_ptr(), ad["b1"].data_ptr(), ad["w2"].data_ptr(), ad["b2"].data_ptr(), next_ln[0].data_ptr(),
@@ -594,7 +602,7 @@ class Wav2Vec2Plan:
                 if "ad" in lw:
                     # MMS: h += adapter(h); the launch also computes the LayerNorm that reads h next -- layer i + 1's, or the encoder's
                     last = i + 1 == len(self.layers)
-                    y, x_op = self._attn_adapter(L, stream, h, lw["ad"], self.enc_ln if last else self.layers[i + 1]["ln1"], last)
+                    y, x_op = self._attn_adapter(L, stream, h, lw, self.enc_ln if last else self.layers[i + 1]["ln1"], last)
             if self.layers and "ad" in self.layers[-1]:
                 h = y
             else:
@@ -1015,6 +1023,13 @@ class HuggingFaceEncoderAdapt(nn.Module):
             if bank.device != device:
                 bank.to(device)
                 self._param_epoch = getattr(self, "_param_epoch", 0) + 1
+        lang_bank = self.__dict__.get("_language_bank")
+        if lang_bank is not None:
+            # the language bank (BaseCTCModule.language_bank) follows the base the same way
+            device = next(self.original_encoder.parameters()).device
+            if lang_bank.device != device:
+                lang_bank.to(device)
+                self._param_epoch = getattr(self, "_param_epoch", 0) + 1
         return out
 
     def _bank_for(self, x: torch.Tensor, check_only: bool = False) -> Optional[LoraBank]:
@@ -1076,6 +1091,9 @@ class HuggingFaceEncoderAdapt(nn.Module):
         return out
 
     def forward(self, audio: torch.Tensor, audio_lengths: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        lang_bank = self.__dict__.get("_language_bank")
+        if self.training and lang_bank is not None:
+            raise NotImplementedError("wav2vec2 encoder: training with a language bank (BaseCTCModule.language_bank) is not implemented")
         if self.training:
             # fine-tuning (module.py:102-127 through this adapter): transformers' training-mode forward -- frozen conv feature extractor, time
             # masking, dropouts, LayerDrop -- as a chain of autograd nodes on the HIP kernels.  What the family's chain has no backward for
@@ -1092,6 +1110,10 @@ class HuggingFaceEncoderAdapt(nn.Module):
         else:
             plan = self._plan(x.device)
             plan.bank = self._bank_for(x)
+            if lang_bank is not None and lang_bank.device != x.device:
+                lang_bank.to(x.device)                                         # new addresses: retire the graphs captured on the old ones
+                self._param_epoch = getattr(self, "_param_epoch", 0) + 1
+            plan.lang_bank = lang_bank
             h = plan.forward(x, audio_lengths if self.mask_input else None)
         cfg = self.original_encoder.config
         n_ad = int(cfg.num_adapter_layers) if getattr(cfg, "add_adapter", False) else 0

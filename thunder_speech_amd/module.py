@@ -179,6 +179,8 @@ class BaseCTCModule(_Base):
         return self._forward_eager(x, lengths)
 
     def _forward_eager(self, x: Tensor, lengths: Tensor) -> Tuple[Tensor, Optional[Tensor]]:
+        if self.__dict__.get("_language_bank") is not None:
+            return self._language_bank_forward(x, lengths)
         graphed = getattr(self, "_frozen_graph", None)
         if graphed is not None and x.is_cuda and not self.encoder.training and \
                 not any(p.requires_grad for p in self.encoder.parameters()):
@@ -195,6 +197,17 @@ class BaseCTCModule(_Base):
                     return fused
             encoded, out_lengths = self.encoder(features, feature_lengths)
         return self.decoder(encoded), out_lengths
+
+    def _language_bank_forward(self, x: Tensor, lengths: Tensor) -> Tuple[Tensor, Optional[Tensor]]:
+        """The forward with a language bank (language_bank()): the encoder takes every clip's attention adapters from the bank, and
+        ts_mms_lang_bank_head_fwd stands in place of the decoder -- logits [B, v_pad, T'], the classes beyond a clip's vocabulary at -1e30."""
+        from . import tensors as _t
+        from .huggingface import language_bank as LB
+        bank = LB.check_forward(self, x)                           # the refusals, by name, before any device work
+        with _t.lengths_scope():
+            features, feature_lengths = self.audio_transform(x, lengths)
+            encoded, out_lengths = self.encoder(features, feature_lengths)
+        return bank.head(encoded.transpose(-1, -2)), out_lengths   # the encoder's [B, C, T'] is a view of its time-major result
 
     def _frozen_head_forward(self, x: Tensor, lengths: Tensor) -> Tuple[Tensor, Optional[Tensor]]:
         """graph_frozen_encoder() while the fused head applies: the graph ends in ts_qn_head_fwd instead of the last block, so a forward gives
@@ -247,6 +260,9 @@ class BaseCTCModule(_Base):
         else:
             pred, _ = self._forward_eager(x, audio_lengths)
             _, collapsed, counts = greedy_decode(pred)
+        if self.__dict__.get("_language_bank") is not None:
+            from .huggingface import language_bank as LB
+            return LB.decode(self, collapsed, counts)              # clip i with the text transform of the language selected for it
         return self.text_transform.decode_collapsed(collapsed, counts)
 
     def predict_adapted(self, x: Tensor, adapters) -> List[str]:
@@ -261,6 +277,71 @@ class BaseCTCModule(_Base):
             return self.predict(x)
         finally:
             self.encoder.select_adapters(previous)
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # Many MMS languages on one module (no reference counterpart; huggingface/language_bank.py, csrc/mms_lang_bank.hip): a bank of language packs
+    # -- the attention adapters of every layer and a CTC head -- next to the one packed base of an MMS checkpoint; every clip of a batch picks
+    # its language by name.  The bank's tensors are plain attributes at fixed addresses (state_dict() does not change): adding, removing and
+    # selecting write in place, so captured graphs keep replaying.  A module without a bank runs the launches it ran before.
+    def language_bank(self, name: str, capacity: int = 8, max_vocab: Optional[int] = None) -> None:
+        """Create a bank of `capacity` language slots and put the language this module was loaded with -- the encoder's attention adapters,
+        `decoder[2]` and `text_transform` as they are now -- into slot 0 under `name`: the resident language, which serves every clip that
+        selects nothing else and cannot be removed.  `max_vocab`: the largest vocabulary the bank takes (a multiple of 16; default: the
+        resident vocabulary rounded up); forward() then returns [B, max_vocab, T'] with the classes beyond a clip's vocabulary at -1e30.
+        Refused by name: an encoder without attention adapters, precision="mxfp8", a second bank."""
+        from .huggingface import language_bank as LB
+        LB.create(self, name, capacity, max_vocab)
+
+    def language_bank_add(self, lang: str, adapter_sd: Dict[str, Tensor], tokens: List[str]) -> int:
+        """Put a language into a free slot: `adapter_sd` with exactly the keys of transformers' `model._get_adapters()` (the contents of an
+        adapter.<lang>.safetensors: the attention adapters and lm_head), `tokens` its vocabulary in id order.  Returns the slot.  Written in
+        place: captured graphs stay valid.  Refused by name: a duplicate name, a full bank, wrong keys or shapes, a vocabulary larger than
+        max_vocab, a blank index other than the resident language's (the greedy decode of a batch has one blank)."""
+        from .huggingface import language_bank as LB
+        return LB.add(self, lang, adapter_sd, tokens)
+
+    def language_bank_load(self, model_dir: str, langs) -> List[int]:
+        """language_bank_add for each of `langs` from a local checkpoint directory: adapter.{lang}.safetensors and that language's entry of the
+        nested vocab.json.  Returns the slots."""
+        from .huggingface import language_bank as LB
+        return LB.load(self, model_dir, langs)
+
+    def language_bank_remove(self, lang: str) -> None:
+        """Zero and free the slot of `lang`; clips that selected it go back to the resident language.  Slot 0 cannot be removed."""
+        from .huggingface import language_bank as LB
+        LB.remove(self, lang)
+
+    def language_bank_names(self) -> List[str]:
+        """The languages in the bank, in slot order (the resident one first)."""
+        from .huggingface import language_bank as LB
+        return LB.names(self)
+
+    def select_languages(self, langs) -> None:
+        """One entry per clip of the batches to come: a language of the bank, or None for the resident one; clips beyond the given entries get
+        the resident language.  One host-to-device copy into the bank's id buffer: nothing is re-captured."""
+        from .huggingface import language_bank as LB
+        LB.select(self, langs)
+
+    def selected_languages(self) -> List[Optional[str]]:
+        """What select_languages() was last given (a copy; [] after language_bank())."""
+        from .huggingface import language_bank as LB
+        return list(LB._bank(self, "selected_languages").selection)
+
+    def predict_languages(self, x: Tensor, langs) -> List[str]:
+        """predict(x) with clip i served by the language `langs[i]` of the bank (None: the resident one) and decoded with that language's
+        vocabulary; the selection that held before the call holds again after it."""
+        previous = self.selected_languages()
+        self.select_languages(langs)
+        try:
+            return self.predict(x)
+        finally:
+            self.select_languages(previous)
+
+    def _one_language(self, what: str) -> None:
+        """`what` turns text into ids, or carries an LM, of one language: refused by name while any clip selects a non-resident language."""
+        if self.__dict__.get("_language_bank") is not None:
+            from .huggingface import language_bank as LB
+            LB.refuse_mixed(self, what)
 
     # ------------------------------------------------------------------------------------------------------------------
     # "When was it said" (no reference counterpart): forced alignment of known transcripts and the spans of the greedy transcript, on the
@@ -327,6 +408,7 @@ class BaseCTCModule(_Base):
         """Forced alignment of `texts` to the clips `x` [batch, time]: per clip the score (sum of the best path's log-probabilities) and
         one TokenSpan per token of the encoded transcript (token, start / end in seconds and in frames, log-probability).  A transcript that
         does not fit its clip gives score -inf and no tokens instead of raising: one bad transcript does not fail a batch."""
+        self._one_language("align")
         from . import ctc_align as A
         logits, out_lengths = self._eval_logits(x, lengths)
         y, y_lengths = self.text_transform.encode(list(texts), device=x.device)
@@ -340,6 +422,7 @@ class BaseCTCModule(_Base):
         the tokens, with the separators read as spaces, gives predict(x) as called under no_grad (this method always runs the inference
         forward; predict() follows the caller's grad mode, and a decoder with trainable parameters takes its f32 training path under grad).
         The clip's score is the sum of its tokens' log-probabilities."""
+        self._one_language("predict_spans")
         from . import ctc_align as A
         logits, _ = self._eval_logits(x, None)
         gs = A.greedy_spans(logits, None, self.text_transform.vocab.blank_idx)
@@ -354,6 +437,7 @@ class BaseCTCModule(_Base):
         """The search that `lm`'s type asks for, on `logits` with their `lengths` (None: every frame): none, the token-level ctc_lm.NGramLM, or
         the word-level ctc_lm.WordNGramLM with its lexicon and hot words.  `logits` may be a function that returns (logits, lengths): the
         keywords are checked before it runs."""
+        self._one_language(what)
         from . import ctc_beam as B
         from . import ctc_lm as M
         blank, word_level = self.text_transform.vocab.blank_idx, isinstance(lm, M.WordNGramLM)
@@ -455,6 +539,7 @@ class BaseCTCModule(_Base):
         Nothing synchronises with the host between the batches.  A recording that fits one window runs as one clip of its own length: its row
         is what `module(x[None], ...)` gives.  A LoRA bank selection (select_adapters) holds for every batch of windows as it does for predict:
         entry i serves row i of each batch."""
+        self._one_language("logits_long (transcribe_long, predict_spans_long, align_long)")
         from . import longform as LF
         recs = self._long_recordings("logits_long", recordings)
         dev, spf, sr = recs[0].device, self.samples_per_frame, self.sample_rate
