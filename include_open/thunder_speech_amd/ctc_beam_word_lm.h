@@ -44,8 +44,8 @@
  *   SUPPORTED: beam_width <= 64, token_cap <= 64 and beam_width (cap + 1) <= 1024, as in ctc_beam_lm.h.
  *   Outputs: those of ts_ctc_beam_lm_search.
  *
- * Next steps, NOT in this ABI: sentencepiece vocabularies, where a word starts at a U+2581 piece (those keep the token-level LM of ctc_beam_lm.h);
- * LM look-ahead inside a word; boosting of partial hot-word matches; neural LMs (rescore the n-best list on the host for those); candidate sets
+ * Next steps, NOT in this ABI: sentencepiece vocabularies, where a word starts at a U+2581 piece (those have ctc_beam_piece_lm.h, which reuses the
+ * structs of this header); LM look-ahead inside a word; boosting of partial hot-word matches; neural LMs (rescore the n-best list on the host for those); candidate sets
  * beyond 1024.
  */
 #ifndef THUNDER_SPEECH_AMD_CTC_BEAM_WORD_LM_H

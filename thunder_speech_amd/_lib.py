@@ -114,9 +114,30 @@ COMPANIONS = {os.path.basename(p)[:-len(".h")]: _read_installed_header(p) for p 
 STAGED = {os.path.basename(p)[:-len(".h")]: _read_installed_header(p) for p in sorted(glob.glob(os.path.join(STAGED_DIR, "*.h")))}
 # queued companions: the same again, for headers that arrived while the staged set was pinned too
 QUEUED = {os.path.basename(p)[:-len(".h")]: _read_installed_header(p) for p in sorted(glob.glob(os.path.join(QUEUED_DIR, "*.h")))}
-# open companions: the same once more, in a table without a pinned length; one of them may include a companion and take its structs
+# open companions: the same once more, in a table without a pinned length; one of them may include a companion, or another open companion, and
+# take its structs
 _companion_structs = {n: s for h in COMPANIONS.values() for n, s in h.structs.items()}
-OPEN = {os.path.basename(p)[:-len(".h")]: _read_installed_header(p, _companion_structs) for p in sorted(glob.glob(os.path.join(OPEN_DIR, "*.h")))}
+OPEN = {}
+
+
+def _read_open_header(key: str, above=()) -> Header:
+    """The open companion `key`, read after the open companions it includes: the structs of those read before it are known to it."""
+    path = os.path.join(OPEN_DIR, key + ".h")
+    if key in above:
+        raise RuntimeError(f"thunder_speech_amd: the C header {path} includes itself")
+    if key not in OPEN:
+        with open(path) as f:
+            code = re.sub(r"/\*.*?\*/|//[^\n]*", " ", f.read(), flags=re.S)
+        for inc in re.findall(r'^\s*#\s*include\s+"thunder_speech_amd/(\w+)\.h"', code, flags=re.M):
+            if os.path.exists(os.path.join(OPEN_DIR, inc + ".h")):
+                _read_open_header(inc, (*above, key))
+        OPEN[key] = _read_installed_header(path, {**_companion_structs, **{n: s for h in OPEN.values() for n, s in h.structs.items()}})
+    return OPEN[key]
+
+
+for _p in sorted(glob.glob(os.path.join(OPEN_DIR, "*.h"))):
+    _read_open_header(os.path.basename(_p)[:-len(".h")])
+OPEN = {k: OPEN[k] for k in sorted(OPEN)}
 _declared_in = {}
 for _h in (CORE, *COMPANIONS.values(), *STAGED.values(), *QUEUED.values(), *OPEN.values()):
     for _name in _h.signatures:
@@ -125,6 +146,7 @@ for _h in (CORE, *COMPANIONS.values(), *STAGED.values(), *QUEUED.values(), *OPEN
         _declared_in[_name] = _h.path
 CtcLm = COMPANIONS["ctc_beam_lm"].structs["ts_ctc_lm"]
 CtcLexicon = OPEN["ctc_beam_word_lm"].structs["ts_ctc_lexicon"]
+CtcPieces = OPEN["ctc_beam_piece_lm"].structs["ts_ctc_pieces"]
 TcsDesc, FrontendDesc, WgradItem = STRUCTS["ts_tcs_desc"], STRUCTS["ts_frontend_desc"], STRUCTS["ts_wgrad_item"]
 TcsLaunch = STRUCTS["ts_tcs_launch"]
 EXPORTED_SYMBOLS = list(SIGNATURES)

@@ -8,7 +8,10 @@ no CPU path for the search.
 
 For the character vocabularies (QuartzNet, the wav2vec2 family) the second half of this module fuses a WORD-level ARPA LM instead: `WordNGramLM`
 compiles the words to the same automaton (word ids as classes) and spells them into a lexicon trie, with hot words; `beam_search_word_lm` runs
-csrc/ctc_beam_word_lm.hip on them (thunder_speech_amd/ctc_beam_word_lm.h)."""
+csrc/ctc_beam_word_lm.hip on them (thunder_speech_amd/ctc_beam_word_lm.h).  For the sentencepiece vocabularies (Citrinet, NeMo word-piece checkpoints
+after `fix_vocab`) the third part does the same with a trie over LETTERS: `PieceWordNGramLM` reads the same word-level ARPA file, a piece that
+begins with U+2581 starts a word, and `beam_search_piece_lm` runs csrc/ctc_beam_piece_lm.hip (thunder_speech_amd/ctc_beam_piece_lm.h); the
+token-level `NGramLM` over pieces remains for LMs that were trained on pieces."""
 from __future__ import annotations
 
 import math
@@ -305,7 +308,7 @@ def beam_search_lm(logits, lm: NGramLM, alpha: float, beta: float, lengths=None,
 # ---- word-level LM over a character vocabulary: lexicon trie, hot words (thunder_speech_amd/ctc_beam_word_lm.h) ---------------------------------
 class WordStep(NamedTuple):
     """What one class does to the pair (word state, lexicon state) on the host: the unweighted log10 met, the pair entered, whether the OOV
-    factor is paid here, and the lexicon word that ended here (None: none, or a word outside the lexicon)."""
+    factor is paid here (a `PieceWordNGramLM` counts how often: a piece can end one word and leave the trie with the next), and the lexicon word that ended here (None: none, or a word outside the lexicon)."""
     log10: float
     state: int
     x: int
@@ -323,35 +326,14 @@ class WordLMWeights:
     struct: object
 
 
-class WordNGramLM:
-    """A word-level back-off n-gram LM for a CHARACTER vocabulary, with the lexicon trie that spells its words in CTC classes.
+class _WordLM:
+    """What the word-level LMs share: the host walk over (word state, lexicon state) pairs and the lexicon tables of a setting.  A subclass
+    provides `lm`, `words`, `hot`, `word_class`, `unk_class`, `edges`, `node_word` and `step`."""
 
-    `words` are the lexicon's words in trie order, `spellings[w]` the classes of word w, `hot[w]` whether it is a hot word, `word_class[w]` its
-    class in the word automaton `lm` -- an `NGramLM` whose classes are the ids of the LM's spellable words (`lm_words`), then `unk_class` for
-    <unk>-as-a-word (a lexicon word the LM lacks has that class), then a class that plays the blank and is never looked up.  Trie: node 0 is the
-    root, `edges[x]` the (class, next node) pairs of node x sorted by class, `node_word[x]` the word that ends at x or -1.  Two words with one
-    spelling share a node; the first in sorted order is the node's word."""
-
-    def __init__(self, order: int, grams: Dict[Tuple[str, ...], Tuple[float, float]], itos: Sequence[str], blank_idx: int, delimiter: str = " ",
-                 lexicon=None, hotwords=(), spell: Optional[Callable[[str], str]] = None, unk_log10: float = -10.0):
-        self.n_classes, self.blank_idx = len(itos), int(blank_idx)
-        where = [c for c, tok in enumerate(itos) if tok == delimiter and c != self.blank_idx]
-        if not where:
-            raise ValueError(f"WordNGramLM: the vocabulary has no class {delimiter!r} to end a word")
-        self.delimiter = where[0]
-        letters: Dict[str, int] = {}
-        for c, tok in enumerate(itos):
-            if c not in (self.blank_idx, self.delimiter) and tok not in _SPECIAL and len(tok) == 1:
-                letters.setdefault(tok, c)
-        unspellable = set()
-
-        def spelled(word: str) -> Optional[Tuple[int, ...]]:
-            text = spell(word) if spell else word
-            if not text or any(ch not in letters for ch in text):
-                unspellable.add(word)
-                return None
-            return tuple(letters[ch] for ch in text)
-
+    def _compile(self, order: int, grams: Dict[Tuple[str, ...], Tuple[float, float]], spelled: Callable[[str], Optional[Tuple[int, ...]]],
+                 unspellable: set, lexicon, hotwords, unk_log10: float) -> None:
+        """The word automaton and the trie of the words that `spelled` can write (it returns None for the others and notes them in
+        `unspellable`); the trie's edges carry what `spelled` returns: CTC classes, or letter ids."""
         # the word automaton: the existing machinery, with word ids as classes
         lm_words = sorted({w for g in grams for w in g if w not in _SPECIAL})
         self.lm_words: List[str] = [w for w in lm_words if spelled(w) is not None]
@@ -389,16 +371,6 @@ class WordNGramLM:
         self._static: dict = {}
         self._cache: dict = {}
 
-    @classmethod
-    def from_arpa(cls, path: str, itos: Sequence[str], blank_idx: int, delimiter: str = " ", lexicon=None, hotwords=(),
-                  spell: Optional[Callable[[str], str]] = None, unk_log10: float = -10.0) -> "WordNGramLM":
-        """The word LM of an ARPA file over the character classes `itos`.  A word is kept if `spell(word)` (default: the word itself) can be
-        written in the one-character classes without the blank and without the class `delimiter`; n-grams with another word are dropped.
-        `lexicon` (an iterable of words; default: the LM's spellable unigrams) and `hotwords` form the trie; a word of either that the LM lacks
-        is scored as <unk>.  `dropped` counts the words -- of the file, the lexicon or the hot words -- that cannot be spelled."""
-        order, tables = read_arpa(path)
-        return cls(order, {g: v for t in tables for g, v in t.items()}, itos, blank_idx, delimiter, lexicon, hotwords, spell, unk_log10)
-
     # ---- lookup on the host (what the kernel does on the device tables) ----
     @property
     def n_nodes(self) -> int:
@@ -409,26 +381,12 @@ class WordNGramLM:
         return self.lm.start_state
 
     def finish(self, state: int, x: int) -> WordStep:
-        """The end of the pending word, as if a delimiter followed; nothing happens at the root."""
+        """The end of the pending word, as if a word boundary followed; nothing happens at the root."""
         if x == 0:
             return WordStep(0.0, state, 0, False, None)
         w = self.node_word[x] if x > 0 else -1
         p, nxt = self.lm.step(state, self.word_class[w] if w >= 0 else self.unk_class)
         return WordStep(p, nxt, 0, w < 0 and x > 0, w if w >= 0 else None)
-
-    def step(self, state: int, x: int, c: int) -> WordStep:
-        """Class c (neither the blank nor outside the classes) from the pair (state, x)."""
-        c = int(c)
-        if c == self.blank_idx or not 0 <= c < self.n_classes:
-            raise ValueError(f"WordNGramLM.step: class {c} is the blank, or outside the classes")
-        if c == self.delimiter:
-            return self.finish(state, x)
-        if x < 0:
-            return WordStep(0.0, state, -1, False, None)
-        for cls_, nxt in self.edges[x]:
-            if cls_ == c:
-                return WordStep(0.0, state, nxt, False, None)
-        return WordStep(0.0, state, -1, True, None)
 
     def walk(self, labels: Sequence[int], eos: bool = False) -> Tuple[float, int, List[int]]:
         """(log10 P(words [</s>]), OOV words, lexicon words in order) of a label string from the start, the pending word included."""
@@ -450,7 +408,7 @@ class WordNGramLM:
         boosts = dict(boosts or {})
         unknown = [w for w in boosts if w not in self.words or not self.hot[self.words.index(w)]]
         if unknown:
-            raise ValueError(f"WordNGramLM: boosts for {unknown}, which are not hot words of this LM")
+            raise ValueError(f"{type(self).__name__}: boosts for {unknown}, which are not hot words of this LM")
         return tuple(float(boosts.get(w, hotword_weight)) if h else 0.0 for w, h in zip(self.words, self.hot))
 
     def lexicon_tables(self, oov_score: float = -10.0, hotword_weight: float = 0.0, boosts: Optional[Dict[str, float]] = None) -> Dict[str, np.ndarray]:
@@ -465,6 +423,64 @@ class WordNGramLM:
                 "word_factor": np.exp(np.array(self.word_boosts(hotword_weight, boosts), np.float64)).reshape(-1),
                 "oov_factor": np.exp(np.array([float(oov_score)], np.float64))}
 
+
+class WordNGramLM(_WordLM):
+    """A word-level back-off n-gram LM for a CHARACTER vocabulary, with the lexicon trie that spells its words in CTC classes.
+
+    `words` are the lexicon's words in trie order, `spellings[w]` the classes of word w, `hot[w]` whether it is a hot word, `word_class[w]` its
+    class in the word automaton `lm` -- an `NGramLM` whose classes are the ids of the LM's spellable words (`lm_words`), then `unk_class` for
+    <unk>-as-a-word (a lexicon word the LM lacks has that class), then a class that plays the blank and is never looked up.  Trie: node 0 is the
+    root, `edges[x]` the (class, next node) pairs of node x sorted by class, `node_word[x]` the word that ends at x or -1.  Two words with one
+    spelling share a node; the first in sorted order is the node's word."""
+
+    def __init__(self, order: int, grams: Dict[Tuple[str, ...], Tuple[float, float]], itos: Sequence[str], blank_idx: int, delimiter: str = " ",
+                 lexicon=None, hotwords=(), spell: Optional[Callable[[str], str]] = None, unk_log10: float = -10.0):
+        self.n_classes, self.blank_idx = len(itos), int(blank_idx)
+        where = [c for c, tok in enumerate(itos) if tok == delimiter and c != self.blank_idx]
+        if not where:
+            raise ValueError(f"WordNGramLM: the vocabulary has no class {delimiter!r} to end a word")
+        self.delimiter = where[0]
+        letters: Dict[str, int] = {}
+        for c, tok in enumerate(itos):
+            if c not in (self.blank_idx, self.delimiter) and tok not in _SPECIAL and len(tok) == 1:
+                letters.setdefault(tok, c)
+        unspellable = set()
+
+        def spelled(word: str) -> Optional[Tuple[int, ...]]:
+            text = spell(word) if spell else word
+            if not text or any(ch not in letters for ch in text):
+                unspellable.add(word)
+                return None
+            return tuple(letters[ch] for ch in text)
+
+        self._compile(order, grams, spelled, unspellable, lexicon, hotwords, unk_log10)
+
+    @classmethod
+    def from_arpa(cls, path: str, itos: Sequence[str], blank_idx: int, delimiter: str = " ", lexicon=None, hotwords=(),
+                  spell: Optional[Callable[[str], str]] = None, unk_log10: float = -10.0) -> "WordNGramLM":
+        """The word LM of an ARPA file over the character classes `itos`.  A word is kept if `spell(word)` (default: the word itself) can be
+        written in the one-character classes without the blank and without the class `delimiter`; n-grams with another word are dropped.
+        `lexicon` (an iterable of words; default: the LM's spellable unigrams) and `hotwords` form the trie; a word of either that the LM lacks
+        is scored as <unk>.  `dropped` counts the words -- of the file, the lexicon or the hot words -- that cannot be spelled."""
+        order, tables = read_arpa(path)
+        return cls(order, {g: v for t in tables for g, v in t.items()}, itos, blank_idx, delimiter, lexicon, hotwords, spell, unk_log10)
+
+    # ---- lookup on the host (what the kernel does on the device tables) ----
+    def step(self, state: int, x: int, c: int) -> WordStep:
+        """Class c (neither the blank nor outside the classes) from the pair (state, x)."""
+        c = int(c)
+        if c == self.blank_idx or not 0 <= c < self.n_classes:
+            raise ValueError(f"WordNGramLM.step: class {c} is the blank, or outside the classes")
+        if c == self.delimiter:
+            return self.finish(state, x)
+        if x < 0:
+            return WordStep(0.0, state, -1, False, None)
+        for cls_, nxt in self.edges[x]:
+            if cls_ == c:
+                return WordStep(0.0, state, nxt, False, None)
+        return WordStep(0.0, state, -1, True, None)
+
+    # ---- device tables ----
     def weights(self, alpha: float, beta: float, oov_score: float = -10.0, hotword_weight: float = 0.0, boosts: Optional[Dict[str, float]] = None,
                 device=None) -> WordLMWeights:
         """The device tables of one setting, cached per (alpha, beta, oov_score, boosts of the words, device).  A NEW setting gets NEW
@@ -533,4 +549,158 @@ def beam_search_word_lm(logits, lm: WordNGramLM, alpha: float, beta: float, leng
                                       frames.data_ptr(), out_len.data_ptr(), scores.data_ptr(), lm_scores.data_ptr(), counts.data_ptr(),
                                       ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(st, "ts_ctc_beam_word_lm_search")
+    return BeamLMResult(tokens, frames, out_len, scores, counts, lm_scores)
+
+
+# ---- word-level LM over a sentencepiece vocabulary: a trie over letters, pieces that start words (thunder_speech_amd/ctc_beam_piece_lm.h) -------
+@dataclass
+class PieceLMWeights(WordLMWeights):
+    """`WordLMWeights` of a `PieceWordNGramLM`: `struct` is the ts_ctc_lexicon over letters, `pieces` the ts_ctc_pieces (its tensors are in
+    `tensors` too)."""
+    pieces: object = None
+
+
+class PieceWordNGramLM(_WordLM):
+    """A word-level back-off n-gram LM for a SENTENCEPIECE vocabulary, with the lexicon trie that spells its words in letters.
+
+    A class whose token begins with `word_start` starts a word (kind 1), any other continues one (kind 0); a LETTER is a character of some such
+    token once the leading `word_start` is stripped, and `letters` lists them in sorted order: their positions are the letter ids.
+    `piece_letters[c]` are the letter ids of class c (none for a bare `word_start`) and `piece_kind[c]` its kind.  A class whose token is <s>,
+    </s> or <unk>, or holds `word_start` anywhere but at the front, has no spelling (kind 2; `unspellable_classes` lists them): inside a word
+    it makes the word OOV.  The trie's edges carry letter ids, so every segmentation of a word reaches the same node.  `words`, `hot`,
+    `word_class`, `lm`, `lm_words`, `unk_class`, `edges`, `node_word`, `dropped` and `dropped_ngrams` are those of `WordNGramLM`."""
+
+    def __init__(self, order: int, grams: Dict[Tuple[str, ...], Tuple[float, float]], itos: Sequence[str], blank_idx: int, word_start: str = "▁",
+                 lexicon=None, hotwords=(), spell: Optional[Callable[[str], str]] = None, unk_log10: float = -10.0):
+        if not word_start:
+            raise ValueError("PieceWordNGramLM: word_start is empty")
+        self.itos, self.n_classes, self.blank_idx, self.word_start = list(itos), len(itos), int(blank_idx), word_start
+        if not 0 <= self.blank_idx < self.n_classes:
+            raise ValueError(f"PieceWordNGramLM: the blank {blank_idx} is outside the {self.n_classes} classes")
+        body = lambda tok: tok[len(word_start):] if tok.startswith(word_start) else tok
+        self.piece_kind: List[int] = [0 if c == self.blank_idx else 2 if tok in _SPECIAL or word_start in body(tok) else int(tok.startswith(word_start))
+                                      for c, tok in enumerate(self.itos)]
+        self.unspellable_classes: List[int] = [c for c, k in enumerate(self.piece_kind) if k == 2]
+        spellable = {c for c, k in enumerate(self.piece_kind) if k != 2 and c != self.blank_idx}
+        self.letters: List[str] = sorted({ch for c in spellable for ch in body(self.itos[c])})
+        letter_id = {ch: i for i, ch in enumerate(self.letters)}
+        self.piece_letters: List[Tuple[int, ...]] = [tuple(letter_id[ch] for ch in body(tok)) if c in spellable else () for c, tok in enumerate(self.itos)]
+        unspellable = set()
+
+        def spelled(word: str) -> Optional[Tuple[int, ...]]:
+            text = spell(word) if spell else word
+            if not text or any(ch not in letter_id for ch in text):
+                unspellable.add(word)
+                return None
+            return tuple(letter_id[ch] for ch in text)
+
+        self._compile(order, grams, spelled, unspellable, lexicon, hotwords, unk_log10)
+
+    @classmethod
+    def from_arpa(cls, path: str, itos: Sequence[str], blank_idx: int, word_start: str = "▁", lexicon=None, hotwords=(),
+                  spell: Optional[Callable[[str], str]] = None, unk_log10: float = -10.0) -> "PieceWordNGramLM":
+        """The word LM of an ordinary word-level ARPA file over the sentencepiece classes `itos`.  A word is kept if `spell(word)` (default: the
+        word itself) can be written in the letters of the pieces; n-grams with another word are dropped.  `lexicon`, `hotwords`, `unk_log10`
+        and `dropped` are those of `WordNGramLM.from_arpa`."""
+        order, tables = read_arpa(path)
+        return cls(order, {g: v for t in tables for g, v in t.items()}, itos, blank_idx, word_start, lexicon, hotwords, spell, unk_log10)
+
+    # ---- lookup on the host (what the kernel does on the device tables) ----
+    def step(self, state: int, x: int, c: int) -> WordStep:
+        """Class c (neither the blank nor outside the classes) from the pair (state, x): a piece that starts a word ends the pending one, then
+        its letters walk the trie.  `oov` COUNTS the OOV factors paid here: the word that ended at a node that is no word, and the word that the
+        piece's letters (or a class without a spelling) take out of the trie -- 0, 1 or 2."""
+        c = int(c)
+        if c == self.blank_idx or not 0 <= c < self.n_classes:
+            raise ValueError(f"PieceWordNGramLM.step: class {c} is the blank, or outside the classes")
+        kind, log10, oov, word = self.piece_kind[c], 0.0, 0, None
+        if kind == 1 and x != 0:
+            log10, state, x, ended_oov, word = self.finish(state, x)
+            oov += int(ended_oov)
+        for letter in self.piece_letters[c] if kind != 2 else (-1,):           # a class without a spelling: one letter that no node has an edge for
+            if x < 0:
+                break
+            nxt = [n for cls_, n in self.edges[x] if cls_ == letter]
+            x, oov = (nxt[0], oov) if nxt else (-1, oov + 1)
+        return WordStep(log10, state, x, oov, word)
+
+    # ---- device tables ----
+    def piece_tables(self) -> Dict[str, np.ndarray]:
+        """The numpy tables of ts_ctc_pieces: piece_begin [n_classes + 1], piece_letter, piece_kind [n_classes]."""
+        begin = np.zeros(self.n_classes + 1, np.int32)
+        begin[1:] = np.cumsum([len(p) for p in self.piece_letters])
+        return {"piece_begin": begin, "piece_letter": np.array([x for p in self.piece_letters for x in p], np.int32).reshape(-1),
+                "piece_kind": np.array(self.piece_kind, np.int32)}
+
+    def weights(self, alpha: float, beta: float, oov_score: float = -10.0, hotword_weight: float = 0.0, boosts: Optional[Dict[str, float]] = None,
+                device=None) -> PieceLMWeights:
+        """The device tables of one setting, with the cache and the fixed-address rules of `WordNGramLM.weights`: a NEW setting gets NEW
+        word_factor / oov_factor tensors, so a graph captured under the old setting keeps replaying it; the trie's and the pieces' tables do
+        not depend on the setting and are shared per device."""
+        import torch
+        from . import _lib
+        per_word = self.word_boosts(hotword_weight, boosts)
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("PieceWordNGramLM.weights: GPU tensors required (no CPU fallback)")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        key = (float(alpha), float(beta), float(oov_score), per_word, str(dev))
+        if key not in self._cache:
+            up = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)
+            tables = self.lexicon_tables(oov_score, hotword_weight, boosts)
+            if str(dev) not in self._static:
+                self._static[str(dev)] = ({k: up(tables[k]) for k in ("edge_begin", "edge_class", "edge_next", "node_word", "word_class")},
+                                          {k: up(v) for k, v in self.piece_tables().items()})
+            trie, pieces = self._static[str(dev)]
+            t = dict(trie, word_factor=up(tables["word_factor"]), oov_factor=up(tables["oov_factor"]))
+            st = _lib.CtcLexicon(n_nodes=self.n_nodes, n_edges=int(t["edge_class"].numel()), n_words=len(self.words), delimiter=-1,
+                                 unk_class=self.unk_class, **{k: v.data_ptr() for k, v in t.items()})
+            pc = _lib.CtcPieces(n_classes=self.n_classes, n_letters=len(self.letters), n_piece_letters=int(pieces["piece_letter"].numel()),
+                                **{k: v.data_ptr() for k, v in pieces.items()})
+            self._cache[key] = PieceLMWeights(self.lm.weights(alpha, beta, dev), float(oov_score), per_word, dict(t, **pieces), st, pc)
+        return self._cache[key]
+
+
+def beam_search_piece_lm(logits, lm: PieceWordNGramLM, alpha: float, beta: float, lengths=None, blank_idx: int = 0, beam_width: int = 16,
+                         token_cap: int = 8, n_best: int = 1, score_eos: bool = True, oov_score: float = -10.0, hotword_weight: float = 0.0,
+                         boosts: Optional[Dict[str, float]] = None):
+    """`beam_search_word_lm` for a sentencepiece vocabulary (csrc/ctc_beam_piece_lm.hip): a word ends where a piece that starts the next one
+    follows, and at the end of the clip; score = log(CTC mass of the surviving alignments) + alpha ln 10 log10 P_LM(words [</s>]) + beta
+    (number of words) + oov_score (number of words outside the lexicon) + the boosts of the hot words.  Hypotheses are sequences of pieces: two
+    segmentations of one text are two hypotheses.  Returns a `BeamLMResult`; `lm_scores` is the unweighted log10 LM score of the words."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    from .ctc_align import _logits_f32
+    lg = _logits_f32(logits, "beam_search_piece_lm")
+    b, v, t = lg.shape
+    if b == 0 or t == 0:
+        raise ValueError("beam_search_piece_lm: empty logits")
+    if not isinstance(lm, PieceWordNGramLM):
+        raise TypeError("beam_search_piece_lm: lm must be a PieceWordNGramLM")
+    if lm.n_classes != v or lm.blank_idx != int(blank_idx):
+        raise ValueError(f"beam_search_piece_lm: the LM was compiled for {lm.n_classes} classes with blank {lm.blank_idx}, the logits have {v} with blank {int(blank_idx)}")
+    dev = lg.device
+    il = None if lengths is None else lengths.to(device=dev, dtype=torch.int64).to(torch.int32).contiguous()
+    L = _lib.lib()
+    nbytes = L.ts_ctc_beam_piece_lm_workspace_bytes(b, t, int(beam_width), int(token_cap))
+    if nbytes < 0:
+        _lib.check(int(nbytes), "ts_ctc_beam_piece_lm_workspace_bytes")
+    n_best = int(n_best)
+    if not 1 <= n_best <= int(beam_width):
+        raise ValueError("beam_search_piece_lm: 1 <= n_best <= beam_width required")
+    w = lm.weights(alpha, beta, oov_score, hotword_weight, boosts, dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    tokens = torch.empty(b, n_best, t, dtype=torch.int32, device=dev)
+    frames = torch.empty(b, n_best, t, dtype=torch.int32, device=dev)
+    out_len = torch.empty(b, n_best, dtype=torch.int32, device=dev)
+    scores = torch.empty(b, n_best, dtype=torch.float32, device=dev)
+    lm_scores = torch.empty(b, n_best, dtype=torch.float32, device=dev)
+    counts = torch.empty(b, dtype=torch.int32, device=dev)
+    st = L.ts_ctc_beam_piece_lm_search(lg.data_ptr(), b, v, t, lg.stride(1), None if il is None else il.data_ptr(), int(blank_idx), int(beam_width),
+                                       int(token_cap), n_best, int(bool(score_eos)), C.byref(w.lm.struct), C.byref(w.struct), C.byref(w.pieces),
+                                       tokens.data_ptr(), frames.data_ptr(), out_len.data_ptr(), scores.data_ptr(), lm_scores.data_ptr(),
+                                       counts.data_ptr(), ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(st, "ts_ctc_beam_piece_lm_search")
     return BeamLMResult(tokens, frames, out_len, scores, counts, lm_scores)

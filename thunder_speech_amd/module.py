@@ -434,24 +434,37 @@ class BaseCTCModule(_Base):
     # CTC prefix beam search (no reference counterpart), on the kernels of csrc/ctc_beam.hip (ctc_beam.py).  predict() is untouched.
     def _beam_search_on(self, what: str, logits: Tensor, lengths: Optional[Tensor], n_best: int, beam_width: int, token_cap: int, lm, alpha: float,
                         beta: float, oov_score: float, hotword_weight: float, boosts):
-        """The search that `lm`'s type asks for, on `logits` with their `lengths` (None: every frame): none, the token-level ctc_lm.NGramLM, or
-        the word-level ctc_lm.WordNGramLM with its lexicon and hot words.  `logits` may be a function that returns (logits, lengths): the
-        keywords are checked before it runs."""
+        """The search that `lm`'s type asks for, on `logits` with their `lengths` (None: every frame): none, the token-level ctc_lm.NGramLM, the
+        word-level ctc_lm.WordNGramLM with its lexicon and hot words, or -- for a sentencepiece vocabulary -- ctc_lm.PieceWordNGramLM.  `logits`
+        may be a function that returns (logits, lengths): the keywords are checked before it runs."""
         self._one_language(what)
         from . import ctc_beam as B
         from . import ctc_lm as M
-        blank, word_level = self.text_transform.vocab.blank_idx, isinstance(lm, M.WordNGramLM)
+        vocab = self.text_transform.vocab
+        blank, word_level, piece_level = vocab.blank_idx, isinstance(lm, M.WordNGramLM), isinstance(lm, M.PieceWordNGramLM)
         if word_level:
-            shown = [c for c, tok in enumerate(self.text_transform.vocab.itos) if tok == " " and c != blank]
+            shown = [c for c, tok in enumerate(vocab.itos) if tok == " " and c != blank]
             if not shown or shown[0] != lm.delimiter:
                 raise ValueError(f"{what}: the LM ends a word at class {lm.delimiter}, this module's vocabulary shows " +
                                  (f"class {shown[0]}" if shown else "no class") + " as ' '")
+        elif piece_level:
+            if lm.blank_idx != blank:
+                raise ValueError(f"{what}: the LM was compiled with the blank at class {lm.blank_idx}, this module's blank is class {blank}")
+            differs = [c for c, (mine, its) in enumerate(zip(vocab.itos, lm.itos)) if mine != its]
+            if differs or len(lm.itos) != len(vocab.itos):
+                c = differs[0] if differs else min(len(lm.itos), len(vocab.itos))
+                show = lambda itos: repr(itos[c]) if c < len(itos) else "no such class"
+                raise ValueError(f"{what}: the LM was compiled for another vocabulary: class {c} is {show(lm.itos)} there and {show(vocab.itos)} "
+                                 "in this module")
         elif (oov_score, hotword_weight, boosts) != (-10.0, 0.0, None):
-            raise ValueError(f"{what}: oov_score, hotword_weight and boosts belong to a ctc_lm.WordNGramLM; this search has no lexicon")
+            raise ValueError(f"{what}: oov_score, hotword_weight and boosts belong to a ctc_lm.WordNGramLM or a ctc_lm.PieceWordNGramLM; this "
+                             "search has no lexicon")
         if callable(logits):
             logits, lengths = logits()
         if word_level:
             return M.beam_search_word_lm(logits, lm, alpha, beta, lengths, blank, beam_width, token_cap, n_best, True, oov_score, hotword_weight, boosts)
+        if piece_level:
+            return M.beam_search_piece_lm(logits, lm, alpha, beta, lengths, blank, beam_width, token_cap, n_best, True, oov_score, hotword_weight, boosts)
         if lm is None:
             return B.beam_search(logits, lengths, blank, beam_width, token_cap, n_best)
         return M.beam_search_lm(logits, lm, alpha, beta, lengths, blank, beam_width, token_cap, n_best)
@@ -469,7 +482,9 @@ class BaseCTCModule(_Base):
         With `lm` (a ctc_lm.NGramLM over this module's classes) the n-gram LM is fused into the search on the kernels of
         csrc/ctc_beam_lm.hip: LM weight `alpha`, token bonus `beta`.  With a ctc_lm.WordNGramLM (a word-level LM over a character
         vocabulary) the search is that of csrc/ctc_beam_word_lm.hip: `beta` is a word bonus, `oov_score` what a word outside the lexicon
-        pays, `hotword_weight` the boost of every hot word and `boosts` a hot word's own; only that LM takes these three."""
+        pays, `hotword_weight` the boost of every hot word and `boosts` a hot word's own.  A ctc_lm.PieceWordNGramLM does the same for a
+        sentencepiece vocabulary on csrc/ctc_beam_piece_lm.hip (a word ends where a piece that starts the next one follows); only these
+        two LMs take the three keywords."""
         from . import ctc_align as A
         res = self._beam_search("predict_beam", x, 1, beam_width, token_cap, lm, alpha, beta, oov_score, hotword_weight, boosts)
         ids, counts = A._to_host(res.tokens[:, 0], res.lengths[:, 0])                                                    # one copy
@@ -480,7 +495,8 @@ class BaseCTCModule(_Base):
         """The `n_best` best transcripts of each clip under CTC prefix beam search, best first: text, score (log of the summed probability
         of the transcript's surviving alignments) and per token the frame and time at which it entered the hypothesis.  With `lm` the
         search is the fused one of predict_beam: `score` is the fused score and every hypothesis carries `lm_score`, the unweighted
-        log10 LM score of its tokens (its words, for a WordNGramLM) and </s>."""
+        log10 LM score of its tokens (its words, for a WordNGramLM) and </s>.  A PieceWordNGramLM gives hypotheses of pieces: two
+        segmentations of one text are two hypotheses."""
         from . import ctc_align as A
         from . import ctc_beam as B
         res = self._beam_search("predict_nbest", x, n_best, beam_width, token_cap, lm, alpha, beta, oov_score, hotword_weight, boosts)
@@ -599,7 +615,8 @@ class BaseCTCModule(_Base):
                         token_cap: int = 8, lm=None, alpha: float = 0.5, beta: float = 1.0, oov_score: float = -10.0, hotword_weight: float = 0.0,
                         boosts=None) -> List[str]:
         """One transcript per recording of any length (logits_long).  beam_width None: greedy (the spans of ctc_align.greedy_spans on the
-        stitched logits and their lengths, joined); otherwise the prefix beam search that `lm`'s type asks for, with predict_beam's keywords."""
+        stitched logits and their lengths, joined); otherwise the prefix beam search that `lm`'s type asks for, with predict_beam's keywords.  A
+        ctc_lm.PieceWordNGramLM is taken as there."""
         from . import ctc_align as A
         if beam_width is None:
             if lm is not None or (oov_score, hotword_weight, boosts) != (-10.0, 0.0, None):
