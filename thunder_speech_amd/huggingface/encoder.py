@@ -551,9 +551,14 @@ class Wav2Vec2Plan:
             x_op = y_op if self.prec else y
         return h, x_op
 
-    def forward(self, audio: torch.Tensor, lengths: Optional[torch.Tensor]) -> torch.Tensor:
+    def forward(self, audio: torch.Tensor, lengths: Optional[torch.Tensor], tap=None) -> torch.Tensor:
         """audio [B, n] fp32 on the GPU; lengths = samples per clip when the model was trained with an attention mask
-        (`mask_input`), else None.  Returns last_hidden_state [B, T', C] fp32 (time-major)."""
+        (`mask_input`), else None.  Returns last_hidden_state [B, T', C] fp32 (time-major).
+        tap: `tap(index, h)` is called, in stream order, with each of transformers' num_hidden_layers + 1 `hidden_states` as an f32 [B, T', C]
+        tensor -- post-LN: the output of encoder.layer_norm, then every layer's output; pre-LN: the stream entering layer 0, the un-normalised
+        stream after every layer but the last (an MMS adapter is inside its layer), then encoder.layer_norm of the final stream.  The layers
+        accumulate into the stream in place: what the tap launches must be issued before it returns (audio classification's weighted layer
+        sum, huggingface/classification.py)."""
         if self.feature_extractor_only:
             raise RuntimeError("this Wav2Vec2Plan holds the feature extractor's weights only (feature_extractor_only=True)")
         L = _lib.lib()
@@ -590,6 +595,8 @@ class Wav2Vec2Plan:
             h = hp
             y, x_op = None, None                        # LN(h) for what comes next, when the previous layer's adapter launch computed it
             for i, lw in enumerate(self.layers):
+                if tap is not None:
+                    tap(i, h)                           # the stream entering layer i, before the layer's launches accumulate into it
                 if x_op is None:
                     _, x_op = self._ln(L, stream, h, lw["ln1"], want_f32=False, mx=self.mx)
                 ctx_op = attention(x_op, lw)
@@ -607,8 +614,10 @@ class Wav2Vec2Plan:
                 h = y
             else:
                 h, _ = self._ln(L, stream, h, self.enc_ln, want_op=False)
+            if tap is not None:
+                tap(len(self.layers), h)
             return self._adapter(L, stream, h) if self.adapter else h
-        h, _ = self._post_ln_layers(L, stream, hp, pos_res, attention)
+        h, _ = self._post_ln_layers(L, stream, hp, pos_res, attention, tap)
         return self._adapter(L, stream, h) if self.adapter else h
 
     def _attention(self, L, stream, b, t, key_len):
@@ -646,11 +655,13 @@ class Wav2Vec2Plan:
 
         return attention
 
-    def _post_ln_layers(self, L, stream, hp, pos_res, attention):
+    def _post_ln_layers(self, L, stream, hp, pos_res, attention, tap=None):
         """The post-LN family's chain (wav2vec2-base, hubert, data2vec-audio, wavlm-base, SEW at its squeezed frame rate): encoder.layer_norm over
         hp (+ pos_res) before the layers, a LayerNorm after each residual add inside them.  -> (f32 result, its GEMM-operand copy)."""
         h, h_op = self._ln(L, stream, hp, self.enc_ln, res=pos_res, mx=self.mx)
-        for lw in self.layers:
+        if tap is not None:
+            tap(0, h)
+        for i, lw in enumerate(self.layers):
             # the projections accumulate into the residual stream inside the GEMM; their biases ride in the LayerNorm launch
             ctx_op = attention(h_op, lw)
             self._linear(L, stream, ctx_op, lw["wo"], None, into=h)
@@ -659,6 +670,8 @@ class Wav2Vec2Plan:
             _, f1_op = self._linear(L, stream, h_op, lw["w1"], lw["b1"], act=1, want_op=True)
             self._linear(L, stream, f1_op, lw["w2"], None, into=h)
             h, h_op = self._ln(L, stream, h, lw["ln2"], xbias=lw["b2"], mx=self.mx)
+            if tap is not None:
+                tap(i + 1, h)
         return h, h_op
 
     def _adapter(self, L, stream, h: torch.Tensor) -> torch.Tensor:

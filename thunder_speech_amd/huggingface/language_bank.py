@@ -5,7 +5,12 @@ vocabulary.  `LanguageBank` holds `capacity` such packs as plain tensors at fixe
 names its language through one id buffer that the kernels read at run time.  Adding, removing and selecting write in place, so a captured
 graph keeps serving whatever the mix of languages in the batch.  The public surface is BaseCTCModule's (language_bank, language_bank_add,
 language_bank_load, language_bank_remove, language_bank_names, select_languages, selected_languages, predict_languages); the module owns the
-head and the text transforms, the encoder's plan reads the adapters (Wav2Vec2Plan._attn_adapter), both through the bank's `ids`."""
+head and the text transforms, the encoder's plan reads the adapters (Wav2Vec2Plan._attn_adapter), both through the bank's `ids`.
+
+Who fills in the ids: `language_router` attaches an audio classifier (huggingface/classification.py: the MMS language-identification checkpoints)
+whose head writes every clip's slot into `ids` on the device (ts_seq_cls_head's `slot` output), so `predict_auto` replays ONE graph -- classifier,
+then ASR -- with no host work in between.  Out of scope: a confidence threshold or fallback policy for the router; LM fusion, alignment and
+long-form transcription under a routed selection (refused as under any mixed selection)."""
 from __future__ import annotations
 
 import json
@@ -212,6 +217,7 @@ def add(module, lang: str, adapter_sd: Dict[str, torch.Tensor], tokens: Sequence
     slot = bank.names.index(None)
     bank.write_slot(slot, lang, [adapter_sd[k] for k in want if k.startswith(prefix)], adapter_sd["lm_head.weight"], adapter_sd["lm_head.bias"],
                     transform)
+    _rewrite_router(module)                                         # the classes mapped to `lang` route to its slot from now on
     return slot
 
 
@@ -241,10 +247,153 @@ def remove(module, lang: str) -> None:
         bank.selection = [None if n == lang else n for n in bank.selection]
         bank.write_ids()
     bank.clear_slot(slot)
+    _rewrite_router(module)                                         # the classes mapped to `lang` route to the resident language again
 
 
 def names(module) -> List[str]:
     return [n for n in _bank(module, "language_bank_names").names if n is not None]
+
+
+# ---- the router: an audio classifier fills in the ids (huggingface/classification.py, thunder_speech_amd/seq_cls.h) ---------------------------
+class LanguageRouter:
+    """An AudioClassifierModule next to a bank: `mapping` {classifier label: bank language}; class_slot int32 [n_labels] on the bank's device:
+    the slot of the language a class is mapped to, -1 for a class of a language the bank does not hold (or of no language).  The table is
+    rewritten IN PLACE whenever the bank's languages change, so a captured graph routes to a language added after its capture."""
+
+    def __init__(self, classifier, mapping: Dict[str, str], bank: LanguageBank):
+        self.classifier, self.mapping = classifier, dict(mapping)
+        self.class_slot = torch.full((len(classifier.labels),), -1, dtype=torch.int32, device=bank.device)
+        self.scratch = torch.full((LORA_BANK_MAX_CLIPS,), -1, dtype=torch.int32, device=bank.device)      # identify_languages' slots
+        self.rewrite(bank)
+
+    def rewrite(self, bank: LanguageBank) -> None:
+        host = torch.full((len(self.classifier.labels),), -1, dtype=torch.int32)
+        for i, label in enumerate(self.classifier.labels):
+            lang = self.mapping.get(label)
+            if lang is not None and lang in bank.names:
+                host[i] = bank.names.index(lang)
+        if self.class_slot.device != bank.device:                   # the bank moved: new addresses (the auto graphs are retired by the epoch)
+            self.class_slot, self.scratch = self.class_slot.to(bank.device), self.scratch.to(bank.device)
+        self.class_slot.copy_(host)
+
+
+def _rewrite_router(module) -> None:
+    router = module.__dict__.get("_language_router")
+    if router is not None:
+        router.rewrite(module.__dict__["_language_bank"])
+
+
+def _router(module, what: str) -> LanguageRouter:
+    _bank(module, what)
+    router = module.__dict__.get("_language_router")
+    if router is None:
+        raise RuntimeError(f"{what}: this module has no language router (language_router() attaches a classifier)")
+    return router
+
+
+def attach_router(module, classifier, mapping: Optional[Dict[str, str]] = None) -> None:
+    bank = _bank(module, "language_router")
+    from .classification import AudioClassifierModule
+    if not isinstance(classifier, AudioClassifierModule):
+        raise TypeError(f"language_router: the classifier must be an AudioClassifierModule, got {type(classifier).__name__}")
+    if int(classifier.sample_rate) != int(module.sample_rate):
+        raise ValueError(f"language_router: the classifier takes waveforms at {classifier.sample_rate} Hz, the module at {module.sample_rate} Hz; "
+                         "both read the same batch")
+    if mapping is None:
+        mapping = {label: label for label in classifier.labels}
+    else:
+        unknown = [k for k in mapping if k not in classifier.labels]
+        if unknown:
+            raise KeyError(f"language_router: the mapping names labels the classifier does not have: {unknown[:5]} (it has {len(classifier.labels)}: "
+                           f"{', '.join(classifier.labels[:5])}, ...)")
+        bad = [(k, v) for k, v in mapping.items() if not isinstance(v, str) or not v]
+        if bad:
+            raise ValueError(f"language_router: the mapping's languages must be non-empty strings, got {bad[:3]}")
+    module.__dict__["_language_router"] = LanguageRouter(classifier, mapping, bank)
+    module.__dict__.pop("_auto_graphs", None)
+
+
+def _check_auto(module, what: str, x: torch.Tensor):
+    """(bank, router) of a routed forward of the batch `x`; the refusals by name, before any device work."""
+    router = _router(module, what)
+    bank = check_forward(module, x)
+    router.classifier._check_forward()
+    return bank, router
+
+
+def identify(module, x: torch.Tensor) -> List[Optional[str]]:
+    bank, router = _check_auto(module, "identify_languages", x)
+    clf = router.classifier
+    if router.class_slot.device != bank.device:
+        router.rewrite(bank)
+    b = int(x.shape[0])
+    xx = clf._prepare(x)
+    lengths = torch.full((b,), x.shape[-1], dtype=torch.int32, device=xx.device)
+    with torch.no_grad():
+        clf._run(xx, lengths, class_slot=router.class_slot, slot=router.scratch)
+    return [bank.names[s] if 0 <= s < bank.capacity else None for s in router.scratch[:b].tolist()]
+
+
+def auto_forward(module, x: torch.Tensor):
+    """One replay of the routed graph of x's signature (captured on first use): the classifier's front end, encoder, pool and head -- the head
+    writes every clip's slot into bank.ids[:B] -- then the module's front end, encoder with the bank's adapters, ts_mms_lang_bank_head_fwd and
+    the greedy decode; no host work between the two encoders.  -> (logits, output lengths, packed): the graph's OWN buffers; packed int32 =
+    collapsed [B * T'], counts [B], ids [B] for one device-to-host read.  The bank's id buffer holds the ROUTED slots afterwards: the caller
+    restores the selection (bank.write_ids())."""
+    from ..module import greedy_decode
+    from ..utils import GraphedForward
+    bank, router = _check_auto(module, "predict_auto", x)
+    clf = router.classifier
+    if router.class_slot.device != bank.device:
+        router.rewrite(bank)
+    xx = clf._prepare(x)                                            # refreshes the head's operands and the soft-maxed layer weights
+    b = int(xx.shape[0])
+    lengths = torch.full((b,), xx.shape[-1], dtype=torch.int32, device=xx.device)
+
+    def run(x_in, ll):
+        clf._run(x_in, ll, class_slot=router.class_slot, slot=bank.ids)
+        logits, out_lengths = module._forward_eager(x_in, ll)
+        _, collapsed, counts = greedy_decode(logits)
+        return logits, out_lengths, torch.cat((collapsed.reshape(-1), counts.reshape(-1), bank.ids[:b]))
+
+    if torch.cuda.is_current_stream_capturing():                    # the caller records its own graph: launch into it
+        with torch.no_grad():
+            return run(xx, lengths)
+    # a table of its own: _graphed_inference and its stamp stay as they are.  The stamp covers both modules' weights and the classifier's
+    # device operands (operand_epoch moves whenever _refresh, called by _prepare above, allocated the head's operands or the soft-max buffer
+    # anew -- after clf.eval() or clf.to(), which change no parameter); the bank's tensors, the class_slot table and the soft-maxed layer
+    # weights are written in place and retire nothing
+    stamp = (module._weights_stamp(), clf._weights_stamp() - clf._layer_weights_version(), clf.encoder.precision, clf.operand_epoch, id(router),
+             router.class_slot.data_ptr(), bank.ids.data_ptr())
+    graphs = module.__dict__.get("_auto_graphs")
+    if graphs is None or graphs[0] != stamp:
+        # recorded on the module's capture stream, as _graphed_inference's graphs: the launch arena is keyed by stream
+        streams = module.__dict__.setdefault("_infer_streams", {})
+        side = streams.get(str(xx.device))
+        if side is None:
+            side = streams[str(xx.device)] = torch.cuda.Stream(device=xx.device)
+        graphs = module.__dict__["_auto_graphs"] = (stamp, GraphedForward(run, stream=side))
+    return graphs[1](xx, lengths)
+
+
+def predict_auto(module, x: torch.Tensor):
+    bank = module.__dict__.get("_language_bank")                   # auto_forward makes the checks, by name, before any device work
+    try:
+        with torch.no_grad():
+            logits, _, packed = auto_forward(module, x)
+        b, t = int(logits.shape[0]), int(logits.shape[2])
+        host = packed.to("cpu")                                     # the one device-to-host read
+    finally:
+        if bank is not None:
+            bank.write_ids()                                        # the selection of select_languages holds again
+    collapsed, counts, ids = host[: b * t].view(b, t), host[b * t: b * t + b], host[b * t + b:].tolist()
+    slots = [s if 0 <= s < bank.capacity and bank.names[s] is not None else 0 for s in ids]
+    texts: List[Optional[str]] = [None] * b
+    for s in sorted(set(slots)):
+        idx = [i for i, si in enumerate(slots) if si == s]
+        for i, text in zip(idx, bank.transforms[s].decode_collapsed(collapsed[idx], counts[idx])):
+            texts[i] = text
+    return texts, [bank.names[s] for s in slots]
 
 
 def select(module, langs) -> None:

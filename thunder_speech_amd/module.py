@@ -114,6 +114,7 @@ class BaseCTCModule(_Base):
         self.__dict__.pop("_infer_graphs", None)
         self.__dict__.pop("_graph_auto", None)
         self.__dict__.pop("_frozen_head", None)
+        self.__dict__.pop("_auto_graphs", None)                    # predict_auto's table (huggingface/language_bank.py)
 
     def train(self, mode: bool = True):
         self.reset_inference_graphs()
@@ -336,6 +337,28 @@ class BaseCTCModule(_Base):
             return self.predict(x)
         finally:
             self.select_languages(previous)
+
+    def language_router(self, classifier, mapping: Optional[Dict[str, str]] = None) -> None:
+        """Attach an AudioClassifierModule (huggingface/classification.py: an MMS language-identification checkpoint) that picks every clip's
+        language on the device.  `mapping`: {classifier label: bank language}, default the identity.  Classes of languages the bank does not
+        hold route to the resident language; language_bank_add / language_bank_remove rewrite the routing table in place, so a captured graph
+        routes to a language added after its capture.  Refused by name: no bank, a mapping that names a label the classifier does not have,
+        differing sample rates."""
+        from .huggingface import language_bank as LB
+        LB.attach_router(self, classifier, mapping)
+
+    def identify_languages(self, x: Tensor) -> List[Optional[str]]:
+        """The routed language of every clip: the bank language of the classifier's most probable class among the classes mapped to a language
+        in the bank; None when there is no such class (the resident language serves the clip)."""
+        from .huggingface import language_bank as LB
+        return LB.identify(self, x)
+
+    def predict_auto(self, x: Tensor) -> Tuple[List[str], List[str]]:
+        """(texts, languages): predict(x) with every clip served by the language the attached classifier routes it to, and that language.  One
+        captured graph per input signature holds the classifier and the ASR forward; the classifier's head writes the slots into the bank's id
+        buffer on the device, so no host work happens between the two encoders.  The selection that held before the call holds again after."""
+        from .huggingface import language_bank as LB
+        return LB.predict_auto(self, x)
 
     def _one_language(self, what: str) -> None:
         """`what` turns text into ids, or carries an LM, of one language: refused by name while any clip selects a non-resident language."""
